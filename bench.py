@@ -2,7 +2,7 @@
 """Headline benchmark: active-voxels/sec, forward + backward of the ScanNet U-Net backbone (BASELINE.json configs[1]):
 ~150k active voxels per scene, 32->64->128->256 channels, 3^3 submanifold + 2^3/2 conv/deconv, fp32.
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg5] [--dtype f32|bf16]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg5] [--dtype f32|bf16] [--dump-outputs DIR]
 
 N > 1, either way:
   * `python bench.py --gpus N ...` with no torchrun environment: this process makes NO GPU call and starts N fresh child
@@ -81,6 +81,15 @@ def parse_args(argv=None):
     ap.add_argument("--forward-only-child", action="store_true",
                     help="(internal) evaluation only, in this fresh process: forward_only steps of the workload, nothing else ever "
                          "allocated -- prints one JSON line with its time and peak HBM (the parent's `forward_only.fresh_process`)")
+    ap.add_argument("--lr", type=float, default=0.0,
+                    help="SGD learning rate of the timed step (default 0: the update still runs in full -- one pass over "
+                         "every parameter and its gradient -- but the parameters keep their values).  The synthetic upstream "
+                         "gradient is the same every step, so any lr > 0 drives the weights along one direction until they "
+                         "overflow: at 1e-6, the cfg2 step's outputs, gradients and parameters were all NaN by step 20")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (backbone output, mask logits, RPN "
+                         "outputs, input-feature gradient, parameter gradients, updated parameters) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (rank 0; a fixed seeded sample of an array above its share)")
     a = ap.parse_args(argv)
     if a.bf16_all:
         a.dtype = "bf16"
@@ -249,7 +258,7 @@ def run(args):
 
     # one balanced scene per rank (cfg 2: seed 1; cfg 4 style: seeds 10+rank)
     seed = 1 if world == 1 else 10 + rank
-    job = SceneStep(args.workload, dev, dtype=args.dtype, prefetch=args.prefetch, seed=seed, grad_seed=100 + rank,
+    job = SceneStep(args.workload, dev, dtype=args.dtype, prefetch=args.prefetch, seed=seed, grad_seed=100 + rank, lr=args.lr,
                     target=args.target, batches_per_step=args.batches_per_step, n_buckets=args.buckets)
 
     # Kernel timing: HIP events on the launch stream around the launches of the dominant kernel on 3-4 steps spread over the
@@ -305,6 +314,8 @@ def run(args):
     sampled = max(1, timer.sampled_steps)
     L.lib().scn_conv_tiles_path_counts(paths, 0)
     dt_local = dt
+    # before any side leg runs another step: the outputs of the LAST TIMED step, as its caller would receive them
+    dumped = dump_outputs(job, args.dump_outputs, torch) if (args.dump_outputs and rank == 0) else None
 
     red_dev = dev if (world == 1 or backend == "nccl") else "cpu"
     tmax = torch.tensor([dt], dtype=torch.float64, device=red_dev)
@@ -369,6 +380,8 @@ def run(args):
                                   "64-bit-addressing fallback above 2^23 rows / 4 GB slabs"} if args.dtype == "f32" else None,
         }
         out.update(extras)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if ks:
             dom = max((k for k in ks if k in dom_names), key=lambda k: ks[k]["ms"], default=max(ks, key=lambda k: ks[k]["ms"]))
             d = ks[dom]
@@ -392,6 +405,45 @@ def run(args):
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_ELEMS_PER_ARRAY = 2 << 20          # float32 elements: 8 MB per array, at most 7 arrays -> 56 MB in all
+
+
+def dump_outputs(job, out_dir, torch):
+    """--dump-outputs DIR: what the last timed step handed its caller, copied to the host after the timed region (nothing
+    of it is timed): the backbone output features, the mask logits and the RPN's box deltas / scores (workloads that have
+    them), the gradient of the input features, the parameter gradients and the parameters after the SGD update (both in
+    FlatParams order, flattened).  Inputs, parameters and upstream gradients are seeded, so the same arguments give the same
+    arrays on every run and every build.  An array above DUMP_ELEMS_PER_ARRAY elements is written as a sample: its
+    flattened elements at a fixed set of positions (seed 0, sorted), the same positions for the same size.
+    -> {name: {"shape": full shape, "sampled": bool}}"""
+    import numpy as np
+    arrays = {"output_features": job.out.features}
+    if job.logits is not None:
+        arrays["mask_logits"] = job.logits
+    if job.rpn_out is not None:
+        arrays["rpn_bbox"], arrays["rpn_score"] = job.rpn_out[0], job.rpn_out[1]
+    if job.fin is not None and job.fin.grad is not None:
+        arrays["input_features_grad"] = job.fin.grad
+    fp = job.flat
+    if fp.flat_grad_valid:                   # the packed path (all-reduce): the mean gradient the update used
+        arrays["param_grads"] = fp.mean_grad()
+    else:                                    # single rank: the gradients where autograd left them
+        arrays["param_grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                                           for p in fp.params])
+    arrays["params"] = fp.flat
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        shape, sampled = list(a.shape), a.size > DUMP_ELEMS_PER_ARRAY
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_ELEMS_PER_ARRAY, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = {"shape": shape, "sampled": bool(sampled)}
+    return {"dir": os.path.abspath(out_dir), "arrays": info}
 
 
 def roofline(dom, d, sampled, args):
@@ -565,7 +617,7 @@ def bf16_side_leg(args, dev, torch):
     parameters), a short run outside the timed region, with the roofline of ITS dominant kernel (k_conv_tb: HBM-bound)."""
     from sparse_rcnn_amd import profiling
     from sparse_rcnn_amd.trainstep import SceneStep
-    job = SceneStep("cfg2", dev, dtype="bf16", prefetch=args.prefetch, seed=1, grad_seed=100)
+    job = SceneStep("cfg2", dev, dtype="bf16", prefetch=args.prefetch, seed=1, grad_seed=100, lr=args.lr)
     n, warm = max(10, min(40, args.steps)), 10
     timer = profiling.KernelTimer(every=max(5, n // 2), names={"k_conv_tb"})
     for _ in range(warm):

@@ -1074,3 +1074,37 @@ def test_bench_self_launch_five_ranks_detection_and_mask_step_on_one_gpu(gpu):
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     assert "rank 3 exited with code 3" in r.stderr and not [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert took < 240, took                      # (start-up of five processes dominates; the survivors do not wait for a time limit)
+
+
+def test_bench_dump_outputs_of_the_timed_step_are_reproducible(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR`: after exactly --steps timed steps the last one's outputs land in DIR as float32 .npy
+    (within 64 MB), the line reports ms_per_step, and a second run with the same arguments computes the same arrays.  The
+    cfg2 scene at full size and 35 steps in all: at the old default lr of 1e-6 the step was all NaN by step 20."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    runs = []
+    for tag in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+               "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path / tag)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 30 and d["ms_per_step"] > 0 and d["config"]["lr"] == 0.0
+    info = d["dump_outputs"]["arrays"]
+    assert {"output_features", "input_features_grad", "param_grads", "params"} <= set(info)
+    assert info["output_features"]["shape"][1] == 32 and info["output_features"]["sampled"]     # 150 k x 32: above its share
+    assert info["input_features_grad"]["shape"][1] == 7 and not info["input_features_grad"]["sampled"]
+    total = 0
+    for name, meta in info.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        total += a.nbytes
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), name
+        if not meta["sampled"]:
+            assert list(a.shape) == meta["shape"], name
+        scale = max(float(np.abs(a).max()), 1e-30)
+        assert float(np.abs(a - b).max()) / scale <= FEAT_TOL, name
+    assert total <= 64 * 2 ** 20
