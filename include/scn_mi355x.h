@@ -59,7 +59,9 @@ extern "C" {
  *      scn_parent_lookup_div, scn_topk_boxes / scn_topk_scratch_bytes, scn_cell_map (117 entry points) */
 /*   5  round 6: + scn_conv_tiles_chain / scn_conv_tiles_chain_counts, scn_wgrad_tiles32 / _scratch_bytes (121 entry points); scn_tiles_build_x: bits 8-10 of `with_x`
  *      = log2 of the row bins in the sort key of a 27-offset table (0: as before); scn_pyramid_build_ex with
- *      SCN_PYRAMID_XCD_ORDER sorts level 0 by (row bin, mask); switches SCN_TS_PROG, SCN_TS_NO_CHAIN, SCN_TB_NO_BINS */
+ *      SCN_PYRAMID_XCD_ORDER sorts level 0 by (row bin, mask); switches SCN_TS_PROG, SCN_TS_NO_CHAIN, SCN_TB_NO_BINS;
+ *      additive within 5: + scn_adam_many / scn_adam_launches / scn_adam_segment_bytes, struct scn_adam_segment (124 entry
+ *      points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -751,6 +753,50 @@ int64_t scn_wgrad_tiles32_scratch_bytes(void);
 int scn_wgrad_tiles32(const float* X, int64_t n_in, const float* dY, int64_t n_out, const int32_t* tstab,
                       const uint32_t* tile_mask, const int32_t* perm, const int64_t* prefix_host, float* dW, void* scratch,
                       int relu_in, scn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Adam / AdamW update (scn_optim.hip): the reference's optimizer, `optim.Adam(learnable_parameter, lr=4e-4)`
+ * (scannet_config/run.py:403-416,1449), stepped once per `batches_per_step` micro-batches (training.py:458-460).
+ *
+ * One call updates a list of fp32 segments.  Per element, in this order, every operation rounded once (correctly rounded
+ * division and square root; fma(a, b, c) = a * b + c rounded once, where torch's compiled GPU kernels fuse it, and no
+ * other contraction) -- torch.optim.Adam's single-tensor, non-capturable step as torch's GPU kernels compute it:
+ *   g  = g_raw * grad_scale;  if (weight_decay != 0) g = fma(weight_decay, p, g)        (coupled decay: Adam)
+ *   p  = p * decay                                                                    (decoupled decay: AdamW; 1 = none)
+ *   m  = w < 0.5 ? fma(w, g - m, m) : fma(-(g - m), 1 - w, g),   w = 1 - beta1          (torch's lerp)
+ *   v  = fma(1 - beta2, g * g, v * beta2)
+ *   p  = fma(-step_size, m / (sqrt(v) * inv_bc2_sqrt + eps), p)
+ * g is read only.  The per-segment constants are computed by the caller in double and rounded to float:
+ * step_size = lr / (1 - beta1^t), inv_bc2_sqrt = 1 / sqrt(1 - beta2^t) (t: the segment's step count AFTER this update;
+ * torch divides by a host scalar as a multiplication by its reciprocal),
+ * decay = 1 - lr * weight_decay for AdamW (then weight_decay = 0 here).  beta1, beta2, eps and grad_scale are rounded to
+ * float in the library, 1 - beta1 and 1 - beta2 in double first.
+ * Alignment: every pointer 4-byte aligned; a segment whose four pointers share their address modulo 16 runs 16-byte accesses
+ * after a scalar head, any other runs scalar (same results).  Segments must not overlap one another.
+ * The segment table is copied into the kernel arguments (at most 80 segments and 4 distinct constant sets per launch,
+ * `scn_adam_launches` tells how many launches a table takes): no device table, no host wait, the table may be reused as soon
+ * as the call returns.  SCN_EINVAL (nothing launched): segs NULL with n_segs > 0, n < 0, a NULL pointer with n > 0, a pointer
+ * not 4-byte aligned, a non-finite beta / eps / grad_scale / step_size / inv_bc2_sqrt / weight_decay / decay,
+ * inv_bc2_sqrt <= 0.
+ * Segments with n == 0 are skipped. */
+typedef struct scn_adam_segment {
+    float* p;                        /* parameters [n], updated */
+    const float* g;                  /* gradient [n] (scaled by grad_scale) */
+    float* m;                        /* first moment [n], updated */
+    float* v;                        /* second moment [n], updated */
+    int64_t n;
+    float step_size;                 /* lr / (1 - beta1^t) */
+    float inv_bc2_sqrt;              /* 1 / sqrt(1 - beta2^t) */
+    float weight_decay;              /* coupled weight decay; 0: none */
+    float decay;                     /* decoupled weight decay factor 1 - lr * weight_decay; 1: none */
+} scn_adam_segment;
+
+/* sizeof(scn_adam_segment) (56): lets a binding check its layout. */
+int64_t scn_adam_segment_bytes(void);
+/* *launches = the number of kernel launches scn_adam_many makes for this table (validates it as scn_adam_many does). */
+int scn_adam_launches(const scn_adam_segment* segs, int n_segs, int* launches);
+int scn_adam_many(const scn_adam_segment* segs, int n_segs, double grad_scale, double beta1, double beta2, double eps,
+                  scn_stream_t stream);
 
 #ifdef __cplusplus
 }

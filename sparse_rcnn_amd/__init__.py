@@ -16,6 +16,7 @@ from .modules import (AddTable, AveragePooling, BatchNormLeakyReLU, BatchNormReL
                       Sequential, SparseToDense, SubmanifoldConvolution, set_feature_storage)
 from .tensor import SparseConvNetTensor                                    # noqa: F401
 from .custom_operations import SparseGlobalPool, split_batch               # noqa: F401  (device forms of the reference's own helpers)
+from . import optim                                                         # noqa: F401  (optim.Adam: the reference's optimizer)
 
 __all__ = [
     "Metadata", "SparseConvNetTensor", "ioLayers", "InputLayer", "OutputLayer", "Sequential", "ConcatTable",

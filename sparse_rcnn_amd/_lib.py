@@ -140,6 +140,9 @@ _SIGS = {
     "scn_exec_timing_collect": (i64, [p, p, i64]),
     "scn_sparse_to_dense_fwd": (C.c_int, [p, p, i64, i32, C.POINTER(i64), p, p]),
     "scn_sparse_to_dense_bwd": (C.c_int, [p, p, i64, i32, C.POINTER(i64), p, p]),
+    "scn_adam_segment_bytes": (i64, []),
+    "scn_adam_launches": (C.c_int, [p, i32, C.POINTER(i32)]),
+    "scn_adam_many": (C.c_int, [p, i32, C.c_double, C.c_double, C.c_double, C.c_double, p]),
 }
 
 EXPORTS = tuple(_SIGS)

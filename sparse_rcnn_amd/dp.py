@@ -271,6 +271,29 @@ class FlatParams:
         else:                                   # (the views into `flat` are made once: `p.data` builds a tensor per access)
             torch._foreach_add_(self._datas, grads, alpha=-lr)
 
+    def adam_step(self, adam):
+        """Adam update (an `optim.FlatAdam`) from the all-reduced mean gradient, the Adam form of sgd_step: one launch over
+        `flat` / `flat_grad` with the moments aligned to `flat`, grad_scale folded into the launch as sgd_step folds it
+        into alpha.  EVERY parameter counts as having a gradient on this path -- zeros where no rank produced one, as
+        gather_grads fills them -- so all step counts and moments advance together and the ranks stay in lockstep.  (The
+        one-rank fast path of adam_step_single_rank skips a None gradient instead, as torch.optim.Adam does: the two differ
+        only for a parameter that got no gradient, e.g. mask-branch weights after an empty ROI crop.)"""
+        adam.step_flat(self)
+
+    def adam_step_single_rank(self, adam):
+        """all_reduce_mean + adam_step, or for ONE rank without a process group the fast path: the update reads the
+        gradients where autograd left them (one segment per parameter, no packing; `flat_grad_valid` False).  On the fast
+        path a parameter whose `.grad` is None is skipped and its step count does not advance, as in torch.optim.Adam;
+        the packed path (adam_step) advances every parameter instead."""
+        if self.buckets or os.environ.get("SCN_STEP_PACKED") or _dist_on(2) or self.rank_weight != 1.0:
+            self.all_reduce_mean()
+            self.adam_step(adam)
+            return
+        self.flat_grad_valid = False
+        if self._datas[0].data_ptr() != self.params[0].data_ptr() or self._datas[-1].data_ptr() != self.params[-1].data_ptr():
+            self._datas = [p.data for p in self.params]
+        adam.step_params(self._datas, [p.grad for p in self.params])
+
 
 def broadcast_params(fp: FlatParams, src: int = 0):
     if _dist_on(2):

@@ -1,6 +1,7 @@
 """One data-parallel training step of the sparse path on one rank: what ``bench.py`` times and the at-size parity tests
 check.  A step = index build (InputLayer rules + every rulebook; rebuilt per batch as in the reference) + forward +
-backward to every parameter and the input features + all-reduce of the flat gradient buffer (RCCL / gloo, N > 1) + SGD.
+backward to every parameter and the input features + all-reduce of the flat gradient buffer (RCCL / gloo, N > 1) + SGD
+(or, `optimizer="adam"`, the reference's Adam: optim.FlatAdam).
 
 Workloads (BASELINE.json configs; SURVEY.md §8d synthetic inputs):
   cfg2  configs[1]  one ~150k-voxel scene, U-Net backbone 32-64-128-256
@@ -109,8 +110,11 @@ class SparseStepModel(torch.nn.Module):
 
 class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
-                 target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1):
-        """batches_per_step: micro-batches whose gradients are accumulated before ONE all-reduce + update, each scaled by
+                 target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
+        1449: the fused Adam launch of optim.FlatAdam with `betas`, `eps`, `weight_decay`; lr=None -> the reference's 4e-4).
+        batches_per_step: micro-batches whose gradients are accumulated before ONE all-reduce + update, each scaled by
         1 / batches_per_step -- the reference's `(loss / batches_per_step).backward()` ... `optimizer.step()`
         (ndsis/training/training.py:436,458-460; 2 or 6 with the mask head, scannet_config/run.py:377-396).  Micro-batch k
         is its own scene (seed + 1000 k); all but the last run under `FlatParams.accumulate()`.
@@ -123,7 +127,13 @@ class SceneStep:
         # step: the SAME synthetic gradient on 3.7 M RPN outputs every step is a steady push, not noise -- at 1e-6 the score
         # field grows 4 % per step and overflows within a bench run (profiles/r5_rpn_stats.txt); the update itself (one SGD
         # pass over the flat buffer) is the same work.  An explicit lr is used as given.
-        self.lr = (1e-8 if workload.endswith("-rpn") else 1e-6) if lr is None else float(lr)
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError("optimizer: sgd | adam")
+        self.optimizer = optimizer
+        if optimizer == "adam":
+            self.lr = 4e-4 if lr is None else float(lr)
+        else:
+            self.lr = (1e-8 if workload.endswith("-rpn") else 1e-6) if lr is None else float(lr)
         if weighting not in ("equal", "count"):
             raise ValueError("weighting: equal | count")
         self.weighting = weighting
@@ -161,6 +171,10 @@ class SceneStep:
             self._init_rpn()
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
+        self.adam = None
+        if optimizer == "adam":
+            from .optim import FlatAdam
+            self.adam = FlatAdam(self.flat, lr=self.lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self._gen = torch.Generator(device="cpu").manual_seed(grad_seed)
         self._gys, self._gms, self._grs = {}, {}, {}
         self._gm_pool = None
@@ -331,6 +345,14 @@ class SceneStep:
             with self.flat.accumulate():
                 self.forward_backward(k, zero=(k == 0))
         self.forward_backward(n - 1, zero=(n == 1))       # the last micro-batch: bucket hooks armed, slices go out
+        if self.adam is not None:
+            self.adam.lr = self.lr
+            if self.weighting == "count":
+                self.flat.all_reduce_mean(total_weight=self._total_weight)
+                self.flat.adam_step(self.adam)
+            else:
+                self.flat.adam_step_single_rank(self.adam)
+            return
         if self.weighting == "count":
             self.flat.all_reduce_mean(total_weight=self._total_weight)
             self.flat.sgd_step(self.lr)
@@ -380,8 +402,14 @@ class SceneStep:
         if self.batches_per_step > 1:
             s += (f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
                   "voxels = all of them")
-        s += (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + plain SGD on the flat parameter buffer, lr {self.lr:g} "
-              "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)")
+        if self.adam is not None:
+            a = self.adam
+            s += (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + Adam (the reference's optimizer, scannet_config/run.py:"
+                  f"1449) on the flat parameter buffer, lr {self.lr:g}, betas ({a.betas[0]:g}, {a.betas[1]:g}), eps {a.eps:g}, "
+                  f"weight decay {a.weight_decay:g}: one fused update launch per <= 80 tensors")
+        else:
+            s += (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + plain SGD on the flat parameter buffer, lr {self.lr:g} "
+                  "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)")
         if self.prefetch:
             s += "; rulebooks of batch i+1 built on a helper thread during batch i"
         return s
