@@ -3,16 +3,21 @@
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline``
 leg may import this module.  The product path (``sparse_rcnn_amd``) never does.
 
-PARITY UNPINNED for the sparse-convolution arithmetic: that arithmetic lives in
-the third-party package ``facebookresearch/SparseConvNet`` (imported by the
-reference as ``sparseconvnet``; no version pinned, README.md:23-31), which is
-neither under /root/reference nor installed here, and the reference holds no
-tests or golden vectors for it.  What pins this restatement
-instead: (i) every operator below is checked against the dense ``torch.nn.functional``
-twin the reference itself pairs it with (module_factory.py:96-112, 231-239,
-255-264, 365-372, 402-412) in ``tests/test_oracle_dense.py``; (ii) the ROI crop
-(the one piece of hot-path arithmetic the reference owns) IS pinned by golden
-vectors generated from the reference's own ``roi_cut`` (``tests/golden/``).
+The sparse-convolution arithmetic lives in the third-party package
+``facebookresearch/SparseConvNet`` (imported by the reference as
+``sparseconvnet``; no version pinned, README.md:23-31), which the reference
+does not ship, and the reference holds no tests or golden vectors for it
+(SURVEY.md §8c).  What pins this restatement instead: (i) every operator below
+is checked against the dense ``torch.nn.functional`` twin the reference pairs it
+with (module_factory.py:96-112, 231-239, 255-264, 365-372, 402-412) in
+``tests/test_oracle_dense.py``; (ii) the same operators are checked against
+fixtures produced by running the reference's OWN dense-mode layers on a
+densified scene (``tests/test_dense_twin_golden.py``), forward and every
+gradient; (iii) the ROI crop (the one piece of hot-path arithmetic the
+reference owns) is pinned by golden vectors generated from the reference's own
+``roi_cut`` (``tests/golden/``).  Not pinned: SparseConvNet's own conventions
+(offset enumeration, weight layout, rule order) -- the mappings from torch's
+layouts are this repository's.
 
 Index work is numpy (integer exact); feature work is torch-CPU fp32, organised
 the way the SparseConvNet CPU path is: per kernel offset gather rows ->
@@ -555,6 +560,78 @@ class _RoundBF16(torch.autograd.Function):
 def bf16_storage(t):
     """Round to bf16 and widen back (value as stored by the bf16 storage path); gradient passes straight through."""
     return _RoundBF16.apply(t)
+
+
+# --------------------------------------------------------------------------
+# N3: the dense RPN stack  (rpn.DenseRpn; module_factory.py:581-611
+#     get_dilation_network, anchor_network.py:73-124 AnchorNetworkConv)
+# --------------------------------------------------------------------------
+
+def _cl_apply(fn, h):
+    """fn on the channels-last rows [B X Y Z, C] of an NCDHW volume (the layout of the HIP path's slabs and of the
+    sign masks it records), back to NCDHW."""
+    B, C = h.shape[:2]
+    rows = fn(h.permute(0, 2, 3, 4, 1).reshape(-1, C))
+    return rows.view(B, *h.shape[2:], C).permute(0, 4, 1, 2, 3).contiguous()
+
+
+def dense_rpn_forward(X, coords, spatial_size, batch_size, stack, head, relu=None, storage=None, tile_weights=None,
+                      sparse_first=True, conv=None):
+    """rpn.DenseRpn's dilation stack and 1x1 head on the CPU with the rounding points of its "tiles" engine
+    (rpn.DenseRpn._forward_tiles).  X [N, C] the level's rows, coords [N, 4] (x, y, z, sample), stack [(weight
+    [Cout, Cin, 3, 3, 3], bias [Cout] | None)] and head (weight [A*7, C, 1, 1, 1], bias) in nn.Conv3d layout.
+    -> the head's output [B, A*7, X, Y, Z] (what `head(stack(sparse_to_dense(X)))` returns).
+
+    relu: torch.relu (default) or a FrozenReLU, applied to the channels-last rows -- one call per stack layer, in
+    layer order.  storage q / tile_weights wq: the bf16 storage mode's roundings (bf16_storage), identity by default.
+    The rounding points, read off the HIP path:
+      sparse first layer (sparse_first and Cin, Cout multiples of 8: one row GEMM + scn_dilate_gather_fwd)
+          P  = q(X @ Wall),  Wall[ci][o][co] = W[co, ci, a, b, c], o = (a*3+b)*3+c   (gemm_table: fp32 weights, one
+               rounding of each output to the slab's dtype)
+          h0 = q(bias + sum_o P[map[cell + d_o]][o]),  d_o = (a-1, b-1, c-1), summed in fp32, bias first, offsets
+               ascending (k_dilate_fwd4 / k_dilate_fwd); a neighbour outside the volume or not active adds nothing
+      dense first layer (the other form)       h0 = q(conv3d(volume, wq(W), b, padding 1))
+      every later 3^3 layer                    h  = q(conv3d(relu(h), wq(W), b, padding 1))   (ReLU fused in the gather)
+      head                                     x = relu(h) widened to fp32 -> fp32 1x1 conv with fp32 weights
+      mixed storage: a layer with Cin or Cout not a multiple of 8 widens its bf16 input to fp32 (modules._conv_input)
+          and runs the fp32 kernels: no rounding from that layer on.
+    Backward is straight-through fp32 (bf16_storage).
+    conv(li, x, W, b): the 3^3 same-convolution of layer li where it runs on the volume (default conv3d, zero padding;
+    tests substitute deliberately wrong ones to show that their bounds are sharp)."""
+    relu = torch.relu if relu is None else relu
+    if conv is None:
+        conv = lambda li, x, W, b: torch.nn.functional.conv3d(x, W, b, padding=1)
+    q = storage if storage is not None else (lambda t: t)
+    wq = tile_weights if tile_weights is not None else (lambda t: t)
+    ident = lambda t: t
+    B = int(batch_size)
+    sx, sy, sz = (int(v) for v in spatial_size)
+    h = None
+    for li, (W, b) in enumerate(stack):
+        cout, cin = W.shape[0], W.shape[1]
+        if cin % 8 or cout % 8:
+            q, wq = ident, ident                      # widened to fp32 here: the fp32 kernels from this layer on
+        if li == 0 and sparse_first and cin % 8 == 0 and cout % 8 == 0:
+            Wall = W.permute(1, 2, 3, 4, 0).reshape(cin, 27 * cout)
+            P = q(X @ Wall).view(-1, 27, cout)
+            Pz = torch.cat([P, P.new_zeros(1, 27, cout)], 0)                 # row N: "no active neighbour"
+            c = torch.from_numpy(np.asarray(coords, dtype=np.int64))
+            cmap = torch.full((B, sx + 2, sy + 2, sz + 2), len(P), dtype=torch.int64)      # zero padding at the faces
+            cmap[c[:, 3], c[:, 0] + 1, c[:, 1] + 1, c[:, 2] + 1] = torch.arange(len(P))
+            acc = (b if b is not None else P.new_zeros(cout)).view(1, 1, 1, 1, cout).expand(B, sx, sy, sz, cout)
+            for o in range(27):
+                da, db_, dc = o // 9, (o // 3) % 3, o % 3
+                rows = cmap[:, da:da + sx, db_:db_ + sy, dc:dc + sz]
+                acc = acc + Pz[rows, o]
+            h = q(acc.permute(0, 4, 1, 2, 3).contiguous())
+            continue
+        if li == 0:
+            h = sparse_to_dense(X, coords, (sx, sy, sz), B)
+        else:
+            h = _cl_apply(relu, h)
+        h = q(conv(li, h, wq(W), b))
+    Wh, bh = head
+    return torch.nn.functional.conv3d(_cl_apply(relu, h), Wh, bh)
 
 
 

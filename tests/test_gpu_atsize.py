@@ -457,7 +457,7 @@ def test_cfg3_end_to_end_backbone_crop_mask_vs_oracle_at_150k(gpu, dtype):
         _check_grad_frozen(name, "grad " + k, got[k], grads[k].view_as(got[k]), FROZEN_L2_F32)
 
 
-def _rpn_chain_vs_oracle(gpu, workload, name):
+def _rpn_chain_vs_oracle(gpu, workload, name, dtype="f32"):
     """The detection + mask step with the RPN boundary inside (`trainstep.SceneStep(workload)`, the step bench.py times) against
     the oracle.  The boxes do not exist before the forward: backbone -> SparseToDense of the anchor level(s) -> dense dilation
     stack(s) + 1x1 head(s) (on this package's tile kernels: rpn.DenseRpn engine "tiles") -> anchors that leave the scene dropped
@@ -468,12 +468,18 @@ def _rpn_chain_vs_oracle(gpu, workload, name):
     the device's sign masks like every other ReLU of the chain), rpn outputs within 1e-4 of their scale; the selection -- made
     on the DEVICE's scores: two evaluations of a large score field differ in their last bits and in top-k ties -- equals the
     oracle's greedy NMS on the device's sorted boxes bit for bit; crop, logits and ALL gradients (backbone + dense RPN + mask
-    tensors + the input features) with the ReLU masks of the HIP forward frozen into the oracle."""
+    tensors + the input features) with the ReLU masks of the HIP forward frozen into the oracle.
+    dtype "bf16": the bf16 storage step against the oracle with the same roundings -- backbone and mask branch as in the cfg-3
+    bf16 test, the dense stacks through O.dense_rpn_forward with the rounding points of the tiles engine (the level slab is
+    bf16, the first layer's P and every stored layer output rounded, tile-kernel weights rounded, the head fp32): backbone
+    features, rpn_bbox and rpn_score within 2^-6 of the scale / 1e-2 relative L2, mask logits 2^-4 / 4e-2, every gradient --
+    the dense RPN's included -- within FROZEN_L2_BF16."""
     import copy
     from sparse_rcnn_amd import rpn as R
     from sparse_rcnn_amd import trainstep as TS
     from sparse_rcnn_amd.trainstep import SceneStep
-    job = SceneStep(workload, gpu, dtype="f32", prefetch=False, seed=1, grad_seed=100, lr=0.0)
+    bf16 = dtype == "bf16"
+    job = SceneStep(workload, gpu, dtype=dtype, prefetch=False, seed=1, grad_seed=100, lr=0.0)
     m = job.model
     with torch.no_grad():
         g = torch.Generator().manual_seed(21)
@@ -530,27 +536,25 @@ def _rpn_chain_vs_oracle(gpu, workload, name):
     fo = job.feats_cpu.clone().requires_grad_()
     fr = O.FrozenReLU(masks)
     inter = []
-    out = O.unet_forward(scene, fo, po, list(ch), relu=fr, interims=inter)
+    q = O.bf16_storage if bf16 else None
+    out = O.unet_forward(scene, fo, po, list(ch), relu=fr, interims=inter, storage=q, tile_weights=q)
     gen = torch.Generator().manual_seed(100)
     gy = torch.randn(out.shape, generator=gen)
     raws, dense_o, mk_at = [], {}, 0
     for li, (r, lvl) in enumerate(zip(rpns, m.rpn_levels)):
         size_l = [v // r.stride for v in size]
-        dense = O.sparse_to_dense(inter[lvl], scene.level_coords[lvl], size_l, B)
+        dense = O.sparse_to_dense(inter[lvl].detach(), scene.level_coords[lvl], size_l, B)
         got_dense = r.to_dense(m.backbone.unet.interims[lvl]).detach().cpu()
-        assert got_dense.shape == dense.shape and torch.equal(got_dense != 0, dense.detach() != 0)       # same cells
-        _record(name, f"SparseToDense of the stride-{r.stride} level", _err(got_dense, dense.detach()), FEAT_TOL)
+        assert got_dense.shape == dense.shape and torch.equal(got_dense != 0, dense != 0)       # same cells
+        _record(name, f"SparseToDense of the stride-{r.stride} level", _err(got_dense, dense), FEAT_TOL)
         stack, head = copy.deepcopy(r.stack).cpu(), copy.deepcopy(r.head).cpu()
-        h = dense
-        for layer in stack:
-            if not isinstance(layer, torch.nn.Conv3d):
-                continue
-            h = layer(h)                                                  # conv3d -> ReLU with the device's sign decisions
-            mk = rpn_masks[mk_at].view(B, *size_l, -1).permute(0, 4, 1, 2, 3)      # the slab is the volume channels-last
-            mk_at += 1
-            assert mk.shape == h.shape
-            h = h * mk.to(h.dtype)
-        raw = head(h)
+        convs = [(l.weight, l.bias) for l in stack if isinstance(l, torch.nn.Conv3d)]
+        # conv3d -> ReLU with the device's sign decisions (the masks are the channels-last slabs of the volume)
+        fr_l = O.FrozenReLU(rpn_masks[mk_at:mk_at + len(convs)])
+        raw = O.dense_rpn_forward(inter[lvl], scene.level_coords[lvl], size_l, B, convs, (head.weight, head.bias), relu=fr_l,
+                                  storage=q, tile_weights=q, sparse_first=R.DenseRpn.SPARSE_FIRST)
+        assert fr_l.k == len(convs)
+        mk_at += len(convs)
         raws.append(raw.view(B, r.n_anchors, 7, -1).permute(0, 3, 1, 2).reshape(B, -1, 7))
         pre = "rpn." if len(rpns) == 1 else f"rpn.levels.{li}."
         dense_o.update(list(stack.named_parameters(prefix=pre + "stack")) + list(head.named_parameters(prefix=pre + "head")))
@@ -558,21 +562,33 @@ def _rpn_chain_vs_oracle(gpu, workload, name):
     raw = torch.cat(raws, 1)[:, inside]
     ob, os_ = raw[..., :6].reshape(B, -1, 2, 3), raw[..., 6]
     e_b, e_s = _err(rpn_bbox, ob), _err(rpn_score, os_)
-    _record(name, "rpn_bbox (dense stack: this library's tile kernels vs torch CPU conv3d)", e_b, 1e-4)
-    _record(name, "rpn_score", e_s, 1e-4)
-    assert e_b["rel_to_scale"] <= 1e-4 and e_s["rel_to_scale"] <= 1e-4, (e_b, e_s)
+    if bf16:
+        _record(name, "rpn_bbox vs oracle with the same roundings", e_b, "rel_to_scale <= 2^-6, rel_l2 <= 1e-2")
+        _record(name, "rpn_score vs oracle with the same roundings", e_s, "rel_to_scale <= 2^-6, rel_l2 <= 1e-2")
+        assert all(e["rel_to_scale"] <= 2.0 ** -6 and e["rel_l2"] <= 1e-2 for e in (e_b, e_s)), (e_b, e_s)
+    else:
+        _record(name, "rpn_bbox (dense stack: this library's tile kernels vs torch CPU conv3d)", e_b, 1e-4)
+        _record(name, "rpn_score", e_s, 1e-4)
+        assert e_b["rel_to_scale"] <= 1e-4 and e_s["rel_to_scale"] <= 1e-4, (e_b, e_s)
     gr = [g.cpu() for g in job._grs[0]]                 # the gradients SceneStep drew for rpn_bbox / rpn_score
     torch.randn(ob.shape, generator=gen), torch.randn(os_.shape, generator=gen)        # (advance the generator as it did)
     boxes_np, cnt, assoc = O.transform_boxes([b.numpy() for b in boxes])
-    logits, src, box_of, rscene = _oracle_mask_branch(job.coords_cpu.numpy(), fo, out, mo, boxes_np, assoc, scene, relu=fr)
+    logits, src, box_of, rscene = _oracle_mask_branch(job.coords_cpu.numpy(), fo, out, mo, boxes_np, assoc, scene, bf16=bf16,
+                                                      relu=fr)
     assert fr.k == len(masks) and len(src) == job.n_roi_rows and logits.shape == job.logits.shape
     gm = job.upstream_grads(0)[1].cpu()
     assert gm.shape == logits.shape
     torch.autograd.backward([out, ob, os_, logits], [gy, gr[0], gr[1], gm])
     e_out, e_log = _err(job.out.features, out), _err(job.logits, logits)
-    _record(name, "backbone features", e_out, FEAT_TOL)
-    _record(name, "mask logits", e_log, FEAT_TOL)
-    assert e_out["rel_to_scale"] <= FEAT_TOL and e_log["rel_to_scale"] <= FEAT_TOL, (e_out, e_log)
+    if bf16:
+        _record(name, "backbone features vs oracle with the same roundings", e_out, "rel_to_scale <= 2^-6, rel_l2 <= 1e-2")
+        _record(name, "mask logits vs oracle with the same roundings", e_log, "rel_to_scale <= 2^-4, rel_l2 <= 4e-2")
+        assert e_out["rel_to_scale"] <= 2.0 ** -6 and e_out["rel_l2"] <= 1e-2, e_out
+        assert e_log["rel_to_scale"] <= 2.0 ** -4 and e_log["rel_l2"] <= 4e-2, e_log
+    else:
+        _record(name, "backbone features", e_out, FEAT_TOL)
+        _record(name, "mask logits", e_log, FEAT_TOL)
+        assert e_out["rel_to_scale"] <= FEAT_TOL and e_log["rel_to_scale"] <= FEAT_TOL, (e_out, e_log)
     grads = {k: v.grad for k, v in po.items()}
     grads.update({"m:" + k: v.grad for k, v in mo.items()})
     grads["input features"] = fo.grad
@@ -586,23 +602,26 @@ def _rpn_chain_vs_oracle(gpu, workload, name):
     assert set(got) == set(grads) and len(grads) == len(pb) + 80 + len(dense_o) + 1
     for k in grads:
         # the dense layers' own gradients: same kernels, same bound
-        _check_grad_frozen(name, "grad " + k, got[k], grads[k].view_as(got[k]), RPN_L2_F32 if k.startswith("d:") else FROZEN_L2_F32)
+        bound = FROZEN_L2_BF16 if bf16 else (RPN_L2_F32 if k.startswith("d:") else FROZEN_L2_F32)
+        _check_grad_frozen(name, "grad " + k, got[k], grads[k].view_as(got[k]), bound)
 
 
-def test_cfg3_rpn_chain_vs_oracle_at_150k(gpu):
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_cfg3_rpn_chain_vs_oracle_at_150k(gpu, dtype):
     """BASELINE configs[2] with the RPN boundary inside the step (`bench.py --workload cfg3-rpn`) on the
     150k-voxel scene: a stand-in RPN (ONE anchor level, 2 x 32 stack, 64 kept) -- see `_rpn_chain_vs_oracle`; 76 backbone + 6
     dense RPN + 80 mask gradient tensors + the input features."""
-    _rpn_chain_vs_oracle(gpu, "cfg3-rpn", "cfg3_rpn_chain_150k")
+    _rpn_chain_vs_oracle(gpu, "cfg3-rpn", "cfg3_rpn_chain_150k" + ("_bf16_storage" if dtype == "bf16" else ""), dtype)
 
 
-def test_ref_crop_rpn_chain_vs_oracle_at_size(gpu):
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_ref_crop_rpn_chain_vs_oracle_at_size(gpu, dtype):
     """the REFERENCE's detection shape as far as this path reaches (`bench.py --workload ref-crop-rpn`):
     plan 32-48-64-80-96-112 on its training batch (12 crops of 128 x 128 x 64, run.py:364,485-488), SparseToDense of BOTH
     anchor levels (64 ch at stride 4, 80 ch at stride 8), a 5 x 128 and a 5 x 256 dilation stack (run.py:525-536,609), 3 + 11
     anchors per cell, top-1024 / NMS 0.5 / 256 kept (run.py:847-853), the 24 best per sample -> crop -> mask branch: see
     `_rpn_chain_vs_oracle`; 120 backbone + 24 dense RPN + 80 mask gradient tensors + the input features."""
-    _rpn_chain_vs_oracle(gpu, "ref-crop-rpn", "ref_crop_rpn_chain")
+    _rpn_chain_vs_oracle(gpu, "ref-crop-rpn", "ref_crop_rpn_chain" + ("_bf16_storage" if dtype == "bf16" else ""), dtype)
 
 
 @pytest.mark.parametrize("variant", ["unet_only", "both_skip", "raw_skip"])

@@ -586,6 +586,136 @@ def test_cell_map_of_a_level(gpu):
     assert np.array_equal(cmap.cpu().numpy(), em)
 
 
+# ---- scn_dilate_gather_fwd / _bwd through the C ABI, bit for bit against plain torch
+_DG_CANARY = {torch.float32: (torch.int32, 0x7FC0DEAD), torch.bfloat16: (torch.int16, 0x7FAD)}     # (NaN bit patterns)
+_DG_TAIL = 67
+
+
+def _dg_buffer(numel, dt, gpu):
+    """numel elements + a tail, every element preset to a NaN canary (an element the kernel skips fails the comparison)."""
+    it, bits = _DG_CANARY[dt]
+    return torch.full((numel + _DG_TAIL,), bits, dtype=it, device=gpu).view(dt)
+
+
+def _dg_tail_intact(buf, numel):
+    it, bits = _DG_CANARY[buf.dtype]
+    return torch.equal(buf[numel:].view(it), torch.full((_DG_TAIL,), bits, dtype=it, device=buf.device))
+
+
+def _dg_level(rng, B, size, occupancy, empty):
+    """Active cells of a [B X Y Z] volume (none in sample `empty`), rows in random order -> (cell_of_row int64, map int32)."""
+    X, Y, Z = size
+    per = X * Y * Z
+    cand = np.concatenate([np.arange(b * per, (b + 1) * per) for b in range(B) if b != empty]).astype(np.int64)
+    n = {"one": 1, "2%": max(1, round(0.02 * len(cand))), "all": len(cand)}[occupancy]
+    cells = rng.choice(cand, size=n, replace=False)
+    cmap = np.full(B * per, -1, np.int32)
+    cmap[cells] = np.arange(n, dtype=np.int32)
+    return torch.from_numpy(cells), torch.from_numpy(cmap)
+
+
+def _dg_shift(B, size, dev):
+    """[27][B X Y Z] cell index of cell + d_o (o = (a*3+b)*3+c, d_o = (a-1, b-1, c-1)), -1 outside the volume."""
+    X, Y, Z = size
+    g = torch.stack(torch.meshgrid(*[torch.arange(v, device=dev) for v in (B, X, Y, Z)], indexing="ij"), 0).reshape(4, -1)
+    out = []
+    for o in range(27):
+        nx, ny, nz = g[1] + o // 9 - 1, g[2] + (o // 3) % 3 - 1, g[3] + o % 3 - 1
+        ok = (nx >= 0) & (nx < X) & (ny >= 0) & (ny < Y) & (nz >= 0) & (nz < Z)
+        out.append(torch.where(ok, ((g[0] * X + nx) * Y + ny) * Z + nz, -1))
+    return out
+
+
+def _dg_fwd_ref(P, cmap, B, size, c, bias):
+    """fp32 sum in the kernel's order (bias first, offsets ascending), one rounding to the slab's dtype."""
+    cells = B * size[0] * size[1] * size[2]
+    Pf = P.float().view(-1, 27, c)
+    acc = bias.view(1, c).expand(cells, c).clone() if bias is not None else torch.zeros(cells, c, device=P.device)
+    m = cmap.long()
+    for o, nb in enumerate(_dg_shift(B, size, P.device)):
+        r = torch.where(nb >= 0, m[nb.clamp(min=0)], -1)
+        hit = r >= 0
+        acc[hit] = acc[hit] + Pf[r[hit], o]
+    return acc.to(P.dtype)
+
+
+def _dg_bwd_ref(dOut, cell_of_row, size, c):
+    """dP[r][o] = dOut[cell(r) - d_o], 0 where that cell is outside the volume."""
+    X, Y, Z = size
+    cr = cell_of_row
+    z, y, x, b = cr % Z, (cr // Z) % Y, (cr // (Y * Z)) % X, cr // (X * Y * Z)
+    dP = torch.zeros(len(cr), 27, c, dtype=dOut.dtype, device=dOut.device)
+    for o in range(27):
+        cx, cy, cz = x - (o // 9 - 1), y - ((o // 3) % 3 - 1), z - (o % 3 - 1)
+        ok = (cx >= 0) & (cx < X) & (cy >= 0) & (cy < Y) & (cz >= 0) & (cz < Z)
+        dP[ok, o] = dOut[((b[ok] * X + cx[ok]) * Y + cy[ok]) * Z + cz[ok]]
+    return dP.view(len(cr), 27 * c)
+
+
+def _dg_run(gpu, dt, c, B, size, P, cmap, cell_of_row, bias, dOut):
+    from sparse_rcnn_amd import _lib as L
+    bf = int(dt == torch.bfloat16)
+    hs = L.host_i64(3)
+    hs[0], hs[1], hs[2] = size
+    n = len(cell_of_row)
+    cells = B * size[0] * size[1] * size[2]
+    out = _dg_buffer(cells * c, dt, gpu)
+    L.check(L.lib().scn_dilate_gather_fwd(L.ptr(P), L.ptr(cmap), B, hs, c, bf, L.ptr(bias), L.ptr(out), L.stream()))
+    dP = _dg_buffer(n * 27 * c, dt, gpu)
+    L.check(L.lib().scn_dilate_gather_bwd(L.ptr(dOut), L.ptr(cell_of_row), n, hs, c, bf, L.ptr(dP), L.stream()))
+    torch.cuda.synchronize()
+    assert _dg_tail_intact(out, cells * c) and _dg_tail_intact(dP, n * 27 * c)
+    return out[:cells * c].view(cells, c), dP[:n * 27 * c].view(n, 27 * c)
+
+
+# (volume, batch, the sample left empty): the cfg3-rpn stride-8 level is 512 x 512 x 256 / 8
+_DG_VOLUMES = [((1, 1, 1), 1, None), ((2, 1, 3), 2, None), ((7, 5, 9), 3, 1), ((64, 64, 32), 1, None)]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("c", [4, 8, 32, 256, 1, 3, 6, 33])
+def test_dilate_gather_fwd_bwd_bit_exact(gpu, dtype, c):
+    """`scn_dilate_gather_fwd` / `_bwd` (the first dense layer of rpn.DenseRpn) called directly, against plain torch with
+    torch.equal: the forward sums bias + up to 27 rows of P in fp32 in the kernel's order and rounds once (bf16: the RNE of
+    `.to(torch.bfloat16)`), the backward is a gather of the output gradient with zeros beyond the faces.  c % 4 == 0 takes
+    the four-channel kernel, the rest the scalar one; bias present and NULL; one active row, ~2 % and every cell; a batch
+    with an empty sample; no active rows (the bias broadcast), n = 0 and batch = 0.  Every buffer the kernels write carries
+    a canary tail that must come back untouched."""
+    dt = torch.float32 if dtype == "f32" else torch.bfloat16
+    rng = np.random.default_rng(1000 + c)
+    gen = torch.Generator().manual_seed(c)
+    for size, B, empty in _DG_VOLUMES:
+        cells = B * size[0] * size[1] * size[2]
+        for occupancy in ("one", "2%", "all"):
+            if occupancy == "all" and cells > 4096:
+                continue
+            cell_of_row, cmap = _dg_level(rng, B, size, occupancy, empty)
+            n = len(cell_of_row)
+            P = torch.randn(n, 27 * c, generator=gen).to(dt).to(gpu)
+            dOut = torch.randn(cells, c, generator=gen).to(dt).to(gpu)
+            for with_bias in (True, False):
+                bias = torch.randn(c, generator=gen).to(gpu) if with_bias else None
+                cr, cm = cell_of_row.to(gpu), cmap.to(gpu)
+                out, dP = _dg_run(gpu, dt, c, B, size, P, cm, cr, bias, dOut)
+                what = (size, B, occupancy, with_bias)
+                assert torch.equal(out, _dg_fwd_ref(P, cm, B, size, c, bias)), what
+                assert torch.equal(dP, _dg_bwd_ref(dOut, cr, size, c)), what
+    # no active row: the map is all -1, the forward is the bias broadcast (zeros without bias), the backward writes nothing
+    size, B = (7, 5, 9), 2
+    cells = B * 7 * 5 * 9
+    cm = torch.full((cells,), -1, dtype=torch.int32, device=gpu)
+    cr = torch.empty(0, dtype=torch.int64, device=gpu)
+    P = torch.empty(1, 27 * c, dtype=dt, device=gpu)                    # (never read: a valid pointer for the ABI's check)
+    dOut = torch.randn(cells, c, generator=gen).to(dt).to(gpu)
+    for bias in (torch.randn(c, generator=gen).to(gpu), None):
+        out, dP = _dg_run(gpu, dt, c, B, size, P, cm, cr, bias, dOut)
+        exp = bias.to(dt).view(1, c).expand(cells, c) if bias is not None else torch.zeros(cells, c, dtype=dt, device=gpu)
+        assert torch.equal(out, exp) and dP.numel() == 0
+    # batch 0: nothing to write
+    out, dP = _dg_run(gpu, dt, c, 0, size, P, cm, cr, None, dOut)
+    assert out.numel() == 0 and dP.numel() == 0
+
+
 def test_deconvolution_needs_cached_level(gpu):
     scn, coords, feats, fg, x, scene, size = _input(gpu, seed=4, cin=4)
     with pytest.raises(scn.ScnError):
@@ -1867,6 +1997,122 @@ def test_dense_rpn_stack_on_the_tile_kernels_equals_the_miopen_engine(gpu):
         outs.append((bb.float(), sc.float()))
     for u, v in zip(*outs):
         assert float((u - v).abs().max()) <= 3e-2 * max(float(v.abs().max()), 1e-6)
+
+
+# ---- rpn.DenseRpn ("tiles" engine) in fp32 and bf16 against the oracle with the HIP path's rounding points
+# (level channels, width, num_dilations, level grid, batch, the sample left empty)
+_RPN_CASES = [(32, 32, 2, (9, 7, 5), 2, None),        # the stand-in shape
+              (64, 128, 3, (12, 10, 6), 2, None),     # the reference's level 1 (the later layers split K)
+              (80, 256, 2, (8, 8, 4), 2, None),       # the reference's level 2
+              (24, 16, 2, (6, 5, 2), 3, 1),           # a thin volume, one empty sample
+              (20, 16, 2, (7, 6, 3), 2, None)]        # c % 8 != 0: the stack widened to fp32 (mixed storage)
+RPN_BF16_FWD = (2.0 ** -6, 4e-3)      # bf16 rpn_bbox / rpn_score: max |d| / scale, relative L2
+RPN_BF16_GRAD = (2.0 ** -4, 2e-2)     # bf16 gradients: max |d| / scale, relative L2 (test_gpu_atsize.FROZEN_L2_BF16)
+
+
+def _rpn_level(gpu, c, grid, batch, empty, seed):
+    """An InputLayer level: a quarter of the cells of every sample but `empty` active, rows in random order."""
+    scn = _scn()
+    rng = np.random.default_rng(seed)
+    per = grid[0] * grid[1] * grid[2]
+    cs = []
+    for b in range(batch):
+        if b != empty:
+            lin = rng.choice(per, size=per // 4, replace=False)
+            cs.append(np.concatenate([np.stack(np.unravel_index(lin, grid), 1), np.full((len(lin), 1), b)], 1))
+    coords = torch.from_numpy(np.concatenate(cs).astype(np.int64))
+    feats = torch.randn(len(coords), c, generator=torch.Generator().manual_seed(seed + 1))
+    x = scn.InputLayer(3, torch.tensor(grid), mode=4)((coords, feats.to(gpu), batch))
+    return x, O.OracleScene(coords.numpy()).coords0
+
+
+def _wrong_conv(mistake):
+    """A same-convolution that is wrong in layer 1 only: replicate instead of zero padding (only the face cells change),
+    or the weights of offsets 0 and 26 exchanged."""
+    def conv(li, x, W, b):
+        if li == 1 and mistake == "replicate":
+            return torch.nn.functional.conv3d(torch.nn.functional.pad(x, (1,) * 6, mode="replicate"), W, b)
+        if li == 1 and mistake == "swap":
+            W = W.flatten(2)[:, :, [26] + list(range(1, 26)) + [0]].view_as(W)
+        return torch.nn.functional.conv3d(x, W, b, padding=1)
+    return conv
+
+
+@pytest.mark.parametrize("case", _RPN_CASES, ids=lambda c: f"c{c[0]}_w{c[1]}x{c[2]}_{'x'.join(map(str, c[3]))}_b{c[4]}")
+@pytest.mark.parametrize("sparse_first", [True, False], ids=["sparse_first", "dense_first"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_dense_rpn_tiles_engine_vs_oracle_forward_and_every_gradient(gpu, dtype, sparse_first, case):
+    """rpn.DenseRpn on the "tiles" engine -- first layer as row GEMM + scn_dilate_gather (SPARSE_FIRST) or on the tile
+    kernels, the later 3^3 layers on k_conv_tb / k_wgrad_tb over a fully active grid, the head on the row GEMM -- against
+    O.dense_rpn_forward with the path's rounding points (bf16: stored slabs and tile-kernel weights rounded) and the ReLU
+    masks the HIP forward recorded (O.FrozenReLU): rpn_bbox, rpn_score, the level-feature gradient and every stack and head
+    parameter gradient.  fp32 within 1e-4 of the scale.  bf16: outputs within 2^-6 of the scale and 4e-3 relative L2,
+    gradients within 2e-2 relative L2 (FROZEN_L2_BF16: the HIP path stores its gradient slabs in bf16, the oracle
+    differentiates straight through in fp32) and 2^-4 of the scale per element (an error confined to a face or a corner
+    hides in the relative L2 over the volume).  The bf16 bounds are shown sharp: the same HIP result against the oracle
+    with one deliberate mistake in layer 1 (replicate padding; offsets 0 and 26 exchanged) misses both forward bounds by
+    more than 4x.  Achieved (profiles/bf16_rpn_parity_errors.jsonl): forward <= 1.6e-3 of the scale, gradients <= 4e-3
+    relative L2; the altered oracles sit 17x and more beyond the forward bounds."""
+    from sparse_rcnn_amd import functional as F
+    from sparse_rcnn_amd.rpn import DenseRpn
+    from test_gpu_atsize import _err, _record           # (the parity log of the at-size tests)
+    c, width, n_dil, grid, batch, empty = case
+    bf16 = dtype == "bf16"
+    x, coords0 = _rpn_level(gpu, c, grid, batch, empty, seed=c + width)
+    torch.manual_seed(c * width)
+    net = DenseRpn(c, stride=8, width=width, num_dilations=n_dil, keep_inside=False).to(gpu)
+    net.engine, net.SPARSE_FIRST = "tiles", sparse_first
+    with torch.no_grad():
+        for p in net.parameters():
+            p.add_(torch.randn_like(p) * 0.05)
+    X = x.features.detach().to(torch.bfloat16 if bf16 else torch.float32).clone().requires_grad_()
+    t = _scn().SparseConvNetTensor(features=X, metadata=x.metadata, spatial_size=x.spatial_size)
+    F.RELU_RECORD = []
+    try:
+        bb, sc, _ = net(t)
+    finally:
+        masks, F.RELU_RECORD = F.RELU_RECORD, None
+    assert len(masks) == n_dil and bb.dtype == sc.dtype == torch.float32
+    g = torch.Generator().manual_seed(3)
+    gb, gs = torch.randn(bb.shape, generator=g), torch.randn(sc.shape, generator=g)
+    torch.autograd.backward([bb, sc], [gb.to(gpu), gs.to(gpu)])
+    torch.cuda.synchronize()
+    names = [n for n, _ in net.named_parameters()]
+    got = [bb, sc, X.grad] + [p.grad for p in net.parameters()]
+
+    def oracle(conv=None):
+        params = [p.detach().cpu().clone().requires_grad_() for p in net.parameters()]
+        Xo = X.detach().float().cpu().requires_grad_()
+        convs = [(params[2 * i], params[2 * i + 1]) for i in range(n_dil)]
+        fr = O.FrozenReLU(masks)
+        q = O.bf16_storage if bf16 else None
+        raw = O.dense_rpn_forward(Xo, coords0, grid, batch, convs, tuple(params[-2:]), relu=fr, storage=q, tile_weights=q,
+                                  sparse_first=sparse_first, conv=conv)
+        assert fr.k == n_dil
+        raw = raw.view(batch, net.n_anchors, 7, -1).permute(0, 3, 1, 2).reshape(batch, -1, 7)
+        ob, os_ = raw[..., :6].reshape(batch, -1, 2, 3), raw[..., 6]
+        torch.autograd.backward([ob, os_], [gb, gs])
+        return [ob, os_, Xo.grad] + [p.grad for p in params]
+
+    ref = oracle()
+    what = ["rpn_bbox", "rpn_score", "level features"] + names
+    if not bf16:
+        for n, a, r in zip(what, got, ref):
+            _close(a, r, 1e-4, n)
+        return
+    name = f"dense_rpn_bf16_{'sparse' if sparse_first else 'dense'}_first_c{c}_w{width}x{n_dil}"
+    for i, (n, a, r) in enumerate(zip(what, got, ref)):
+        e = _err(a, r)
+        tol = RPN_BF16_FWD if i < 2 else RPN_BF16_GRAD
+        _record(name, n if i < 2 else "grad " + n, e, f"rel_to_scale <= {tol[0]:.4g}, rel_l2 <= {tol[1]}")
+        assert bool(torch.isfinite(a).all()) and e["rel_to_scale"] <= tol[0] and e["rel_l2"] <= tol[1], (n, e)
+    # sharpness: the same HIP outputs against an oracle with one mistake in layer 1 miss both forward bounds by > 4x
+    for mistake in ("replicate", "swap"):
+        bad = oracle(_wrong_conv(mistake))
+        for n, a, r in zip(what[:2], got[:2], bad[:2]):
+            e = _err(a, r)
+            _record(name, f"{n} vs the oracle with '{mistake}' in layer 1", e, "rel_to_scale and rel_l2 > 4 x bound")
+            assert e["rel_to_scale"] > 4 * RPN_BF16_FWD[0] and e["rel_l2"] > 4 * RPN_BF16_FWD[1], (mistake, n, e)
 
 
 def test_roi_selector_takes_the_references_anchor_description_callable(gpu):

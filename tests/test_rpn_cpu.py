@@ -90,3 +90,95 @@ def test_get_roi_selector_follows_training_mode_like_the_references_conditional_
     assert pair._member().proposal_selector.num_keep_post_nms == 32 and pair._member().proposal_selector.thresh_nms == 0.3
     pair.train()
     assert pair._member() is pair.train_module
+
+
+# ---- the dense stack's oracle (oracle.scn_oracle.dense_rpn_forward): the GPU tests hold DenseRpn's "tiles" engine to it
+def _level(seed, size, batch, n, c, empty=()):
+    """n random active cells per sample (none in the samples of `empty`) of a `size` grid, features [rows, c]."""
+    rng = np.random.default_rng(seed)
+    cs = []
+    for b in range(batch):
+        if b in empty:
+            continue
+        lin = rng.choice(int(np.prod(size)), size=n, replace=False)
+        cs.append(np.concatenate([np.stack(np.unravel_index(lin, size), 1), np.full((n, 1), b)], 1))
+    coords = np.concatenate(cs).astype(np.int64)
+    X = torch.randn(len(coords), c, generator=torch.Generator().manual_seed(seed + 1))
+    return coords, X
+
+
+def _cpu_rpn(c, width, n_dil, seed=3):
+    torch.manual_seed(seed)
+    net = R.DenseRpn(c, stride=8, width=width, num_dilations=n_dil, keep_inside=False)
+    with torch.no_grad():
+        for p in net.parameters():
+            p.add_(torch.randn_like(p) * 0.1)
+    convs = [l for l in net.stack if isinstance(l, torch.nn.Conv3d)]
+    return net, [(l.weight, l.bias) for l in convs], (net.head.weight, net.head.bias)
+
+
+def _scale_err(a, b):
+    a, b = a.detach(), b.detach()
+    return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-30)
+
+
+@pytest.mark.parametrize("c,width,size,batch", [(16, 16, (7, 6, 5), 2), (24, 8, (5, 4, 3), 3), (20, 16, (6, 5, 4), 2)])
+def test_dense_rpn_oracle_both_first_layer_forms_equal_torch_conv3d(c, width, size, batch):
+    """With identity roundings the sparse first layer (row GEMM + dilation gather, zero padding at the faces) and the dense
+    one both equal the module's own `head(stack(sparse_to_dense(X)))` within fp32 rounding, forward and every gradient."""
+    from oracle import scn_oracle as O
+    net, stack, head = _cpu_rpn(c, width, 2)
+    coords, X = _level(1, size, batch, 20, c)
+    X.requires_grad_()
+    ref = net.head(net.stack(O.sparse_to_dense(X, coords, size, batch)))
+    g = torch.randn(ref.shape, generator=torch.Generator().manual_seed(2))
+    params = list(net.parameters())
+    ref_g = torch.autograd.grad(ref, [X] + params, g)
+    for sparse_first in (True, False):
+        got = O.dense_rpn_forward(X, coords, size, batch, stack, head, sparse_first=sparse_first)
+        assert got.shape == ref.shape and _scale_err(got, ref) <= 1e-6, sparse_first
+        for a, b in zip(torch.autograd.grad(got, [X] + params, g), ref_g):
+            assert _scale_err(a, b) <= 1e-6, sparse_first
+
+
+def test_dense_rpn_oracle_bf16_roundings_of_the_two_forms_agree_within_bf16_noise():
+    """The bf16 storage roundings (P and every stored layer output rounded, tile-kernel weights rounded in the dense form
+    only) move the output by bf16 noise, and the two forms land within that noise of each other; with a level width that is
+    not a multiple of 8 the stack is widened to fp32 before its first layer and no rounding is left."""
+    from oracle import scn_oracle as O
+    r = O.bf16_storage
+    for c, width, sparse_diff in ((16, 16, True), (20, 16, False)):
+        net, stack, head = _cpu_rpn(c, width, 3)
+        coords, X = _level(4, (8, 7, 5), 2, 40, c)
+        X = X.to(torch.bfloat16).float()                          # a bf16-stored level
+        with torch.no_grad():
+            f32 = O.dense_rpn_forward(X, coords, (8, 7, 5), 2, stack, head)
+            outs = [O.dense_rpn_forward(X, coords, (8, 7, 5), 2, stack, head, storage=r, tile_weights=r, sparse_first=sf)
+                    for sf in (True, False)]
+        for o in outs:
+            if sparse_diff:
+                assert 1e-5 < _scale_err(o, f32) <= 2.0 ** -6
+            else:
+                assert torch.equal(o, f32)
+        e = _scale_err(outs[0], outs[1])
+        assert (0 < e <= 2.0 ** -6) if sparse_diff else e == 0
+        assert float((outs[0] - outs[1]).norm() / outs[1].norm()) <= 1e-2
+
+
+@pytest.mark.parametrize("sparse_first", [True, False])
+def test_dense_rpn_oracle_of_an_empty_sample_is_the_head_of_the_bias_only_stack(sparse_first):
+    """A sample without active rows sees the bias of the first layer on every cell; the rest of the stack and the head then
+    act on that constant volume as on any other -- exactly, since adding zeros changes no bit (the reference runs the whole
+    batch, every sample at the bias, so that torch's CPU convolution blocks the batch the same way)."""
+    from oracle import scn_oracle as O
+    net, stack, head = _cpu_rpn(16, 8, 3)
+    size = (6, 5, 4)
+    coords, X = _level(7, size, 3, 15, 16, empty=(1,))
+    got = O.dense_rpn_forward(X, coords, size, 3, stack, head, sparse_first=sparse_first)
+    with torch.no_grad():
+        h = stack[0][1].view(1, -1, 1, 1, 1).expand(3, -1, *size).contiguous()
+        for W, b in stack[1:]:
+            h = torch.nn.functional.conv3d(torch.relu(h), W, b, padding=1)
+        exp = torch.nn.functional.conv3d(torch.relu(h), *head)
+    assert torch.equal(got[1].detach(), exp[1])
+    assert not torch.equal(got[0], got[1])
