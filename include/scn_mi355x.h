@@ -61,7 +61,9 @@ extern "C" {
  *      = log2 of the row bins in the sort key of a 27-offset table (0: as before); scn_pyramid_build_ex with
  *      SCN_PYRAMID_XCD_ORDER sorts level 0 by (row bin, mask); switches SCN_TS_PROG, SCN_TS_NO_CHAIN, SCN_TB_NO_BINS;
  *      additive within 5: + scn_adam_many / scn_adam_launches / scn_adam_segment_bytes, struct scn_adam_segment (124 entry
- *      points) */
+ *      points);
+ *      additive within 5: + scn_rpn_targets, scn_rpn_sample_workspace_bytes / scn_rpn_sample_batchwise,
+ *      scn_rpn_loss_scratch_bytes / scn_rpn_loss, scn_rpn_loss_scale (130 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -797,6 +799,45 @@ int64_t scn_adam_segment_bytes(void);
 int scn_adam_launches(const scn_adam_segment* segs, int n_segs, int* launches);
 int scn_adam_many(const scn_adam_segment* segs, int n_segs, double grad_scale, double beta1, double beta2, double eps,
                   scn_stream_t stream);
+
+/* ---- RPN loss (ndsis/modules/loss.py RpnLoss with BatchwiseBboxTargetSelector; utils/bbox.py select_bbox, bbox_transform) ----
+ * Three steps, every one graph-capturable (no allocation, copy or synchronisation inside; all counts stay on the device):
+ *
+ * scn_rpn_targets: anchors fp32 [n_anchors][2][3] = (centre, size), shared by every sample; gt_boxes fp32 [total][2][3] =
+ * (start, stop), the boxes of sample b at rows box_offsets[b] .. box_offsets[b+1]-1 (box_offsets: HOST array of batch+1
+ * non-decreasing values, copied into the kernel arguments).  Per sample b and anchor i: max_overlap[b][i] = the largest IoU
+ * with a box of the sample, argmax[b][i] = that box's index within the sample (ties: the lowest), bbox_target[b][i] =
+ * bbox_transform(anchor, matched box).  The IoU follows the reference's operation order with every operation rounded once
+ * (max_overlap is bit-equal to it); log is within ulps.  A sample with no boxes: overlap 0, argmax -1, the target of a zero
+ * box.  Any number of boxes per sample.
+ *
+ * scn_rpn_sample_batchwise: over all n = batch * anchors overlaps, positive = overlap >= positive_overlap, negative =
+ * overlap < negative_overlap; min_count = min(#pos, #neg) members of the larger set (the negatives when the counts are
+ * equal) are drawn uniformly without replacement, the smaller set is kept whole.  label = positive; score_weight = (kept or
+ * drawn) / max(1, 2 min_count); bbox_weight = label / max(#pos, min_inverse_weight).  counts (may be NULL) = {#pos, #neg}.
+ * The draw is a function of (seed, counter) only: key = a keyed bijection of the flat index, the min_count smallest keys
+ * of the larger set are drawn (radix select on the device).  workspace: scn_rpn_sample_workspace_bytes(), 8-byte aligned,
+ * zero before its first use; every call leaves it zero again (one workspace per stream).  n < 2^31.
+ *
+ * scn_rpn_loss: score_loss = sum BCE-with-logits(score, label) * score_weight, bbox_loss = sum bbox_weight[i] * smoothL1_sigma
+ * (bbox[i] - bbox_target[i]) (over the 6 components); dscore / dbbox = their gradients for an upstream gradient of 1.  n =
+ * batch * anchors.  The sums are accumulated in double in a fixed order (per-block partials, one finishing block): bitwise
+ * identical from run to run.  scratch: scn_rpn_loss_scratch_bytes(n), 8-byte aligned.
+ *
+ * scn_rpn_loss_scale: out_dscore = dscore * *grad_score_loss, out_dbbox = dbbox * *grad_bbox_loss (the upstream gradients
+ * are read on the device); a NULL output is not written. */
+int scn_rpn_targets(const float* anchors, int64_t n_anchors, const float* gt_boxes, const int64_t* box_offsets, int batch,
+                    float* max_overlap, int64_t* argmax, float* bbox_target, scn_stream_t stream);
+int64_t scn_rpn_sample_workspace_bytes(void);
+int scn_rpn_sample_batchwise(const float* overlaps, int64_t n, float positive_overlap, float negative_overlap,
+                             float min_inverse_weight, uint64_t seed, uint64_t counter, void* workspace, float* label,
+                             float* score_weight, float* bbox_weight, int64_t* counts, scn_stream_t stream);
+int64_t scn_rpn_loss_scratch_bytes(int64_t n);
+int scn_rpn_loss(const float* score, const float* bbox, const float* label, const float* score_weight, const float* bbox_target,
+                 const float* bbox_weight, int64_t n, float sigma, void* scratch, float* score_loss, float* bbox_loss,
+                 float* dscore, float* dbbox, scn_stream_t stream);
+int scn_rpn_loss_scale(const float* dscore, const float* dbbox, int64_t n, const float* grad_score_loss,
+                       const float* grad_bbox_loss, float* out_dscore, float* out_dbbox, scn_stream_t stream);
 
 #ifdef __cplusplus
 }

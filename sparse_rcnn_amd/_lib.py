@@ -143,6 +143,12 @@ _SIGS = {
     "scn_adam_segment_bytes": (i64, []),
     "scn_adam_launches": (C.c_int, [p, i32, C.POINTER(i32)]),
     "scn_adam_many": (C.c_int, [p, i32, C.c_double, C.c_double, C.c_double, C.c_double, p]),
+    "scn_rpn_targets": (C.c_int, [p, i64, p, C.POINTER(i64), i32, p, p, p, p]),
+    "scn_rpn_sample_workspace_bytes": (i64, []),
+    "scn_rpn_sample_batchwise": (C.c_int, [p, i64, f32, f32, f32, C.c_uint64, C.c_uint64, p, p, p, p, p, p]),
+    "scn_rpn_loss_scratch_bytes": (i64, [i64]),
+    "scn_rpn_loss": (C.c_int, [p, p, p, p, p, p, i64, f32, p, p, p, p, p, p]),
+    "scn_rpn_loss_scale": (C.c_int, [p, p, i64, p, p, p, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)

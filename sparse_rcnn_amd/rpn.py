@@ -142,6 +142,15 @@ class DenseRpn(nn.Module):
             got = self._anchor_cache[key] = (idx, a[idx])
         return got
 
+    def target_calculator(self, shape, device=None):
+        """The reference's `rpn_target_calculator` (anchor.py:148-165 get_bbox_targets) over exactly the anchors `forward` returns
+        for a level of spatial size `shape`: calculator(list of [n_i, 2, 3] boxes) -> (max_overlaps, argmax, bbox_targets)
+        (loss.RpnTargetCalculator, scn_rpn_targets)."""
+        from .loss import RpnTargetCalculator
+        device = device if device is not None else self.head.weight.device
+        anchors = self.inside_for(shape, device)[1] if self.keep_inside else self.anchors_for(shape, device)
+        return RpnTargetCalculator(anchors)
+
     def _finish(self, raw, shape):
         """raw [B, N, 7] in anchor order -> (rpn_bbox, rpn_score, anchors), inside-the-scene anchors only when asked."""
         if self.keep_inside:
@@ -283,16 +292,29 @@ class MultiLevelRpn(nn.Module):
         scene = tuple(int(v) * self.levels[0].stride for v in level_tensors[0].spatial_size)
         return self.combine(outs, scene)
 
+    def _inside(self, level_anchors, scene_shape, device):
+        key = (tuple(scene_shape), tuple(a.shape[0] for a in level_anchors), str(device))
+        got = self._cache.get(key)
+        if got is None:
+            anchors = torch.cat(level_anchors, 0)
+            idx = inside_indicator(anchors, torch.tensor(scene_shape, dtype=torch.float32), self.allowed_border).nonzero().squeeze(1)
+            got = self._cache[key] = (idx, anchors[idx])
+        return got
+
+    def target_calculator(self, scene_shape, device=None):
+        """The reference's `rpn_target_calculator` (anchor.py:148-165 get_bbox_targets) over exactly the inside anchors
+        `forward` returns for a scene of `scene_shape` voxels (every level's grid: scene_shape / its stride)
+        (loss.RpnTargetCalculator, scn_rpn_targets)."""
+        from .loss import RpnTargetCalculator
+        device = device if device is not None else self.levels[0].head.weight.device
+        scene = tuple(int(v) for v in scene_shape)
+        level_anchors = [l.anchors_for(tuple(v // l.stride for v in scene), device) for l in self.levels]
+        return RpnTargetCalculator(self._inside(level_anchors, scene, device)[1])
+
     def combine(self, outs, scene_shape):
         """Per-level (rpn_bbox, rpn_score, anchors) over ALL anchors of each level -> the reference's concatenation in level
         order with the anchors that leave `scene_shape` dropped (`rpn_bbox_score_splitter`, anchor.py:177-197)."""
-        key = (tuple(scene_shape), tuple(o[2].shape[0] for o in outs), str(outs[0][0].device))
-        got = self._cache.get(key)
-        if got is None:
-            anchors = torch.cat([o[2] for o in outs], 0)
-            idx = inside_indicator(anchors, torch.tensor(scene_shape, dtype=torch.float32), self.allowed_border).nonzero().squeeze(1)
-            got = self._cache[key] = (idx, anchors[idx])
-        idx, anchors = got
+        idx, anchors = self._inside([o[2] for o in outs], tuple(scene_shape), outs[0][0].device)
         rpn_bbox = torch.cat([o[0] for o in outs], 1).index_select(1, idx)
         rpn_score = torch.cat([o[1] for o in outs], 1).index_select(1, idx)
         rpn_score.cell_flags = [f for o in outs for f in getattr(o[1], "cell_flags", [])]

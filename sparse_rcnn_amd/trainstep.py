@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib as L
 from .dp import FlatParams, broadcast_params
 from .maskhead import MaskBranch
 from .synthetic import make_batch, make_boxes
@@ -111,8 +112,13 @@ class SparseStepModel(torch.nn.Module):
 class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        """optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False):
+        """rpn_loss (the `-rpn` workloads only): train the RPN on the reference's RPN loss (loss.RpnLoss with
+        BatchwiseBboxTargetSelector(0.35, 0.15, 1/8), sigma 2; scannet_config/run.py:359-368,876-884) against the scene's
+        synthetic boxes, in place of the fixed synthetic gradient on rpn_bbox / rpn_score.  Targets and draw are queued before
+        the backbone forward; the two loss values stay on the device as `.rpn_losses`.  The mask branch keeps its synthetic
+        gradient.
+        optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
         1449: the fused Adam launch of optim.FlatAdam with `betas`, `eps`, `weight_decay`; lr=None -> the reference's 4e-4).
         batches_per_step: micro-batches whose gradients are accumulated before ONE all-reduce + update, each scaled by
         1 / batches_per_step -- the reference's `(loss / batches_per_step).backward()` ... `optimizer.step()`
@@ -122,6 +128,8 @@ class SceneStep:
         (each rank in proportion to its active voxels: what a loss normalised by batch-level counts gives when the
         batch is sharded one scene per rank, loss.py:401-431; the counts are summed over ranks once per step)."""
         ch, gr, tg, nb, self.baseline_entry, n_samples = WORKLOADS[workload]
+        if rpn_loss and not workload.endswith("-rpn"):
+            raise ValueError("rpn_loss=True needs an RPN in the step (the -rpn workloads)")
         self.workload, self.dtype, self.prefetch = workload, dtype, prefetch
         # lr=None: the workload's default (reported by describe() and in bench.py's line).  1e-6, and 1e-8 with an RPN in the
         # step: the SAME synthetic gradient on 3.7 M RPN outputs every step is a steady push, not noise -- at 1e-6 the score
@@ -169,6 +177,14 @@ class SceneStep:
                                      batchnorm=workload.endswith("-bn")).to(self.device)
         if self.with_rpn:
             self._init_rpn()
+        self.rpn_loss = bool(rpn_loss)
+        self.rpn_losses = None
+        self.keep_rpn_grads = False            # (tests: retain the gradients that reach rpn_bbox / rpn_score)
+        if self.rpn_loss:
+            from .loss import BatchwiseBboxTargetSelector, RpnLoss
+            self.rpn_criterion = RpnLoss(BatchwiseBboxTargetSelector(0.35, 0.15, max_weight=1 / 8, seed=seed), sigma=2.)
+            self._rpn_targets = {}
+            self._rpn_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
         self.adam = None
@@ -194,6 +210,23 @@ class SceneStep:
 
     def _scene_shape(self):
         return tuple(float(v) for v in self.size)
+
+    def _rpn_target_setup(self, k):
+        """(calculator over the inside anchors of micro-batch k's scene, its boxes concatenated on the device, host offsets):
+        a function of the scene shape and the scene's boxes only, built once."""
+        got = self._rpn_targets.get(k)
+        if got is None:
+            rpn = self.model.rpn
+            if hasattr(rpn, "levels"):
+                calc = rpn.target_calculator(tuple(int(v) for v in self.size), self.device)
+            else:
+                calc = rpn.target_calculator(tuple(int(v) // rpn.stride for v in self.size), self.device)
+            offs = [0]
+            for b in self.boxes:
+                offs.append(offs[-1] + b.shape[0])
+            gt = torch.cat([b.reshape(-1, 6) for b in self.boxes], 0).float().to(self.device) if offs[-1] else None
+            got = self._rpn_targets[k] = (calc, gt, offs)
+        return got
 
     def _init_rpn(self):
         """Random-init heads give near-constant scores; the synthetic RPN gets a head whose scores spread (so that top-k and
@@ -253,6 +286,13 @@ class SceneStep:
         cut = None
         if m.mask is not None and EARLY_ROI_CUT:
             cut = m.mask.prepare_cut(self.coords, self.size, self.boxes)      # (resident int64 coords: no dependency on md)
+        rpn_prep = None
+        if self.rpn_loss:
+            # the RPN loss's targets and draw depend on the anchors (the scene shape) and the boxes only: queued ahead of the
+            # backbone, they overlap nothing the forward waits for
+            calc, gt, offs = self._rpn_target_setup(k)
+            ov, am, tg = calc.from_concatenated(gt, offs)
+            rpn_prep = (ov, am, tg) + tuple(self.rpn_criterion.bbox_target_selector(ov))
         out = m.backbone(self.coords, fin, self.size, self.batch_size, metadata=md, after_encoder=hook)
         self._start_prefetch(k)      # (LATE_PREFETCH: the helper thread is started once this batch's forward kernels are queued)
         gy = self._gys.get(k)
@@ -286,12 +326,23 @@ class SceneStep:
                 self.rpn_out = (rpn_bbox, rpn_score, anchors, roi_score, boxes, roi_index)
                 if self.mask_boxes is not None:       # (the reference's mask head trains on <= 24 selected proposals per sample)
                     boxes = [b[:self.mask_boxes] for b in boxes]
-                gr = self._grs.get(k)
-                if gr is None or gr[0].shape != rpn_bbox.shape:
-                    gr = self._grs[k] = tuple((torch.randn(t.shape, generator=self._gen) * 1e-3).to(self.device)
-                                              for t in (rpn_bbox, rpn_score))
-                roots += [rpn_bbox, rpn_score]
-                root_grads += [g if scale == 1.0 else g * scale for g in gr]
+                if self.keep_rpn_grads:
+                    rpn_bbox.retain_grad()
+                    rpn_score.retain_grad()
+                if self.rpn_loss:
+                    calc = self._rpn_targets[k][0]
+                    if calc.anchors.data_ptr() != anchors.data_ptr() or calc.anchors.shape != anchors.shape:
+                        raise L.ScnError("SceneStep: the RPN loss's anchors are not the ones the RPN returned")
+                    self.rpn_losses = self.rpn_criterion.loss(rpn_prep, rpn_score, rpn_bbox)
+                    roots += list(self.rpn_losses)           # (score_loss + bbox_loss) / batches_per_step
+                    root_grads += [self._rpn_grad, self._rpn_grad]
+                else:
+                    gr = self._grs.get(k)
+                    if gr is None or gr[0].shape != rpn_bbox.shape:
+                        gr = self._grs[k] = tuple((torch.randn(t.shape, generator=self._gen) * 1e-3).to(self.device)
+                                                  for t in (rpn_bbox, rpn_score))
+                    roots += [rpn_bbox, rpn_score]
+                    root_grads += [g if scale == 1.0 else g * scale for g in gr]
             logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
             gm = self._gms.get(k)
             if gm is None or gm.shape != logits.shape:
@@ -399,6 +450,9 @@ class SceneStep:
                   "points) -> mask branch (SubM1 + 2 units @16, internal U-Net 23-32-48-64, Linear 23-32-18); CROP + MASK "
                   "BRANCH ONLY: the boxes are synthetic and known before the forward (no RPN in this step; "
                   "--workload cfg3-rpn has it)")
+        if self.rpn_loss:
+            s += ("; the RPN trains on the reference's RPN loss (BCE-with-logits + smooth L1, sigma 2) against the synthetic "
+                  "boxes: device anchor targets, batch-wide 0.35 / 0.15 sampling, max weight 1/8 (scn_rpnloss.hip)")
         if self.batches_per_step > 1:
             s += (f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
                   "voxels = all of them")
