@@ -63,7 +63,9 @@ extern "C" {
  *      additive within 5: + scn_adam_many / scn_adam_launches / scn_adam_segment_bytes, struct scn_adam_segment (124 entry
  *      points);
  *      additive within 5: + scn_rpn_targets, scn_rpn_sample_workspace_bytes / scn_rpn_sample_batchwise,
- *      scn_rpn_loss_scratch_bytes / scn_rpn_loss, scn_rpn_loss_scale (130 entry points) */
+ *      scn_rpn_loss_scratch_bytes / scn_rpn_loss, scn_rpn_loss_scale (130 entry points);
+ *      additive within 5: + scn_mask_overlap_draw, scn_mask_loss_scratch_bytes / scn_mask_loss, scn_mask_loss_bwd,
+ *      scn_mask_pack (135 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -838,6 +840,57 @@ int scn_rpn_loss(const float* score, const float* bbox, const float* label, cons
                  float* dscore, float* dbbox, scn_stream_t stream);
 int scn_rpn_loss_scale(const float* dscore, const float* dbbox, int64_t n, const float* grad_score_loss,
                        const float* grad_bbox_loss, float* out_dscore, float* out_dbbox, scn_stream_t stream);
+
+/* ---- mask loss (ndsis/modules/model.py OverlapCalculator, TrainSelector(0.2, 0, (24, 0, True)), SparseMaskLossSelector;
+ * ndsis/modules/loss.py MaskLoss) ----
+ * Every call is graph-capturable: the per-sample tables below are HOST arrays copied into the kernel arguments (32 samples
+ * per launch), nothing is allocated, copied or waited for.
+ *
+ * scn_mask_overlap_draw: pred_boxes fp32 [P][2][3] and gt_boxes fp32 [G][2][3] = (start, stop); sample b owns the proposals
+ * pred_offsets[b] .. pred_offsets[b+1]-1 (at most 1024 per sample) and the boxes gt_offsets[b] .. gt_offsets[b+1]-1 (both
+ * offset arrays: batch+1 non-decreasing values from 0).  overlaps_given = 0: max_overlap[i] = the largest IoU of proposal i
+ * with a box of its sample, argmax[i] = that box's index within the sample (ties: the lowest), 0 and 0 without boxes; the IoU
+ * follows bbox_overlap_prediction's operation order with every operation rounded once (bit-equal to the reference); either
+ * output may be NULL.  overlaps_given = 1: max_overlap / argmax are read instead.  fwd_boxes NULL: nothing else happens.
+ * Otherwise the draw: positives = max_overlap >= positive_threshold; n_drawn[b] = min(num_positive, #positives of b) of them
+ * are drawn uniformly without replacement.  Forward boxes of sample b start at fwd_offsets[b] (HOST, from 0) and hold
+ * cap_b = min(num_positive, P_b) slots, then the G_b boxes of the sample in order:
+ *   slot q < n_drawn[b]: the drawn proposal's box, gt_association = its argmax, pred_selection = its index within the sample;
+ *   slot q >= n_drawn[b]: start = stop = 0 (a box that selects no point), gt_association = -1, pred_selection = -1;
+ *   box cap_b + g: gt_boxes[g] of the sample, gt_association = g.
+ * pred_selection (may be NULL) is [sum cap_b] int64, sample b's slots at fwd_offsets[b] - gt_offsets[b]; n_drawn (may be
+ * NULL) is [batch] int64.  The drawn slots are in ascending key order, key = a keyed 32-bit bijection of (sample, index)
+ * whose round keys derive from (seed, counter): the draw is a function of those only.  batch < 65536.
+ *
+ * scn_mask_loss: logits fp32 [m][k] over the crop's rows; src_row / box_of int32 [m] (RoiSelection: box-major, the rows of
+ * a box contiguous); gt_association int64 [n_boxes], n_boxes = box_offsets[batch], the boxes of sample b at box_offsets[b] ..
+ * box_offsets[b+1]-1; labels int64 [gt_offsets[batch]], sample b's at gt_offsets[b]; mask_words: sample b's instances
+ * packed as [G_b][ceil(N_b / 32)] uint32 at word_offsets[b] (bit p % 32 of word p / 32 = point row p of the sample, as
+ * scn_mask_pack writes them), N_b = point_offsets[b+1] - point_offsets[b] and point row p = src_row - point_offsets[b].
+ * All four offset arrays are HOST arrays of batch+1 values.  A box whose association is outside 0 .. G_b-1 or whose label is
+ * outside 0 .. k-1 is dropped, and so is a box without rows (the reference's NaN).  loss = sum_b w_b l_b / sum_b w_b over the
+ * boxes kept, l_b = the mean BCE-with-logits of the box's label column against the instance's bits, w_b =
+ * class_weights[label] (fp32 [k], or NULL: 1); 0 if no box is kept.  Sums in double, fixed order: bitwise identical reruns.
+ * scratch: scn_mask_loss_scratch_bytes(n_boxes, m), 8-byte aligned; it keeps what scn_mask_loss_bwd reads.
+ *
+ * scn_mask_loss_bwd: dlogits fp32 [m][k] = *grad_loss * (sigmoid(x) - t) * w_b / (rows_b * sum w) in the label column of the
+ * row's box, 0 elsewhere; scratch as left by scn_mask_loss with the same n_boxes and m.
+ *
+ * scn_mask_pack: masks[b] = device bool / uint8 [n_gt[b]][n_points[b]] (HOST array of device pointers) -> out_words, the
+ * samples back to back in the layout above. */
+int scn_mask_overlap_draw(const float* pred_boxes, const int64_t* pred_offsets, const float* gt_boxes, const int64_t* gt_offsets,
+                          int batch, float* max_overlap, int64_t* argmax, int overlaps_given, float positive_threshold,
+                          int num_positive, uint64_t seed, uint64_t counter, const int64_t* fwd_offsets, float* fwd_boxes,
+                          int64_t* gt_association, int64_t* pred_selection, int64_t* n_drawn, scn_stream_t stream);
+int64_t scn_mask_loss_scratch_bytes(int64_t n_boxes, int64_t m);
+int scn_mask_loss(const float* logits, int64_t m, int k, const int32_t* src_row, const int32_t* box_of,
+                  const int64_t* gt_association, const int64_t* box_offsets, const int64_t* labels, const int64_t* gt_offsets,
+                  const uint32_t* mask_words, const int64_t* word_offsets, const int64_t* point_offsets, int batch,
+                  const float* class_weights, void* scratch, float* loss, scn_stream_t stream);
+int scn_mask_loss_bwd(const float* grad_loss, const void* scratch, int64_t n_boxes, int64_t m, int k, const int32_t* box_of,
+                      float* dlogits, scn_stream_t stream);
+int scn_mask_pack(const uint8_t* const* masks, const int64_t* n_gt, const int64_t* n_points, int batch, uint32_t* out_words,
+                  scn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ from .modules import (AddTable, AveragePooling, BatchNormLeakyReLU, BatchNormReL
 from .tensor import SparseConvNetTensor                                    # noqa: F401
 from .custom_operations import SparseGlobalPool, split_batch               # noqa: F401  (device forms of the reference's own helpers)
 from . import optim                                                         # noqa: F401  (optim.Adam: the reference's optimizer)
-from . import loss                                                          # noqa: F401  (loss.RpnLoss: the reference's RPN loss)
+from . import loss                                                          # noqa: F401  (loss.RpnLoss, loss.MaskLoss: the reference's RPN and mask losses)
 
 __all__ = [
     "Metadata", "SparseConvNetTensor", "ioLayers", "InputLayer", "OutputLayer", "Sequential", "ConcatTable",

@@ -149,6 +149,13 @@ _SIGS = {
     "scn_rpn_loss_scratch_bytes": (i64, [i64]),
     "scn_rpn_loss": (C.c_int, [p, p, p, p, p, p, i64, f32, p, p, p, p, p, p]),
     "scn_rpn_loss_scale": (C.c_int, [p, p, i64, p, p, p, p, p]),
+    "scn_mask_overlap_draw": (C.c_int, [p, C.POINTER(i64), p, C.POINTER(i64), i32, p, p, i32, f32, i32, C.c_uint64,
+                                        C.c_uint64, C.POINTER(i64), p, p, p, p, p]),
+    "scn_mask_loss_scratch_bytes": (i64, [i64, i64]),
+    "scn_mask_loss": (C.c_int, [p, i64, i32, p, p, p, C.POINTER(i64), p, C.POINTER(i64), p, C.POINTER(i64), C.POINTER(i64), i32,
+                                p, p, p, p]),
+    "scn_mask_loss_bwd": (C.c_int, [p, p, i64, i64, i32, p, p, p]),
+    "scn_mask_pack": (C.c_int, [C.POINTER(p), C.POINTER(i64), C.POINTER(i64), i32, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -12,8 +12,12 @@
 Nothing on this path waits on the host: no `.item()`, `.cpu()` or `nonzero`.  The targets and the draw depend on the anchors and
 the boxes only, so they can be queued before the network that produces rpn_score / rpn_bbox runs (`RpnLoss.prepare`).
 Each data-parallel rank normalises over its own samples (the reference's batch is one process).
+
+The mask loss (OverlapCalculator, TrainSelector, MaskLoss: the second half of this file) follows the same rules.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 from torch import nn
@@ -230,3 +234,376 @@ class RpnLoss(nn.Module):
 
     def forward(self, gt_bbox, rpn_target_calculator, rpn_score, rpn_bbox):
         return self.loss(self.prepare(gt_bbox, rpn_target_calculator), rpn_score, rpn_bbox)
+
+
+# ---- mask loss ----------------------------------------------------------------------------------------------------------
+# The reference's mask-training path (ndsis/modules/model.py OverlapCalculator :896-916, TrainSelector :919-1014,
+# SparseMaskLossSelector :1152-1227; ndsis/modules/loss.py MaskLoss :271-318) on the device (csrc/scn_maskloss.hip):
+#
+#     roi boxes, gt boxes  --OverlapCalculator / TrainSelector-->  forward boxes (drawn proposals ++ all gt), gt_association
+#         (scn_mask_overlap_draw: IoU, max, argmax and the draw in one launch, one workgroup per sample)
+#     --MaskBranch (crop + network)-->  mask_scores [M, K], (RoiSelection, counts, batch_splits)
+#     --MaskLoss-->  0-dim loss (scn_mask_loss: per-box BCE in double + one finishing block; backward: one launch)
+#
+# Nothing here waits on the host: every count the kernels need is a shape (the proposals per sample after RoiSelector.finish,
+# the ground truths per sample, the crop's rows), and the tables travel in the kernel arguments.
+
+from collections import namedtuple
+
+SelectionDescriptor = namedtuple("SelectionDescriptor", ["forward_boxes", "pred_selection", "gt_selection", "gt_association"])
+
+__all__ += ["OverlapCalculator", "TrainSelector", "SelectionDescriptor", "PackedMasks", "pack_gt_masks", "MaskLoss"]
+
+MAX_PROPOSALS_PER_SAMPLE = 1024            # csrc/scn_maskloss.hip kMaxProposals
+
+
+def _boxes_list(boxes, name):
+    out = []
+    for i, b in enumerate(boxes):
+        if not torch.is_tensor(b) or b.dim() != 3 or tuple(b.shape[1:]) != (2, 3):
+            raise ValueError(f"{name}[{i}]: [n, 2, 3] (start, stop) boxes required, got "
+                             f"{tuple(b.shape) if torch.is_tensor(b) else type(b).__name__}")
+        if not b.is_cuda:
+            raise L.ScnError(f"{name}[{i}]: a GPU tensor is required (there is no CPU path)")
+        if b.dtype != torch.float32:
+            raise ValueError(f"{name}[{i}]: fp32 is required, got {b.dtype}")
+        out.append(b.detach())
+    return out
+
+
+def _flat(tensors, dtype, device, tail=()):
+    """One contiguous tensor over a list: a view when the members already lie back to back in one storage (what
+    TrainSelector and SceneStep hand out), else torch.cat (a device copy, no host wait)."""
+    n = sum(int(t.shape[0]) for t in tensors)
+    if n == 0:
+        return torch.empty((0,) + tuple(tail), dtype=dtype, device=device)
+    first = tensors[0]
+    adjacent = all(t.is_contiguous() and t.dtype == dtype and t.device == first.device for t in tensors)
+    if adjacent:                  # (one storage: two allocations may also lie back to back)
+        base = first.untyped_storage().data_ptr()
+        adjacent = all(t.untyped_storage().data_ptr() == base for t in tensors if t.shape[0])
+    if adjacent:
+        row = first.element_size() * (first[0].numel() if first.shape[0] else 1)
+        ptr = first.data_ptr()
+        for t in tensors:
+            if t.shape[0] and t.data_ptr() != ptr:
+                adjacent = False
+                break
+            ptr += int(t.shape[0]) * row
+    if adjacent and first.shape[0]:
+        return first.as_strided((n,) + tuple(first.shape[1:]), first.stride())
+    return torch.cat([t.reshape((-1,) + tuple(tail)).to(dtype) for t in tensors], 0).contiguous()
+
+
+def _offsets(counts):
+    ho = L.host_i64(len(counts) + 1)
+    acc = 0
+    ho[0] = 0
+    for i, c in enumerate(counts):
+        acc += int(c)
+        ho[i + 1] = acc
+    return ho
+
+
+class OverlapCalculator(nn.Module):
+    """`OverlapCalculator()` (model.py:896-916): forward(pred_bbox_list, gt_bbox_list) -> [(pred_bbox, gt_bbox, max_overlap,
+    argmax_overlap)] per sample; max_overlap fp32 [P_s] and argmax int64 [P_s] (first index of the maximum; 0 and 0 for a
+    sample without ground truth).  The IoU is bbox_overlap_prediction's, bit-equal.  One launch for the batch."""
+
+    def forward(self, pred_bbox_list, gt_bbox_list):
+        preds = _boxes_list(pred_bbox_list, "pred_bbox")
+        gts = _boxes_list(gt_bbox_list, "gt_bbox")
+        if len(preds) != len(gts):
+            raise ValueError(f"{len(preds)} proposal lists and {len(gts)} ground-truth lists")
+        for i, p in enumerate(preds):
+            if p.shape[0] > MAX_PROPOSALS_PER_SAMPLE:
+                raise ValueError(f"pred_bbox[{i}]: at most {MAX_PROPOSALS_PER_SAMPLE} proposals per sample")
+        if not preds:
+            return []
+        dev = preds[0].device
+        pc = [int(p.shape[0]) for p in preds]
+        pred = _flat(preds, torch.float32, dev, (2, 3))
+        gt = _flat(gts, torch.float32, dev, (2, 3))
+        mx = torch.empty(sum(pc), dtype=torch.float32, device=dev)
+        am = torch.empty(sum(pc), dtype=torch.int64, device=dev)
+        L.check(L.lib().scn_mask_overlap_draw(L.ptr(pred), _offsets(pc), L.ptr(gt), _offsets([g.shape[0] for g in gts]), len(pc),
+                                              L.ptr(mx), L.ptr(am), 0, 0.0, 0, 0, 0, None, None, None, None, None, L.stream()))
+        out, o = [], 0
+        for p, g, n in zip(pred_bbox_list, gt_bbox_list, pc):
+            out.append((p, g, mx[o:o + n], am[o:o + n]))
+            o += n
+        return out
+
+
+class TrainSelector(nn.Module):
+    """`TrainSelector(positive_threshold, negative_threshold=0, random_selector=(24, 0, True))` (model.py:919-1014) as the
+    reference's mask network configures it (run.py:799-810): per sample, min(num_pos, #positives) proposals with
+    max_overlap >= positive_threshold are drawn uniformly without replacement, and every ground-truth box is appended.
+
+    forward(descriptions) -> (forward_boxes_list, SelectionDescriptor list), descriptions = OverlapCalculator's output.
+    Fixed-capacity layout (no count leaves the device): sample s has cap_s = min(num_pos, P_s) slots, then its G_s ground
+    truths.  The first min(num_pos, #positives) slots hold the drawn proposals; the others hold the box start = stop = 0,
+    which the crop gives no point, with gt_association -1 and pred_selection -1 -- the reference drops such a box's NaN loss,
+    so the loss and its gradients are those of the reference's selection.  gt_selection = arange(G_s).
+    The draw is a function of (seed, draw counter); the counter advances by one per call and is kept in state_dict
+    (as BatchwiseBboxTargetSelector's).  `select(pred_bbox_list, gt_bbox_list)` = OverlapCalculator + forward in one launch.
+    `last_drawn`: int64 [batch] device tensor, the proposals drawn per sample."""
+
+    SelectionDescriptor = SelectionDescriptor
+
+    def __init__(self, positive_threshold, negative_threshold=0, random_selector=(24, 0, True), seed=0):
+        super().__init__()
+        if negative_threshold:
+            raise ValueError("TrainSelector: negative_threshold != 0 is not provided (the reference's mask and class paths "
+                             "use 0)")
+        if random_selector is None:
+            raise ValueError("TrainSelector: random_selector=None is not provided (the reference's `all_selector` branch "
+                             "raises NameError)")
+        if not (isinstance(random_selector, tuple) and len(random_selector) == 3):
+            raise ValueError("TrainSelector: random_selector = (num_pos, num_neg, use_gt) required")
+        num_pos, num_neg, use_gt = random_selector
+        if num_neg:
+            raise ValueError("TrainSelector: num_neg != 0 is not provided (no negatives are drawn at negative_threshold 0)")
+        if not use_gt:
+            raise ValueError("TrainSelector: use_gt=False is not provided (the reference's configuration appends the "
+                             "ground truth)")
+        if int(num_pos) < 0:
+            raise ValueError("TrainSelector: num_pos >= 0 required")
+        self.positive_threshold = float(positive_threshold)
+        self.negative_threshold = 0
+        self.num_pos = int(num_pos)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.counter = 0
+        self.last_drawn = None
+        self._arange = None
+
+    def get_extra_state(self):
+        return {"seed": self.seed, "counter": self.counter}
+
+    def set_extra_state(self, state):
+        self.seed, self.counter = int(state["seed"]), int(state["counter"])
+
+    def _gt_range(self, n, dev):
+        a = self._arange
+        if a is None or a.numel() < n or a.device != dev:
+            a = self._arange = torch.arange(max(n, 256), dtype=torch.int64, device=dev)
+        return a[:n]
+
+    def _run(self, preds, gts, counter, mx=None, am=None):
+        for i, p in enumerate(preds):
+            if p.shape[0] > MAX_PROPOSALS_PER_SAMPLE:
+                raise ValueError(f"pred_bbox[{i}]: at most {MAX_PROPOSALS_PER_SAMPLE} proposals per sample")
+        if len(preds) != len(gts):
+            raise ValueError(f"{len(preds)} proposal lists and {len(gts)} ground-truth lists")
+        if not preds:
+            return [], [], []
+        dev = preds[0].device
+        pc = [int(p.shape[0]) for p in preds]
+        gc = [int(g.shape[0]) for g in gts]
+        cap = [min(self.num_pos, n) for n in pc]
+        pred = _flat(preds, torch.float32, dev, (2, 3))
+        gt = _flat(gts, torch.float32, dev, (2, 3))
+        given = mx is not None
+        if not given:
+            mx = torch.empty(sum(pc), dtype=torch.float32, device=dev)
+            am = torch.empty(sum(pc), dtype=torch.int64, device=dev)
+        nf = sum(cap) + sum(gc)
+        fwd = torch.empty((nf, 2, 3), dtype=torch.float32, device=dev)
+        assoc = torch.empty(nf, dtype=torch.int64, device=dev)
+        psel = torch.empty(sum(cap), dtype=torch.int64, device=dev)
+        drawn = torch.empty(len(pc), dtype=torch.int64, device=dev)
+        L.check(L.lib().scn_mask_overlap_draw(L.ptr(pred), _offsets(pc), L.ptr(gt), _offsets(gc), len(pc), L.ptr(mx), L.ptr(am),
+                                              1 if given else 0, self.positive_threshold, self.num_pos, self.seed,
+                                              int(counter) & (2 ** 64 - 1), _offsets([c + g for c, g in zip(cap, gc)]),
+                                              L.ptr(fwd), L.ptr(assoc), L.ptr(psel), L.ptr(drawn), L.stream()))
+        self.last_drawn = drawn
+        fwd_list, descs, overlaps = [], [], []
+        f = o = s = 0
+        for p, g, n, c, ng in zip(preds, gts, pc, cap, gc):
+            fb = fwd[f:f + c + ng]
+            fwd_list.append(fb)
+            descs.append(SelectionDescriptor(fb, psel[s:s + c], self._gt_range(ng, dev), assoc[f:f + c + ng]))
+            overlaps.append((p, g, mx[o:o + n], am[o:o + n]))
+            f, o, s = f + c + ng, o + n, s + c
+        return overlaps, fwd_list, descs
+
+    def draw(self, descriptions, counter):
+        """forward() for an explicit draw counter (the counter of this module is left alone)."""
+        descriptions = list(descriptions)
+        preds = _boxes_list([d[0] for d in descriptions], "pred_bbox")
+        gts = _boxes_list([d[1] for d in descriptions], "gt_bbox")
+        dev = preds[0].device if preds else None
+        mx = _flat([_device_f32(d[2], "max_overlap") for d in descriptions], torch.float32, dev)
+        am_parts = []
+        for i, d in enumerate(descriptions):
+            a = d[3]
+            if not torch.is_tensor(a) or a.dtype != torch.int64 or not a.is_cuda or a.shape != (preds[i].shape[0],):
+                raise ValueError(f"argmax_overlap[{i}]: int64 GPU [P_s] required")
+            if d[2].shape != (preds[i].shape[0],):
+                raise ValueError(f"max_overlap[{i}]: [P_s] required")
+            am_parts.append(a)
+        am = _flat(am_parts, torch.int64, dev)
+        _, fwd_list, descs = self._run(preds, gts, counter, mx, am)
+        return tuple(fwd_list), tuple(descs)
+
+    def forward(self, descriptions):
+        out = self.draw(descriptions, self.counter)
+        self.counter += 1
+        return out
+
+    def select(self, pred_bbox_list, gt_bbox_list):
+        """OverlapCalculator and forward in ONE launch: -> (overlap descriptions, forward_boxes_list, descriptors)."""
+        out = self._run(_boxes_list(pred_bbox_list, "pred_bbox"), _boxes_list(gt_bbox_list, "gt_bbox"), self.counter)
+        self.counter += 1
+        return out
+
+
+class PackedMasks:
+    """Ground-truth instance masks packed on the device: `words` int32 (uint32 bit patterns), sample s's [G_s][ceil(N_s / 32)]
+    words from `word_offsets[s]`, bit p % 32 of word p / 32 = point row p of the sample.  n_gt / n_points: host lists."""
+
+    def __init__(self, words, n_gt, n_points):
+        self.words, self.n_gt, self.n_points = words, list(n_gt), list(n_points)
+        self.word_offsets = [0]
+        for g, n in zip(self.n_gt, self.n_points):
+            self.word_offsets.append(self.word_offsets[-1] + g * ((n + 31) // 32))
+
+    def __len__(self):
+        return len(self.n_gt)
+
+    def unpack(self, s):
+        """bool device [G_s, N_s] of sample s (for checks)."""
+        g, n = self.n_gt[s], self.n_points[s]
+        w = (n + 31) // 32
+        words = self.words[self.word_offsets[s]:self.word_offsets[s + 1]].view(g, w)
+        bits = (words.unsqueeze(-1) >> torch.arange(32, device=words.device, dtype=torch.int32)) & 1
+        return bits.reshape(g, w * 32)[:, :n].bool()
+
+
+def pack_gt_masks(gt_mask_list):
+    """list (one per sample) of bool / uint8 [G_s, N_s] masks over the sample's point rows (the reference's batch['gt_mask'])
+    -> PackedMasks on the masks' device.  One launch."""
+    masks = []
+    for i, m in enumerate(gt_mask_list):
+        if not torch.is_tensor(m) or m.dim() != 2:
+            raise ValueError(f"gt_mask[{i}]: [G, N] required")
+        if not m.is_cuda:
+            raise L.ScnError(f"gt_mask[{i}]: a GPU tensor is required (there is no CPU path)")
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"gt_mask[{i}]: bool or uint8 required, got {m.dtype}")
+        masks.append(m.contiguous().view(torch.uint8))
+    dev = masks[0].device if masks else torch.device("cuda", torch.cuda.current_device())
+    n_gt = [int(m.shape[0]) for m in masks]
+    n_pt = [int(m.shape[1]) for m in masks]
+    out = PackedMasks(None, n_gt, n_pt)
+    out.words = torch.empty(max(out.word_offsets[-1], 1), dtype=torch.int32, device=dev)
+    B = len(masks)
+    if B:
+        ptrs = (C.c_void_p * B)(*[m.data_ptr() for m in masks])
+        L.check(L.lib().scn_mask_pack(ptrs, (L.i64 * B)(*n_gt), (L.i64 * B)(*n_pt), B,
+                                      L.ptr(out.words), L.stream()))
+    return out
+
+
+class _MaskLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, src_row, box_of, assoc, box_offs, labels, gt_offs, packed, pt_offs, class_weights):
+        m, k = scores.shape
+        n_boxes = int(assoc.shape[0])
+        dev = scores.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        scratch = torch.empty(L.lib().scn_mask_loss_scratch_bytes(n_boxes, m), dtype=torch.uint8, device=dev)
+        B = len(box_offs) - 1
+        L.check(L.lib().scn_mask_loss(L.ptr(scores), m, k, L.ptr(src_row), L.ptr(box_of), L.ptr(assoc), _host(box_offs),
+                                      L.ptr(labels), _host(gt_offs), L.ptr(packed.words), _host(packed.word_offsets),
+                                      _host(pt_offs), B, L.ptr(class_weights), L.ptr(scratch), L.ptr(loss), L.stream()))
+        ctx.save_for_backward(scratch, box_of)
+        ctx.dims = (n_boxes, m, k)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        scratch, box_of = ctx.saved_tensors
+        n_boxes, m, k = ctx.dims
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 10
+        d = torch.empty((m, k), dtype=torch.float32, device=scratch.device)
+        gg = g.float().contiguous()
+        L.check(L.lib().scn_mask_loss_bwd(L.ptr(gg), L.ptr(scratch), n_boxes, m, k, L.ptr(box_of), L.ptr(d), L.stream()))
+        return (d,) + (None,) * 9
+
+
+def _host(offs):
+    ho = L.host_i64(len(offs))
+    for i, v in enumerate(offs):
+        ho[i] = int(v)
+    return ho
+
+
+class MaskLoss(nn.Module):
+    """`SparseMaskLossSelector` (the branch with a selection description, model.py:1152-1227) and `MaskLoss(class_weights)`
+    (loss.py:271-318) fused: forward(mask_scores [M, K] fp32, selection, descriptions, gt_label, gt_mask) -> 0-dim fp32 loss
+    with autograd to mask_scores.  selection = (RoiSelection, box counts per sample, points per sample) as MaskBranch.forward
+    returns it; descriptions = TrainSelector's SelectionDescriptor list (gt_association per forward box, -1: no ground
+    truth); gt_label = list of int64 [G_s] device tensors; gt_mask = PackedMasks or the list of bool [G_s, N_s] device masks.
+    Per box: the logit column of its instance's label, BCE-with-logits against the instance's mask bits, averaged over the
+    box's rows; boxes without rows (the reference's NaN) or without ground truth are dropped; the loss is the mean over the
+    remaining boxes (with class_weights: sum(w l) / sum(w)), or 0 if none remains."""
+
+    def __init__(self, class_weights=None):
+        super().__init__()
+        self.class_weights = None if class_weights is None else torch.as_tensor(class_weights, dtype=torch.float32)
+
+    def forward(self, mask_scores, selection, descriptions, gt_label, gt_mask):
+        from .roi import RoiSelection, selection_from_matrix
+        scores = _device_f32(mask_scores, "mask_scores")
+        if scores.dim() != 2:
+            raise ValueError(f"mask_scores: [M, K] required, got {tuple(scores.shape)}")
+        sel, box_counts, batch_splits = selection
+        if not isinstance(sel, RoiSelection):
+            sel = selection_from_matrix(sel)
+        dev = scores.device
+        m, k = scores.shape
+        if sel.src_row.shape[0] != m:
+            raise L.ScnError(f"mask_scores has {m} rows, the selection {sel.src_row.shape[0]}")
+        descriptions, gt_label = list(descriptions), list(gt_label)
+        box_counts = [int(c) for c in box_counts]
+        splits = [int(c) for c in batch_splits]
+        B = len(box_counts)
+        if not (len(descriptions) == len(gt_label) == len(splits) == B):
+            raise ValueError(f"{B} samples in the selection, {len(descriptions)} descriptions, {len(gt_label)} label lists, "
+                             f"{len(splits)} batch splits")
+        if sum(box_counts) != sel.n_boxes or sum(splits) != sel.n_points:
+            raise L.ScnError("box counts / batch splits do not match the selection")
+        assocs = []
+        for s, d in enumerate(descriptions):
+            a = d.gt_association if hasattr(d, "gt_association") else d[3]
+            if not torch.is_tensor(a) or a.dtype != torch.int64 or not a.is_cuda or a.shape != (box_counts[s],):
+                raise ValueError(f"descriptions[{s}].gt_association: int64 GPU [{box_counts[s]}] required (one per forward box)")
+            assocs.append(a)
+        for s, l in enumerate(gt_label):
+            if not torch.is_tensor(l) or l.dtype != torch.int64 or not l.is_cuda or l.dim() != 1:
+                raise ValueError(f"gt_label[{s}]: int64 GPU [G_s] required")
+        if not isinstance(gt_mask, PackedMasks):
+            gt_mask = pack_gt_masks(gt_mask)
+        if gt_mask.n_gt != [int(l.shape[0]) for l in gt_label] or gt_mask.n_points != splits:
+            raise ValueError(f"gt_mask: [G_s, N_s] = {list(zip(gt_mask.n_gt, gt_mask.n_points))} per sample required by the labels "
+                             f"and batch splits, {list(zip([int(l.shape[0]) for l in gt_label], splits))}")
+        cw = self.class_weights
+        if cw is not None:
+            if cw.numel() != k:
+                raise ValueError(f"class_weights: {k} entries (one per logit column) required, got {cw.numel()}")
+            if cw.device != dev:
+                cw = self.class_weights = cw.to(dev)
+        assoc = _flat(assocs, torch.int64, dev)
+        labels = _flat(gt_label, torch.int64, dev)
+        box_offs = [0]
+        for c in box_counts:
+            box_offs.append(box_offs[-1] + c)
+        gt_offs = [0]
+        for l in gt_label:
+            gt_offs.append(gt_offs[-1] + int(l.shape[0]))
+        pt_offs = [0]
+        for n in splits:
+            pt_offs.append(pt_offs[-1] + n)
+        return _MaskLossFunction.apply(scores, sel.src_row, sel.box_of, assoc, box_offs, labels, gt_offs, gt_mask, pt_offs, cw)

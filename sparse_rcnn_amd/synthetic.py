@@ -126,3 +126,31 @@ def make_boxes(coords, n_boxes=64, seed=3, lo=8.0, hi=96.0):
         stop = start + edge
         out.append(torch.from_numpy(np.stack([start, stop], 1).astype(np.float32)))
     return out
+
+
+def make_instances(coords, boxes, n_classes=18, seed=5):
+    """Synthetic ground-truth instances for the scene's boxes: per sample, (labels int64 [G_s] uniform over n_classes,
+    masks bool [G_s, N_s] over the sample's point rows, duplicates included -- the reference's batch['gt_label'] /
+    batch['gt_mask']).  Point p belongs to instance g if it lies inside box g under the ROI crop's own rule (floor(start)
+    <= x < ceil(stop) per axis, as scn_roi_boxes / the reference's BBoxTransformerSlice + get_inside_indicator apply it) AND
+    its voxel centre lies inside the ellipsoid inscribed in the box: some of a box's points, not all of them.
+    Deterministic, on the host.  -> (labels list, masks list) of CPU tensors."""
+    rng = np.random.default_rng(seed)
+    c = coords.numpy() if isinstance(coords, torch.Tensor) else np.asarray(coords)
+    labels, masks = [], []
+    for b, bx in enumerate(boxes):
+        pts = c[c[:, 3] == b][:, :3]
+        bx = (bx.numpy() if isinstance(bx, torch.Tensor) else np.asarray(bx)).astype(np.float32).reshape(-1, 2, 3)
+        g = len(bx)
+        labels.append(torch.from_numpy(rng.integers(0, n_classes, size=g).astype(np.int64)))
+        lo, hi = np.floor(bx[:, 0]).astype(np.int64), np.ceil(bx[:, 1]).astype(np.int64)
+        ctr = (bx[:, 0].astype(np.float64) + bx[:, 1]) / 2
+        rad = (bx[:, 1].astype(np.float64) - bx[:, 0]) / 2
+        m = np.zeros((g, len(pts)), dtype=bool)
+        centre = pts.astype(np.float64) + 0.5
+        for i in range(g):
+            inside = ((pts >= lo[i]) & (pts < hi[i])).all(1)
+            r = np.where(rad[i] > 0, rad[i], 1.0)
+            m[i] = inside & ((((centre - ctr[i]) / r) ** 2).sum(1) <= 1.0)
+        masks.append(torch.from_numpy(m))
+    return labels, masks

@@ -32,7 +32,7 @@ import torch
 from . import _lib as L
 from .dp import FlatParams, broadcast_params
 from .maskhead import MaskBranch
-from .synthetic import make_batch, make_boxes
+from .synthetic import make_batch, make_boxes, make_instances
 from .unet import Backbone
 
 REF_PLAN = (32, 48, 64, 80, 96, 112)      # the reference's own sparse U-Net plan, `arange * 16 + 32` (scannet_config/run.py:539-549,587-591)
@@ -112,12 +112,20 @@ class SparseStepModel(torch.nn.Module):
 class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None):
         """rpn_loss (the `-rpn` workloads only): train the RPN on the reference's RPN loss (loss.RpnLoss with
         BatchwiseBboxTargetSelector(0.35, 0.15, 1/8), sigma 2; scannet_config/run.py:359-368,876-884) against the scene's
         synthetic boxes, in place of the fixed synthetic gradient on rpn_bbox / rpn_score.  Targets and draw are queued before
-        the backbone forward; the two loss values stay on the device as `.rpn_losses`.  The mask branch keeps its synthetic
-        gradient.
+        the backbone forward; the two loss values stay on the device as `.rpn_losses`.
+        mask_loss (the `-rpn` workloads only): train the mask branch on the reference's mask loss (scannet_config/run.py:
+        398,799-810,857-862,876-891): after the proposal selection, loss.TrainSelector(0.2, 0, (24, 0, True)) draws up to 24
+        proposals per sample with IoU >= 0.2 against the scene's synthetic ground truth and appends every ground-truth box (one
+        launch), the mask branch crops and runs on those boxes, and loss.MaskLoss (BCE-with-logits of the instance's label
+        column against its mask, synthetic.make_instances) is backpropagated with gradient 1 / batches_per_step.  This
+        replaces both the seeded synthetic gradient on the mask logits and ref-crop-rpn's cut to the 24 best-scored
+        proposals.  The loss stays on the device as `.mask_losses`.  Without it the mask branch gets the synthetic gradient.
+        n_gt (the `-rpn` workloads): the ground-truth instances per sample both losses see are the first n_gt synthetic boxes
+        (None: all of them; ref-crop-rpn has 256 per crop, which would put > 3000 boxes through the mask branch).
         optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
         1449: the fused Adam launch of optim.FlatAdam with `betas`, `eps`, `weight_decay`; lr=None -> the reference's 4e-4).
         batches_per_step: micro-batches whose gradients are accumulated before ONE all-reduce + update, each scaled by
@@ -130,6 +138,13 @@ class SceneStep:
         ch, gr, tg, nb, self.baseline_entry, n_samples = WORKLOADS[workload]
         if rpn_loss and not workload.endswith("-rpn"):
             raise ValueError("rpn_loss=True needs an RPN in the step (the -rpn workloads)")
+        if mask_loss and not workload.endswith("-rpn"):
+            raise ValueError("mask_loss=True needs an RPN in the step (the -rpn workloads)")
+        if n_gt is not None and not workload.endswith("-rpn"):
+            raise ValueError("n_gt applies to the ground truth of the -rpn workloads")
+        if n_gt is not None and int(n_gt) < 1:
+            raise ValueError("n_gt >= 1 required")
+        self.n_gt = None if n_gt is None else int(n_gt)
         self.workload, self.dtype, self.prefetch = workload, dtype, prefetch
         # lr=None: the workload's default (reported by describe() and in bench.py's line).  1e-6, and 1e-8 with an RPN in the
         # step: the SAME synthetic gradient on 3.7 M RPN outputs every step is a steady push, not noise -- at 1e-6 the score
@@ -163,8 +178,10 @@ class SceneStep:
         for k in range(self.batches_per_step):
             coords, feats, size, bs, splits = make_batch(n_samples, self.grid, target or tg, dup=1.15, seed=seed + 1000 * k)
             boxes = make_boxes(coords, self.n_boxes, seed=seed + 1000 * k + 2) if self.n_boxes else None
+            gt_boxes = boxes if (boxes is None or self.n_gt is None) else [b[:self.n_gt] for b in boxes]
             self._scenes.append(dict(coords_cpu=coords, feats_cpu=feats, size=size, batch_size=bs, splits=splits,
-                                     coords=coords.to(self.device), feats=feats.to(self.device), boxes=boxes))   # resident in HBM
+                                     coords=coords.to(self.device), feats=feats.to(self.device), boxes=boxes,
+                                     gt_boxes=gt_boxes))   # resident in HBM
         self._use_scene(0)
         torch.manual_seed(0)
         self.with_rpn = workload.endswith("-rpn")
@@ -185,6 +202,29 @@ class SceneStep:
             self.rpn_criterion = RpnLoss(BatchwiseBboxTargetSelector(0.35, 0.15, max_weight=1 / 8, seed=seed), sigma=2.)
             self._rpn_targets = {}
             self._rpn_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
+        self.mask_loss = bool(mask_loss)
+        self.mask_losses = None
+        self.mask_out = None
+        self.keep_mask_grads = False           # (tests: retain the gradient that reaches the mask logits)
+        if self.mask_loss:
+            from .loss import MaskLoss, TrainSelector, pack_gt_masks
+            # run.py:799-810: mask_network_params.selection_tuple = (24, 0, True) behind TrainSelector(0.2); MaskLoss without
+            # class weights (run.py:398, 876-891)
+            self.mask_selector = TrainSelector(0.2, 0, (24, 0, True), seed=seed + 17)
+            self.mask_criterion = MaskLoss(class_weights=None)
+            self._mask_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
+            for k, sc in enumerate(self._scenes):      # instances built and packed once per scene
+                labels, masks = make_instances(sc["coords_cpu"], sc["gt_boxes"], n_classes=self.model.mask.classes,
+                                               seed=seed + 1000 * k + 5)
+                flat = torch.cat(labels).to(self.device)
+                views, o = [], 0
+                for l in labels:
+                    views.append(flat[o:o + l.shape[0]])
+                    o += l.shape[0]
+                sc["gt_label"] = views
+                sc["gt_mask_cpu"] = masks
+                sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in masks])
+                sc["gt_dev"] = [b.float().to(self.device) for b in sc["gt_boxes"]]
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
         self.adam = None
@@ -206,6 +246,7 @@ class SceneStep:
         self.coords_cpu, self.feats_cpu, self.size, self.batch_size, self.splits = (
             sc["coords_cpu"], sc["feats_cpu"], sc["size"], sc["batch_size"], sc["splits"])
         self.coords, self.feats, self.boxes = sc["coords"], sc["feats"], sc["boxes"]
+        self.gt_boxes = sc["gt_boxes"]
         self._k = k
 
     def _scene_shape(self):
@@ -222,9 +263,9 @@ class SceneStep:
             else:
                 calc = rpn.target_calculator(tuple(int(v) // rpn.stride for v in self.size), self.device)
             offs = [0]
-            for b in self.boxes:
+            for b in self.gt_boxes:
                 offs.append(offs[-1] + b.shape[0])
-            gt = torch.cat([b.reshape(-1, 6) for b in self.boxes], 0).float().to(self.device) if offs[-1] else None
+            gt = torch.cat([b.reshape(-1, 6) for b in self.gt_boxes], 0).float().to(self.device) if offs[-1] else None
             got = self._rpn_targets[k] = (calc, gt, offs)
         return got
 
@@ -284,7 +325,7 @@ class SceneStep:
         # boxes of a step are known before its backbone runs (here: synthetic; in the reference: the RPN's proposals of
         # the same forward, so this applies to the mask branch's SECOND use of a scene, e.g. evaluation on cached proposals)
         cut = None
-        if m.mask is not None and EARLY_ROI_CUT:
+        if m.mask is not None and EARLY_ROI_CUT and not self.mask_loss:
             cut = m.mask.prepare_cut(self.coords, self.size, self.boxes)      # (resident int64 coords: no dependency on md)
         rpn_prep = None
         if self.rpn_loss:
@@ -324,7 +365,14 @@ class SceneStep:
                 rpn_bbox, rpn_score, anchors, sel_state = rpn_state["out"]
                 roi_score, boxes, roi_index = m.roi_selector.finish(sel_state)
                 self.rpn_out = (rpn_bbox, rpn_score, anchors, roi_score, boxes, roi_index)
-                if self.mask_boxes is not None:       # (the reference's mask head trains on <= 24 selected proposals per sample)
+                descs = None
+                if self.mask_loss:
+                    # model.py:172-196: OverlapCalculator + TrainSelector on this forward's proposals, one launch; the mask
+                    # branch runs on the drawn proposals ++ every ground-truth box
+                    sc = self._scenes[k]
+                    _, boxes, descs = self.mask_selector.select(boxes, sc["gt_dev"])
+                    boxes = list(boxes)
+                elif self.mask_boxes is not None:     # (the reference's mask head trains on <= 24 selected proposals per sample)
                     boxes = [b[:self.mask_boxes] for b in boxes]
                 if self.keep_rpn_grads:
                     rpn_bbox.retain_grad()
@@ -345,7 +393,17 @@ class SceneStep:
                     root_grads += [g if scale == 1.0 else g * scale for g in gr]
             logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
             gm = self._gms.get(k)
-            if gm is None or gm.shape != logits.shape:
+            if self.mask_loss:
+                sc = self._scenes[k]
+                if self.keep_mask_grads and logits.requires_grad:
+                    logits.retain_grad()
+                self.mask_out = (selection, descs)
+                self.mask_losses = self.mask_criterion(logits, selection, descs, sc["gt_label"], sc["gt_mask"])
+                if self.mask_losses.requires_grad:
+                    roots.append(self.mask_losses)
+                    root_grads.append(self._mask_grad)
+                self.n_roi_rows = int(logits.shape[0])
+            elif gm is None or gm.shape != logits.shape:
                 if self.with_rpn:
                     # the proposals -- and with them the number of cropped points -- change from step to step: dM is a slice
                     # of one device-resident pool (drawing 2 M normals on the host per step would be timed as part of it)
@@ -357,7 +415,7 @@ class SceneStep:
                 else:
                     gm = self._gms[k] = torch.randn(logits.shape, generator=self._gen).to(self.device)
                 self.n_roi_rows = sum(g.shape[0] for g in self._gms.values())
-            if logits.requires_grad and logits.shape[0]:
+            if logits.requires_grad and logits.shape[0] and not self.mask_loss:
                 roots.append(logits)
                 root_grads.append(gm if scale == 1.0 else gm * scale)
             # (an empty crop -- no proposal caught a point: the mask branch contributes nothing on this rank)
@@ -453,6 +511,14 @@ class SceneStep:
         if self.rpn_loss:
             s += ("; the RPN trains on the reference's RPN loss (BCE-with-logits + smooth L1, sigma 2) against the synthetic "
                   "boxes: device anchor targets, batch-wide 0.35 / 0.15 sampling, max weight 1/8 (scn_rpnloss.hip)")
+        if self.mask_loss:
+            s += ("; the mask branch trains on the reference's mask loss: IoU of the proposals against the synthetic ground "
+                  "truth" + (f" (the first {self.n_gt} boxes per sample)" if self.n_gt else "") + ", TrainSelector(0.2, 0, "
+                  "(24, 0, True)) draws <= 24 proposals with IoU >= 0.2 per sample and appends every ground-truth box "
+                  "(one launch), BCE-with-logits of the instance's label column against its ellipsoid mask, mean over the "
+                  "boxes with points (scn_maskloss.hip)")
+        elif self.n_gt:
+            s += f"; ground truth: the first {self.n_gt} synthetic boxes per sample"
         if self.batches_per_step > 1:
             s += (f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
                   "voxels = all of them")
