@@ -283,9 +283,9 @@ def conv(X, W, b, rules, n_out):
     return _ConvFn.apply(X, W, b, rules, n_out)
 
 
-def batchnorm_relu_fwd(X, gamma, beta, running_mean, running_var, eps=1e-4, momentum=0.9,
-                       leak=0.0, training=True):
-    """A8.  momentum is the RETAIN fraction (SparseConvNet convention, SURVEY §4.1 caveat).
+def batchnorm_affine(X, gamma, beta, running_mean, running_var, eps=1e-4, momentum=0.9, training=True):
+    """The normalisation half of A8: (X - mean) / sqrt(var + eps) * gamma + beta, before the (leaky) ReLU.
+    momentum is the RETAIN fraction (SparseConvNet convention, SURVEY §4.1 caveat).
     The normalisation uses the biased batch variance (divide by N); the running_var update takes the UNBIASED
     estimate (divide by N - 1) -- [UPSTREAM-SCN] BatchNormalization forward as recalled, also torch.nn.BatchNorm's
     convention (the dense twin the reference pairs this layer with, module_factory.py:101-112)."""
@@ -297,7 +297,13 @@ def batchnorm_relu_fwd(X, gamma, beta, running_mean, running_var, eps=1e-4, mome
         running_var.mul_(momentum).add_(var.detach() * ((1 - momentum) * (n / (n - 1) if n > 1 else 1.0)))
     else:
         mean, var = running_mean, running_var
-    y = (X - mean) / torch.sqrt(var + eps) * gamma + beta
+    return (X - mean) / torch.sqrt(var + eps) * gamma + beta
+
+
+def batchnorm_relu_fwd(X, gamma, beta, running_mean, running_var, eps=1e-4, momentum=0.9,
+                       leak=0.0, training=True):
+    """A8: batchnorm_affine, then the (leaky) ReLU of the normalised pre-activation."""
+    y = batchnorm_affine(X, gamma, beta, running_mean, running_var, eps, momentum, training)
     return torch.where(y > 0, y, y * leak)
 
 
@@ -423,11 +429,24 @@ class OracleScene:
         return len(self.level_coords[level])
 
 
-def unet_param_shapes(cin, channels, identity_first=False, min_channels=0):
+def unet_param_shapes(cin, channels, identity_first=False, min_channels=0, batchnorm=False):
     """Ordered (name, shape) list for the A12 U-Net (SURVEY Appendix A.1 layer list).  identity_first: encoder level 0
     is the reference's FLD('I') (no layer; the mask head's internal U-Net, scannet_config/run.py:756-775).
     min_channels: decoder level l comes up max(channels[l], min_channels) wide (module_factory.py:789-804, 533-578):
-    Deconvolution(-> d), NetworkInNetwork(d + channels[l] -> d), units(d)."""
+    Deconvolution(-> d), NetworkInNetwork(d + channels[l] -> d), units(d).
+    batchnorm: every ReLU of a residual unit is a BatchNormReLU (`res{u}.bn{v}.weight` = gamma, `.bias` = beta, in front
+    of conv v) and the unit's SubM convolutions have no bias (sparse_rcnn_amd.unet.residual_block(c, batchnorm=True))."""
+    def res(prefix, c):
+        out = []
+        for u in range(2):
+            for v in range(2):
+                if batchnorm:
+                    out += [(f"{prefix}.res{u}.bn{v}.weight", (c,)), (f"{prefix}.res{u}.bn{v}.bias", (c,)),
+                            (f"{prefix}.res{u}.conv{v}.weight", (27, c, c))]
+                else:
+                    out += [(f"{prefix}.res{u}.conv{v}.weight", (27, c, c)), (f"{prefix}.res{u}.conv{v}.bias", (c,))]
+        return out
+
     shapes = []
     L = len(channels)
     for l, c in enumerate(channels):
@@ -437,27 +456,27 @@ def unet_param_shapes(cin, channels, identity_first=False, min_channels=0):
             shapes += [(f"enc{l}.in.weight", (1, cin, c)), (f"enc{l}.in.bias", (c,))]
         else:
             shapes += [(f"enc{l}.in.weight", (8, channels[l - 1], c)), (f"enc{l}.in.bias", (c,))]
-        for u in range(2):
-            for v in range(2):
-                shapes += [(f"enc{l}.res{u}.conv{v}.weight", (27, c, c)), (f"enc{l}.res{u}.conv{v}.bias", (c,))]
+        shapes += res(f"enc{l}", c)
     cup = channels[-1]
     for l in range(L - 2, -1, -1):
         c, d = channels[l], max(channels[l], min_channels)
         shapes += [(f"dec{l}.up.weight", (8, cup, d)), (f"dec{l}.up.bias", (d,))]
         shapes += [(f"dec{l}.nin.weight", (d + c, d)), (f"dec{l}.nin.bias", (d,))]
-        for u in range(2):
-            for v in range(2):
-                shapes += [(f"dec{l}.res{u}.conv{v}.weight", (27, d, d)), (f"dec{l}.res{u}.conv{v}.bias", (d,))]
+        shapes += res(f"dec{l}", d)
         cup = d
     return shapes
 
 
-def init_unet_params(cin, channels, seed=0, identity_first=False):
-    """N(0, sqrt(2/(Cin*k^3))) weights, small random biases so bias paths are exercised."""
+def init_unet_params(cin, channels, seed=0, identity_first=False, batchnorm=False):
+    """N(0, sqrt(2/(Cin*k^3))) weights, small random biases so bias paths are exercised; batch-norm gamma
+    1 + N(0, 0.1), beta N(0, 0.05) (away from the identity so that both enter every gradient)."""
     g = torch.Generator().manual_seed(seed)
     params = {}
-    for name, shape in unet_param_shapes(cin, channels, identity_first):
-        if name.endswith("weight"):
+    for name, shape in unet_param_shapes(cin, channels, identity_first, batchnorm=batchnorm):
+        if ".bn" in name:
+            params[name] = (1.0 + 0.1 * torch.randn(shape, generator=g)) if name.endswith("weight") \
+                else 0.05 * torch.randn(shape, generator=g)
+        elif name.endswith("weight"):
             fan = shape[-2] * (shape[0] if len(shape) == 3 else 1)
             params[name] = torch.randn(shape, generator=g) * (2.0 / fan) ** 0.5
         else:
@@ -484,7 +503,8 @@ class FrozenReLU:
 
 
 def unet_forward(scene: OracleScene, feats_pts: torch.Tensor, params: dict, channels, identity_first=False,
-                 storage=None, tile_weights=None, split_nin=False, record=None, relu=None, interims=None):
+                 storage=None, tile_weights=None, split_nin=False, record=None, relu=None, interims=None,
+                 batchnorm=False, bn_running=None, bn_training=True):
     """A12: encoder level = {SubM1 | Conv2s2} + 2x[x + SubM3(ReLU(SubM3(ReLU(x))))];
     decoder level = ReLU -> Deconv2s2 -> Join(up, skip) -> NiN -> 2x residual
     (module_factory.py:127-183, 513-578; custom_container.py:70-83: cat((upsampled, skip))).
@@ -495,8 +515,14 @@ def unet_forward(scene: OracleScene, feats_pts: torch.Tensor, params: dict, chan
     keep fp32 weights).  split_nin: the NetworkInNetwork over a JoinTable as the HIP path evaluates it -- one GEMM per
     joined part, the first partial result stored (rounded) before the second is added.
     relu: replaces torch.relu (FrozenReLU: prescribed sign masks, consumed in the order the network applies its ReLUs).
-    interims: a list that receives the encoder outputs (differentiable: the RPN's inputs, model.py:293-298)."""
+    interims: a list that receives the encoder outputs (differentiable: the RPN's inputs, model.py:293-298).
+    batchnorm: sparse_rcnn_amd.unet.residual_block(c, batchnorm=True) -- every ReLU of a residual unit is a BatchNormReLU
+    (`relu(batchnorm_affine(x))`, eps 1e-4, momentum 0.9 as scn.BatchNormReLU's defaults; a FrozenReLU then takes the sign
+    of the normalised pre-activation), the unit's convolutions have no bias.  bn_running: dict of the running statistics
+    (`<prefix>.res<u>.bn<v>.running_mean` / `.running_var`; missing entries start at 0 / 1), updated in place in training
+    mode (bn_training) and read in evaluation mode."""
     P = params
+    bn_running = {} if bn_running is None else bn_running
     relu = torch.relu if relu is None else relu        # relu: a FrozenReLU (prescribed masks), default the real one
     q = storage if storage is not None else (lambda t: t)
     wq = tile_weights if tile_weights is not None else (lambda t: t)
@@ -508,10 +534,20 @@ def unet_forward(scene: OracleScene, feats_pts: torch.Tensor, params: dict, chan
         rules = scene.subm_rules(level, 3)
         n = scene.n(level)
         for u in range(2):
+            if batchnorm:
+                y = q(conv(act(x, f"{prefix}.res{u}.bn0"), wq(P[f"{prefix}.res{u}.conv0.weight"]), None, rules, n))
+                y = conv(act(y, f"{prefix}.res{u}.bn1"), wq(P[f"{prefix}.res{u}.conv1.weight"]), None, rules, n)
+                x = q(x + y)
+                continue
             y = q(conv(relu(x), wq(P[f"{prefix}.res{u}.conv0.weight"]), P[f"{prefix}.res{u}.conv0.bias"], rules, n))
             y = conv(relu(y), wq(P[f"{prefix}.res{u}.conv1.weight"]), P[f"{prefix}.res{u}.conv1.bias"], rules, n)
             x = q(x + y)
         return x
+
+    def act(x, name):
+        rm = bn_running.setdefault(f"{name}.running_mean", torch.zeros(x.shape[1], dtype=x.dtype))
+        rv = bn_running.setdefault(f"{name}.running_var", torch.ones(x.shape[1], dtype=x.dtype))
+        return relu(batchnorm_affine(x, P[f"{name}.weight"], P[f"{name}.bias"], rm, rv, 1e-4, 0.9, bn_training))
 
     for l in range(L):
         if l == 0 and identity_first:

@@ -1017,6 +1017,11 @@ class BatchNormReLUFunction(torch.autograd.Function):
         X = _f32(features)
         n, c = X.shape
         g, b = _f32(weight), _f32(bias)
+        if not (g.numel() == b.numel() == running_mean.numel() == running_var.numel() == c):
+            # a channel-padded slab (modules._ConvBase.pad_out_to) is wider than the layer: the kernels would normalise the
+            # pad columns with statistics and parameters read past the layer's, and the pad would stop being zero
+            raise ValueError(f"batch norm over a {c}-column slab with {g.numel()} planes: the slab must be exactly as wide "
+                             "as the layer (no channel padding)")
         scratch = torch.empty(lib.scn_bn_scratch_bytes(c), dtype=torch.uint8, device=X.device)
         group = _sync_group(sync) if training else None
         n_stat = n
@@ -1048,6 +1053,9 @@ class BatchNormReLUFunction(torch.autograd.Function):
         Y = torch.empty_like(X)
         L.check(lib.scn_bn_fwd(L.ptr(X), n, c, L.ptr(mean), L.ptr(var), eps, L.ptr(g), L.ptr(b), leak, L.ptr(Y),
                                L.stream()))
+        # the layer's ReLU decisions for RELU_RECORD: Y > 0 exactly where the normalised pre-activation the kernels compute
+        # (forward and backward alike: ((x - mean) * rsqrt(var + eps)) * gamma + beta) is > 0 -- leak * pre is never > 0
+        _rec_relu(Y)
         ctx.save_for_backward(X, g, b, mean, var)
         ctx.cfg = (eps, leak, training)
         ctx.sync = (group, n_stat)

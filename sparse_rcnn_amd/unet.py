@@ -112,6 +112,9 @@ class SparseUNet(nn.Module):
             self.phys0 = (c0 + 7) // 8 * 8
             d0 = self.decoder[-1]
             if self.out_channels == c0:                      # the whole level is padded
+                if batchnorm:
+                    raise ValueError(f"batch norm on a level-0 width of {c0}: that level runs on slabs zero-padded to "
+                                     f"{self.phys0} columns, and batch norm takes no padded slab")
                 self.out_phys = self.phys0
                 d0["up"][1].pad_out_to = self.phys0
                 d0["nin"].pad_out_to = self.phys0
@@ -357,13 +360,30 @@ class SparseUNet(nn.Module):
             self._res(out, f"dec{l}", d["units"])
         return out
 
+    def named_oracle_running_stats(self):
+        """{`<prefix>.res<u>.bn<v>.running_mean` / `.running_var`: buffer} of the batch-norm layers (batchnorm=True), named
+        as oracle.scn_oracle.unet_forward's `bn_running`."""
+        out = {}
+        units_of = [(f"enc{l}", level[1]) for l, level in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
+        units_of += [(f"dec{len(self.channels) - 2 - i}", d["units"]) for i, d in enumerate(self.decoder)]
+        for prefix, unit_seq in units_of:
+            for u, block in enumerate(unit_seq):
+                for v, bn in enumerate(m for m in block[0][1] if isinstance(m, M._BatchNorm)):
+                    out[f"{prefix}.res{u}.bn{v}.running_mean"] = bn.running_mean
+                    out[f"{prefix}.res{u}.bn{v}.running_var"] = bn.running_var
+        return out
+
     @staticmethod
     def _res(out, prefix, unit_seq):
         for u, block in enumerate(unit_seq):
             inner = block[0][1]
+            for v, bn in enumerate(m for m in inner if isinstance(m, M._BatchNorm)):
+                out[f"{prefix}.res{u}.bn{v}.weight"], out[f"{prefix}.res{u}.bn{v}.bias"] = bn.weight, bn.bias
             convs = [m for m in inner if isinstance(m, M.SubmanifoldConvolution)]
             for v, cv in enumerate(convs):
-                out[f"{prefix}.res{u}.conv{v}.weight"], out[f"{prefix}.res{u}.conv{v}.bias"] = cv.weight, cv.bias
+                out[f"{prefix}.res{u}.conv{v}.weight"] = cv.weight
+                if cv.bias is not None:                     # batchnorm=True: the unit's convolutions have no bias
+                    out[f"{prefix}.res{u}.conv{v}.bias"] = cv.bias
 
     def load_reference_state_dict(self, state_dict, prefix=None, strict=True):
         """Load a checkpoint written by the REFERENCE's FeatureExtractor (training.py:386-391 saves model.state_dict()):

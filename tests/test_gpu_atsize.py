@@ -395,6 +395,65 @@ def _oracle_cfg3_step(coords, feats, boxes, pb, pm, ch, grad_seed, dt=torch.floa
     return out, logits, grads, len(src)
 
 
+def test_cfg2_bn_step_vs_oracle_at_150k(gpu):
+    """The cfg2-bn step bench.py times (trainstep.SceneStep("cfg2-bn"): Backbone 32-64-128-256 with BatchNormReLU in place of
+    every ReLU of the residual units, their convolutions without bias; the layer-by-layer path) on the 150k-voxel scene,
+    against O.unet_forward(batchnorm=True) in float64.  Forward features within FEAT_TOL of the scale (the oracle's own
+    decisions); with the 28 BN-ReLU and 3 ReLU decisions of the HIP forward frozen into the oracle, every convolution,
+    gamma and beta gradient and the input gradient within FROZEN_L2_F32 relative L2; the batch statistics each layer folded
+    into its running statistics (momentum 0.9, started from zero) within FEAT_TOL."""
+    from sparse_rcnn_amd.trainstep import SceneStep
+    job = SceneStep("cfg2-bn", gpu, prefetch=False, seed=1, grad_seed=100, lr=0.0)
+    unet = job.model.backbone.unet
+    assert unet.training and unet._exec_plan() is False
+    g = torch.Generator().manual_seed(21)
+    with torch.no_grad():                    # gamma / beta away from (1, 0), biases away from zero
+        for k, p in unet.named_oracle_params().items():
+            if ".bn" in k:
+                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g) if k.endswith("weight")
+                        else 0.05 * torch.randn(p.shape, generator=g))
+            elif p.dim() == 1:
+                p.copy_(torch.randn(p.shape, generator=g) * 0.05)
+        running = unet.named_oracle_running_stats()
+        for t in running.values():           # the step's statistics land in them unmixed: r = 0.1 * (mean, f * var)
+            t.zero_()
+    with _record_relu_masks() as masks:
+        job.forward_backward()
+    torch.cuda.synchronize()
+    assert len(masks) == 28 + 3 and len(running) == 2 * 28
+    ch = list(job.channels)
+    shapes = dict(O.unet_param_shapes(7, ch, batchnorm=True))
+    pb = unet.named_oracle_params()
+    assert set(pb) == set(shapes) and not any(k.endswith(".bias") and ".conv" in k and ".res" in k for k in pb)
+    po = {k: p.detach().cpu().double().clone().view(shapes[k]).requires_grad_() for k, p in pb.items()}
+    fo = job.feats_cpu.double().clone().requires_grad_()
+    scene = O.OracleScene(job.coords_cpu.numpy())
+    with torch.no_grad():
+        plain = O.unet_forward(scene, fo.detach(), po, ch, batchnorm=True, bn_running={})
+    ran = {k: torch.zeros(t.shape, dtype=torch.float64) for k, t in running.items()}
+    exp = O.unet_forward(scene, fo, po, ch, relu=O.FrozenReLU(masks), batchnorm=True, bn_running=ran)
+    exp.backward(job._gys[0].cpu().double())
+    name = "cfg2_bn_step_150k"
+    e = _err(job.out.features, plain)
+    _record(name, "forward features", e, FEAT_TOL)
+    assert job.out.features.shape == (150_000, 32) and e["rel_to_scale"] <= FEAT_TOL, e
+    for k, p in list(pb.items()) + [("input features", job.fin)]:
+        ref = fo.grad if k == "input features" else po[k].grad.view_as(p)
+        _check_grad_frozen(name, "grad " + k, p.grad, ref, FROZEN_L2_F32)
+    worst = {}
+    for k in running:
+        if not k.endswith("running_mean"):
+            continue
+        base = k[:-len("running_mean")]
+        rv = ran[base + "running_var"]                          # 0.1 * f * var; the mean's error is measured in 0.1 std
+        dm = (running[k].cpu().double() - ran[k]).abs() / ((0.1 * rv).sqrt() + 1e-30)
+        dv = (running[base + "running_var"].cpu().double() - rv).abs() / (rv + 1e-30)
+        worst[base] = max(dm.max().item(), dv.max().item())
+    _record(name, "running statistics (worst of 28 layers)", dict(max_abs=max(worst.values()), scale=1.0,
+                                                                  rel_to_scale=max(worst.values()), rel_l2=0.0), FEAT_TOL)
+    assert max(worst.values()) <= FEAT_TOL, worst
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_cfg3_end_to_end_backbone_crop_mask_vs_oracle_at_150k(gpu, dtype):
     """BASELINE configs[2] as ONE chain at size: trainstep.SceneStep("cfg3") -- the step bench.py times --
