@@ -296,6 +296,24 @@ inline bool is_leaf(int op) {
     return op == SCN_OP_WGRAD_SUBM || op == SCN_OP_WGRAD2_SUBM || op == SCN_OP_WGRAD_DOWN || op == SCN_OP_WGRAD_UP ||
            op == SCN_OP_WGRAD_IDENT || op == SCN_OP_COLSUM;
 }
+
+// A weight gradient whose units run at the end of the pass (grouped) must read what it would have read in place: true when
+// an op after it writes a slab it reads (then it launches in place).  No pass the package builds does that -- the side-stream
+// fork above assumes the same -- but the op list is the caller's.
+bool overwritten_later(const scn_exec_op* ops, int n_ops, int i, void* const* bufs) {
+    const scn_exec_op& o = ops[i];
+    const int reads[4] = {o.x, o.y, o.x1, o.y1};
+    for (int j = i + 1; j < n_ops; ++j) {
+        if (is_leaf(ops[j].op)) continue;                // leaves write parameter gradients only
+        const int writes[2] = {ops[j].y, ops[j].y1};
+        for (int w : writes) {
+            if (w < 0) continue;
+            for (int r : reads)
+                if (r >= 0 && (r == w || (bufs[r] != nullptr && bufs[r] == bufs[w]))) return true;
+        }
+    }
+    return false;
+}
 }  // namespace
 
 extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn_exec_level* levels, int n_levels,
@@ -328,9 +346,15 @@ extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn
             defer = true;
         }
     }
+    // Grouped weight gradients: with deferred sums, the fp32 weight gradients' unit launches are recorded too and run at the
+    // end of the pass as grouped launches (one per pass for the package's plans), before the sums.  Same plans, units and
+    // sums: same bits.  SCN_EXEC_GROUP_WGRAD=0: each launches in place.  Not with the launch timing (it brackets ops).
+    const scn::SwitchVal group_sw = scn::sw(scn::SW_EXEC_GROUP_WGRAD);
+    const bool group = defer && !(group_sw.set && group_sw.i == 0) && !g_timing.on;
     Ctx c{levels, n_levels, bufs, params, grads, scratch, arrival, stream};
     Ctx cs{levels, n_levels, bufs, params, grads, side_scratch, arrival, side_stream};
     if (defer) SCN_REQUIRE(scn_wgrad_defer_begin() == SCN_OK);
+    if (group) SCN_REQUIRE(scn::wgrad_defer_group(true) == SCN_OK);
     bool side_used = false;
     for (int i = 0; i < n_ops; ++i) {
         int rc;
@@ -360,6 +384,10 @@ extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn
                 r.info[6] = child ? L.n : (L.prefix_host ? L.prefix_host[27] - L.prefix_host[0] : 0);
                 g_timing.recs.push_back(r);
             }
+        } else if (group && is_wgrad(ops[i].op) && overwritten_later(ops, n_ops, i, bufs)) {
+            (void)scn::wgrad_defer_group(false);
+            rc = run_op(c, ops[i], own[i] ? (char*)scratch + own[i] : nullptr);
+            (void)scn::wgrad_defer_group(true);
         } else {
             rc = run_op(c, ops[i], defer && own[i] ? (char*)scratch + own[i] : nullptr);
         }

@@ -106,6 +106,13 @@ __device__ __forceinline__ typename Frag<T>::type widen(const R& r) {
     return f;
 }
 
+// Rule range [p_lo, p_hi) of (virtual) offset ov = prob * n_real + o of a launch's plan
+__device__ __forceinline__ void wd_range(const DPlan& plan, int ov, int o, int prob, long long& p_lo, long long& p_hi) {
+    const long long p_shift = prob * plan.p_rules;                     // every problem walks the same rule list
+    p_lo = plan.rule_start[ov] - p_shift;
+    p_hi = plan.rule_start[ov + 1] - p_shift;
+}
+
 template <int TA, int TB, bool QUAD, bool EDGE, bool IDENT, bool HB = false>
 __global__ __launch_bounds__(256) void k_wgrad_direct(const float* __restrict__ X_0, int cin, const float* __restrict__ dY_0,
                                                       int cout, const int* __restrict__ in_rows,
@@ -113,320 +120,139 @@ __global__ __launch_bounds__(256) void k_wgrad_direct(const float* __restrict__ 
                                                       float* __restrict__ slabs, int relu_in,
                                                       float* __restrict__ db_slabs, unsigned db_mask, int cout_pad,
                                                       WdOps more) {
-    typedef typename Frag<TA>::type fa_t;
-    typedef typename Frag<TB>::type fb_t;
-    constexpr bool PACKED = HB && !EDGE;                         // bf16 rows kept packed in the ring
-    typedef typename RawFrag<TA, PACKED>::type ra_t;
-    typedef typename RawFrag<TB, PACKED>::type rb_t;
-    constexpr int ES = HB ? 2 : 4;                               // bytes per stored element
-    constexpr int WI = 16 * TA, WJ = 16 * TB;                   // wave block
-    constexpr int CBI = QUAD ? 2 * WI : WI, CBJ = QUAD ? 2 * WJ : WJ;
-    constexpr int NACC = TA * TB;
-    extern __shared__ __attribute__((aligned(16))) float red[];     // K mode: 4 partial blocks + 4 x 64 bias sums
+    const int unit = blockIdx.x, zb = blockIdx.z;
+#include "scn_wgrad_unit.inc"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if WD_TIMELINE
-    const long long wd_t0 = wall_clock64();
-#endif
-    const int i = lane & 15, kq = lane >> 4;
-    const int unit = blockIdx.x;
-    // offset of this unit: unit_start is non-decreasing, so o = #{o' : unit >= unit_start[o'+1]} -- one ballot instead
-    // of a serial scalar search (every workgroup pays its prologue; with ~1000 short workgroups it adds up)
-    const int ov = wd_offset_of(plan, unit, lane);                               // (virtual) offset of this unit
-    const int prob = ov / plan.n_real;                                            // which operand pair (scalar)
-    const int o = ov - prob * plan.n_real;
-    const float* X = prob ? (const float*)more.X[prob] : X_0;
-    const float* dY = prob ? (const float*)more.dY[prob] : dY_0;
-    const int s_unit = unit - plan.unit_start[ov];
-    const int bi = blockIdx.z / plan.nbj, bj = blockIdx.z % plan.nbj;
-    const int wi = QUAD ? (wave >> 1) : 0, wj = QUAD ? (wave & 1) : 0;
-    const int ci0 = bi * CBI + wi * WI, co0 = bj * CBJ + wj * WJ;       // first channel of the wave block
+// ---------------------------------------------------------------------------------------------------------------------------
+// Grouped weight gradients (scn_exec: a backward pass's leaves at its end, scn::wgrad_defer_group): the k_wgrad_direct
+// launches of a pass as ONE grid.  Each job keeps the plan, the slabs and the instantiation of its standalone launch; only
+// the grid changes: workgroup -> (job, channel block, unit) through a prefix table, then exactly the standalone unit code on
+// exactly the standalone unit.  The small leaves fill the slots the big ones leave idle in their last round, and a pass
+// pays one launch boundary instead of one per leaf.
+//
+// A job in the kernel arguments (the DPlan of a launch is 1.6 KB): the unit prefix of its virtual offsets and the rule
+// prefix of its REAL offsets.  The rule range of virtual offset prob * n_real + o is [prefix[o], prefix[o + 1]) -- the
+// standalone plan's rule_start[ov] - prob * p_rules (multi_problem_plan: problem p's rules sit p * P behind, prefix[0] = 0).
+// ---------------------------------------------------------------------------------------------------------------------------
+#define WG_MAX_JOBS 6           // jobs per grouped launch (kernel arguments: 3.4 KB, like k_wgradd_sum_many's)
+#define WG_MAXV 54              // virtual offsets of a job: two problems of 27 offsets
+#define WG_MAXR 27              // real offsets of a job
+struct GJob {
+    const void* X[2]; const void* dY[2];        // operand pairs of problems 0 and 1
+    const int* in_rows; const int* out_rows;
+    float* slabs; float* db_slabs;
+    long long per;
+    int cin, cout, relu_in, cout_pad, n_off, n_real, nbi, nbj, units, kind;
+    unsigned db_mask;
+    int unit_start[WG_MAXV + 1];
+    long long prefix[WG_MAXR + 1];
+};
+struct GroupJobs { int n; int block_start[WG_MAX_JOBS + 1]; GJob job[WG_MAX_JOBS]; };
 
-    const long long p_shift = prob * plan.p_rules;                     // every problem walks the same rule list
-    const long long p_lo = plan.rule_start[ov] - p_shift, p_hi = plan.rule_start[ov + 1] - p_shift;
-    const long long p0 = p_lo + (long long)s_unit * plan.per;
-    const long long p1 = p0 + plan.per < p_hi ? p0 + plan.per : p_hi;
-    // this wave's rule range [q0, q1): K mode = a quarter of the unit (multiple of 16 rules), QUAD = the whole unit
-    long long q0 = p0, q1 = p1;
-    if (!QUAD) {
-        const long long quarter = ((p1 - p0 + 63) / 64) * 16;
-        q0 = p0 + wave * quarter;
-        q1 = q0 + quarter < p1 ? q0 + quarter : p1;
-    }
-    // rules of this wave, relative to q0: nfull whole blocks of 16 (pipelined, unmasked) + one masked tail block
-    const int nrel = __builtin_amdgcn_readfirstlane(q1 > q0 ? (int)(q1 - q0) : 0);
-    const int nfull = nrel / 16;
-    const int* inq = IDENT ? nullptr : in_rows + q0;
-    const int* outq = IDENT ? nullptr : out_rows + q0;
-    const int lane_r = 4 * kq;
-    const int q0i = (int)q0;                                   // identity list: rule index == row index (< 2^31)
+__device__ __forceinline__ int wd_offset_of(const GJob& j, int unit, int lane) {          // n_off <= 54: one ballot
+    const bool lo = lane < j.n_off && unit >= j.unit_start[lane + 1];
+    return __builtin_amdgcn_readfirstlane(__popcll(__ballot(lo)));
+}
+__device__ __forceinline__ void wd_range(const GJob& j, int ov, int o, int prob, long long& p_lo, long long& p_hi) {
+    p_lo = j.prefix[o];
+    p_hi = j.prefix[o + 1];
+}
 
-    // channel offsets of this lane inside a row: T consecutive floats starting at ci0 + TA*i (resp. co0 + TB*i)
-    const int ca = ci0 + TA * i, cbn = co0 + TB * i;
-    bool a_ok[TA], b_ok[TB];
-#pragma unroll
-    for (int t = 0; t < TA; ++t) a_ok[t] = !EDGE || ca + t < cin;
-#pragma unroll
-    for (int t = 0; t < TB; ++t) b_ok[t] = !EDGE || cbn + t < cout;
-    const bool do_db = db_slabs != nullptr && ((db_mask >> o) & 1u) && bi == 0 && wi == 0;
+// instantiation of a k_wgrad_direct launch as one number (host and device)
+#define WD_KIND(TA_, TB_, Q_, E_, I_, H_) \
+    ((TA_) | ((TB_) << 3) | ((Q_) ? 1 << 6 : 0) | ((E_) ? 1 << 7 : 0) | ((I_) ? 1 << 8 : 0) | ((H_) ? 1 << 9 : 0))
 
-    f32x4 acc[TA][TB];
-#pragma unroll
-    for (int a = 0; a < TA; ++a)
-#pragma unroll
-        for (int b = 0; b < TB; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float dbacc[TB];
-#pragma unroll
-    for (int t = 0; t < TB; ++t) dbacc[t] = 0.f;
-
-    // A block = 16 rules = 4 MFMA steps; lane group kq owns rules qb + 4*kq + s, s = step.
-    // Three named register sets (0,1,2) rotate through: indices of block b+3.., rows of block b+2.., MFMAs of block b.
-    // The instruction budget matters as much as the latency: a 16x16x4 fp32 MFMA is 32 cycles = 8 VALU slots, and at
-    // TA = TB = 2 a block has only 16 of them.  So: the block offset of the index loads is SCALAR (saddr + lane offset +
-    // immediate, zero VALU), a row address is ONE v_mad_i64_i32 (row * stride + per-lane base), ReLU is one v_max
-    // against 0 or -inf, and rule masking exists only in the peeled tail block.  (First version: ~110 VALU per block,
-    // VALU-issue-bound at 1/3 of the MFMA rate.)
-    const char* xlane = (const char*)X + (long long)ca * ES;
-    const char* ylane = (const char*)dY + (long long)cbn * ES;
-    const int xstride = ES * cin, ystride = ES * cout;         // int: row * stride is one v_mad_i64_i32
-    const int relu_lo = (relu_in & 1) ? 0 : (int)0x80000000;
-    // EDGE with whole fragments (relu_in bit 1, set by the host when Cin % TA == 0, Cout % TB == 0 and rows are 16-byte
-    // aligned -- the reference's 48 / 80 / 112-channel layers on 64-wide blocks): a lane's T channels are all inside the
-    // layer or all outside, so the row piece is still ONE vector load, from a clamped lane offset, zeroed at use
-    const bool evec = EDGE && !HB && (relu_in & 2);
-    const char* xlane_e = (const char*)X + (long long)(a_ok[0] ? ca : 0) * ES;
-    const char* ylane_e = (const char*)dY + (long long)(b_ok[0] ? cbn : 0) * ES;
-    const int last_full = nfull > 0 ? (nfull - 1) * 16 : 0;        // prefetches past the end re-read the last whole block
-#define WD_IDX(IN, OUT, QB)                                                                          \
-    {                                                                                                \
-        const int qs_ = (QB) < last_full ? (QB) : last_full;           /* scalar */                  \
-        _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) {                                           \
-            IN[s_] = IDENT ? q0i + qs_ + lane_r + s_ : inq[qs_ + lane_r + s_];                       \
-            OUT[s_] = (IDENT || WD_EXP) ? q0i + qs_ + lane_r + s_ : outq[qs_ + lane_r + s_];         \
-        }                                                                                            \
-    }
-#define WD_ROWS(A, B, IN, OUT)                                                                       \
-    _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) {                                               \
-        if (EDGE) {                  /* element loads; channels past the end read channel 0 (zeroed at use) */ \
-            if constexpr (!HB) {                                                                     \
-                if (evec) {              /* whole fragments in or out: one vector load per row piece */ \
-                    A[s_] = *(const ra_t*)(xlane_e + (long long)IN[s_] * xstride);                   \
-                    B[s_] = *(const rb_t*)(ylane_e + (long long)OUT[s_] * ystride);                  \
-                    continue;                                                                        \
-                }                                                                                    \
-            }                                                                                        \
-            if (HB) {                                                                                \
-                const unsigned short* xr_ = (const unsigned short*)X + (long long)IN[s_] * cin;      \
-                const unsigned short* yr_ = (const unsigned short*)dY + (long long)OUT[s_] * cout;   \
-                _Pragma("unroll") for (int t_ = 0; t_ < TA; ++t_)                                    \
-                    A[s_][t_] = __uint_as_float((unsigned)xr_[a_ok[t_] ? ca + t_ : 0] << 16);       \
-                _Pragma("unroll") for (int t_ = 0; t_ < TB; ++t_)                                    \
-                    B[s_][t_] = __uint_as_float((unsigned)yr_[b_ok[t_] ? cbn + t_ : 0] << 16);       \
-            } else {                                                                                 \
-                const float* xr_ = X + (long long)IN[s_] * cin;                                      \
-                const float* yr_ = dY + (long long)OUT[s_] * cout;                                   \
-                _Pragma("unroll") for (int t_ = 0; t_ < TA; ++t_) A[s_][t_] = xr_[a_ok[t_] ? ca + t_ : 0]; \
-                _Pragma("unroll") for (int t_ = 0; t_ < TB; ++t_) B[s_][t_] = yr_[b_ok[t_] ? cbn + t_ : 0]; \
-            }                                                                                        \
-        } else if (WD_EXP == 1) {                                                                    \
-            A[s_] = *(const ra_t*)(xlane + (long long)IN[s_] * xstride);                             \
-            _Pragma("unroll") for (int t_ = 0; t_ < (int)(sizeof(rb_t) / 4); ++t_)                   \
-                ((float*)&B[s_])[t_] = __int_as_float(0x3f800000 | (OUT[s_] & 0xffff));              \
-        } else if (WD_EXP == 2) {                                                                    \
-            A[s_] = *(const ra_t*)(xlane + (long long)IN[s_] * xstride);                             \
-            B[s_] = *(const rb_t*)((const char*)red + (((OUT[s_] & 15) * 16 + i) * (int)sizeof(rb_t)));  \
-        } else {                                                                                     \
-            A[s_] = *(const ra_t*)(xlane + (long long)IN[s_] * xstride);                             \
-            B[s_] = *(const rb_t*)(ylane + (long long)OUT[s_] * ystride);                            \
-        }                                                                                            \
-    }
-    // MASK: rules at or past `nrel` contribute nothing (tail block only)
-#define WD_MFMA(A, B, QB, MASK)                                                                      \
-    _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) {                                               \
-        const bool v_ = !(MASK) || (QB) + lane_r + s_ < nrel;                                        \
-        fa_t a_ = widen<TA, PACKED>(A[s_]);                                                          \
-        fb_t b_ = widen<TB, PACKED>(B[s_]);                                                          \
-        _Pragma("unroll") for (int t_ = 0; t_ < TA; ++t_) {                                          \
-            /* ReLU as ONE integer max on the bit pattern (fmaxf costs a canonicalising v_max x,x more; inline asm \
-               hides the VALU->MFMA hazard from the compiler): negative floats are negative ints */  \
-            float x_ = __int_as_float(max(__float_as_int(a_[t_]), relu_lo));                         \
-            if ((MASK) || EDGE) x_ = (v_ && a_ok[t_]) ? x_ : 0.f;                                    \
-            a_[t_] = x_;                                                                             \
-        }                                                                                            \
-        if ((MASK) || EDGE) {                                                                        \
-            _Pragma("unroll") for (int t_ = 0; t_ < TB; ++t_) b_[t_] = (v_ && b_ok[t_]) ? b_[t_] : 0.f; \
-        }                                                                                            \
-        if (do_db) { _Pragma("unroll") for (int t_ = 0; t_ < TB; ++t_) dbacc[t_] += b_[t_]; }         \
-        _Pragma("unroll") for (int ta_ = 0; ta_ < TA; ++ta_)                                         \
-            _Pragma("unroll") for (int tb_ = 0; tb_ < TB; ++tb_)                                     \
-                acc[ta_][tb_] = MFMA16(a_[ta_], b_[tb_], acc[ta_][tb_]);                             \
-    }
-
-    int in0[4], out0[4], in1[4], out1[4], in2[4], out2[4];
-    ra_t a0[4], a1[4], a2[4];
-    rb_t b0[4], b1[4], b2[4];
-    // Ring depth: 3 sets (rows two blocks ahead) for the small wave blocks; 2 sets (one block ahead) at TA = TB = 4,
-    // where a block is 64 MFMAs = 2048 cycles and the third set would cost the second resident wave per SIMD
-    // (64 accumulators + 3 x 32 row registers + indices > 256 registers).
-    constexpr bool DEEP = WD_DEEP_ALL || TA * TB < 16;
-    if (DEEP && nfull > 0) {
-        // (the prologue's issue order is pinned too: the loop header's wait counts are the merge of both ways in)
-        WD_IDX(in0, out0, 0);
-        WD_IDX(in1, out1, 16);
-        __builtin_amdgcn_sched_barrier(0);
-        WD_IDX(in2, out2, 32);
-        __builtin_amdgcn_sched_barrier(0);
-        WD_ROWS(a0, b0, in0, out0);
-        WD_IDX(in0, out0, 48);
-        __builtin_amdgcn_sched_barrier(0);
-        WD_ROWS(a1, b1, in1, out1);
-        WD_IDX(in1, out1, 64);
-        // steady state, block b (set b%3 holds its rows): queue rows of b+2 (indices arrived), indices of b+5, multiply b.
-        // The scheduling barriers keep each phase's address arithmetic in its phase: hoisted to the loop top it made
-        // every iteration wait for the newest index loads (s_waitcnt vmcnt(0)) and serialised the pipeline.
-        int qb = 0, b = 0;
-        for (; b + 3 <= nfull; b += 3, qb += 48) {
-            __builtin_amdgcn_sched_barrier(0);
-            WD_ROWS(a2, b2, in2, out2);
-            WD_IDX(in2, out2, qb + 80);
-            WD_MFMA(a0, b0, qb, false);
-            __builtin_amdgcn_sched_barrier(0);
-            WD_ROWS(a0, b0, in0, out0);
-            WD_IDX(in0, out0, qb + 96);
-            WD_MFMA(a1, b1, qb + 16, false);
-            __builtin_amdgcn_sched_barrier(0);
-            WD_ROWS(a1, b1, in1, out1);
-            WD_IDX(in1, out1, qb + 112);
-            WD_MFMA(a2, b2, qb + 32, false);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // remainder: 0, 1 or 2 whole blocks; their rows are already queued (sets 0 and 1)
-        if (b < nfull) { WD_MFMA(a0, b0, qb, false); }
-        if (b + 1 < nfull) { WD_MFMA(a1, b1, qb + 16, false); }
-    }
-    if (!DEEP && nfull > 0) {
-        WD_IDX(in0, out0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        WD_IDX(in1, out1, 16);
-        __builtin_amdgcn_sched_barrier(0);
-        WD_ROWS(a0, b0, in0, out0);
-        WD_IDX(in0, out0, 32);
-        // block b: set b%2 holds its rows; queue rows of b+1, indices of b+3, multiply b
-        int qb = 0, b = 0;
-        for (; b + 2 <= nfull; b += 2, qb += 32) {
-            __builtin_amdgcn_sched_barrier(0);
-            WD_ROWS(a1, b1, in1, out1);
-            WD_IDX(in1, out1, qb + 48);
-            WD_MFMA(a0, b0, qb, false);
-            __builtin_amdgcn_sched_barrier(0);
-            WD_ROWS(a0, b0, in0, out0);
-            WD_IDX(in0, out0, qb + 64);
-            WD_MFMA(a1, b1, qb + 16, false);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (b < nfull) { WD_MFMA(a0, b0, qb, false); }
-    }
-    if (nrel > nfull * 16) {        // tail block: clamped indices, masked values, no pipelining (once per wave)
-        const int qt = nfull * 16;
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-            int r_ = qt + lane_r + s_;
-            r_ = r_ < nrel ? r_ : nrel - 1;
-            in2[s_] = IDENT ? q0i + r_ : inq[r_];
-            out2[s_] = IDENT ? q0i + r_ : outq[r_];
-        }
-        WD_ROWS(a2, b2, in2, out2);
-        WD_MFMA(a2, b2, qt, true);
-    }
-#undef WD_IDX
-#undef WD_ROWS
-#undef WD_MFMA
-
-#if WD_TIMELINE
-    const long long wd_t1 = wall_clock64();
-#endif
-    float* slab = slabs + ((long long)unit * (plan.nbi * plan.nbj) + blockIdx.z) * (CBI * CBJ);
-    float* dbr = red + (QUAD ? 0 : 4 * NACC * 4 * 64);                  // [4 waves][64 columns]
-
-    // ---- K mode: add the four waves' partial blocks in wave order.  Every wave stores its whole block to LDS
-    // ([wave][element][lane], conflict-free) and then OWNS a quarter of the elements: it adds the four copies of its
-    // quarter in wave order and writes those rows of the slab -- the epilogue is spread over the 4 waves and never holds
-    // more than one quarter in registers (a first version had wave 0 add everything: 200+ VGPRs, one wave per SIMD).
-    // acc[a][b][j] is row TA*(4kq+j)+a, column TB*i+b of the wave block.
-    if (!QUAD) {
-        float* mine = red + wave * (NACC * 4 * 64);
-#pragma unroll
-        for (int a = 0; a < TA; ++a)
-#pragma unroll
-            for (int b = 0; b < TB; ++b)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mine[((a * TB + b) * 4 + j) * 64 + lane] = acc[a][b][j];
-        __syncthreads();
-        // the 4 TA (a, j) pairs in order p = 4 a + j, TA consecutive ones per wave (TA = 4: a = wave; TA = 2: a = wave / 2,
-        // j = 2 (wave & 1) + jj -- the owners of rounds 1-2; TA = 3: three pairs that may straddle two a)
-#pragma unroll
-        for (int jj = 0; jj < TA; ++jj) {
-            const int p_own = wave * TA + jj;
-            const int a_own = p_own >> 2, jx = p_own & 3;
-            fb_t v;
-#pragma unroll
-            for (int b = 0; b < TB; ++b) {
-                const float* src = red + ((a_own * TB + b) * 4 + jx) * 64 + lane;
-                v[b] = ((src[0] + src[NACC * 4 * 64]) + src[2 * NACC * 4 * 64]) + src[3 * NACC * 4 * 64];
-            }
-            const int r = TA * (4 * kq + jx) + a_own;
-            *(fb_t*)(slab + r * CBJ + TB * i) = v;
+// VAR 4: the 2 x 2 K-mode forms only (the C = 32 levels, 4 workgroups per CU, 98 VGPRs); VAR 2: every fp32 form without
+// EDGE, held to 2 workgroups per CU -- what the 4 x 4 forms have alone -- by amdgpu_waves_per_eu (227 VGPRs, no spill; the
+// unconstrained union took 292 registers).  EDGE and bf16-row forms are wider (up to 290 registers) and launch on their own.
+template <int VAR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VAR, VAR))) void k_wgrad_group(GroupJobs g) {
+    int j = 0;
+    while (j + 1 < g.n && (int)blockIdx.x >= g.block_start[j + 1]) ++j;
+    const GJob& J = g.job[j];
+    const int local = (int)blockIdx.x - g.block_start[j];
+    const int zb = local / J.units, unit = local - zb * J.units;     // the standalone grid runs x (units) fastest
+    const float* __restrict__ X_0 = (const float*)J.X[0];
+    const float* __restrict__ dY_0 = (const float*)J.dY[0];
+    const int cin = J.cin, cout = J.cout, relu_in = J.relu_in, cout_pad = J.cout_pad;
+    const int* __restrict__ in_rows = J.in_rows;
+    const int* __restrict__ out_rows = J.out_rows;
+    float* __restrict__ slabs = J.slabs;
+    float* __restrict__ db_slabs = J.db_slabs;
+    const unsigned db_mask = J.db_mask;
+    const GJob& plan = J;
+    const GJob& more = J;
+    // the unit body of the standalone instantiation <TA, TB, QUAD, EDGE = false, IDENT, HB = false>
+#define WG_UNIT(TA_, TB_, Q_, I_) \
+    constexpr int TA = TA_, TB = TB_;  \
+    constexpr bool QUAD = Q_, EDGE = false, IDENT = I_, HB = false;
+    if constexpr (VAR == 4) {
+        switch (J.kind) {
+        case WD_KIND(2, 2, false, false, false, false): {
+            WG_UNIT(2, 2, false, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(2, 2, false, false, true, false): {
+            WG_UNIT(2, 2, false, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        default: break;
         }
     } else {
-#pragma unroll
-        for (int a = 0; a < TA; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = wi * WI + TA * (4 * kq + j) + a;
-                fb_t v;
-#pragma unroll
-                for (int b = 0; b < TB; ++b) v[b] = acc[a][b][j];
-                *(fb_t*)(slab + r * CBJ + wj * WJ + TB * i) = v;
-            }
-    }
-
-    // ---- bias gradient: lanes (i, kq) hold column sums of their own rules -> add the 4 kq groups, then the waves ------
-    if (db_slabs != nullptr && ((db_mask >> o) & 1u) && bi == 0) {
-#pragma unroll
-        for (int t = 0; t < TB; ++t) {
-            float v = dbacc[t];
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
-            dbacc[t] = v;
+        switch (J.kind) {
+        case WD_KIND(2, 2, false, false, false, false): {
+            WG_UNIT(2, 2, false, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(2, 2, false, false, true, false): {
+            WG_UNIT(2, 2, false, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(2, 4, false, false, false, false): {
+            WG_UNIT(2, 4, false, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(2, 4, false, false, true, false): {
+            WG_UNIT(2, 4, false, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(4, 2, false, false, false, false): {
+            WG_UNIT(4, 2, false, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(4, 2, false, false, true, false): {
+            WG_UNIT(4, 2, false, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(3, 3, false, false, false, false): {
+            WG_UNIT(3, 3, false, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(3, 3, false, false, true, false): {
+            WG_UNIT(3, 3, false, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(4, 4, false, false, false, false): {
+            WG_UNIT(4, 4, false, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(4, 4, false, false, true, false): {
+            WG_UNIT(4, 4, false, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(4, 4, true, false, false, false): {
+            WG_UNIT(4, 4, true, false)
+#include "scn_wgrad_unit.inc"
+        } break;
+        case WD_KIND(4, 4, true, false, true, false): {
+            WG_UNIT(4, 4, true, true)
+#include "scn_wgrad_unit.inc"
+        } break;
+        default: break;
         }
-        if (!QUAD) {
-            if (kq == 0) {
-#pragma unroll
-                for (int t = 0; t < TB; ++t) dbr[wave * 64 + TB * i + t] = dbacc[t];
-            }
-            __syncthreads();
-            if (wave == 0 && kq == 0) {
-#pragma unroll
-                for (int t = 0; t < TB; ++t) {
-                    const int c = TB * i + t;
-                    const float v = ((dbr[c] + dbr[64 + c]) + dbr[128 + c]) + dbr[192 + c];
-                    if (co0 + c < cout_pad) db_slabs[(long long)unit * cout_pad + co0 + c] = v;
-                }
-            }
-        } else if (wi == 0 && kq == 0) {
-#pragma unroll
-            for (int t = 0; t < TB; ++t)
-                if (cbn + t < cout_pad) db_slabs[(long long)unit * cout_pad + cbn + t] = dbacc[t];
-        }
     }
-#if WD_TIMELINE
-    if (lane == 0) {
-        const long long slot = (((long long)blockIdx.x + (long long)gridDim.x * blockIdx.z) * 4 + wave) & 65535;
-        wd_stamps[slot * 4 + 0] = wd_t0; wd_stamps[slot * 4 + 1] = wd_t1; wd_stamps[slot * 4 + 2] = wall_clock64();
-        wd_stamps[slot * 4 + 3] = nrel;
-    }
-#endif
+#undef WG_UNIT
 }
 
 
@@ -811,11 +637,150 @@ static int multi_problem_plan(int cin, int cout, const int64_t* prefix_host, int
     return rc;
 }
 
-// Deferred sums (scn_wgrad_defer_begin / _flush): per calling thread, the sums of the launches made in between.
+// One k_wgrad_direct launch, as wgrad_impl plans it: what the standalone launch passes, and what a grouped launch needs.
 namespace {
-struct DeferState { bool on = false; std::vector<SumArgs> jobs; std::vector<int> blocks; };
+struct WdLaunch {
+    DPlan pl;
+    int ta, tb;
+    bool quad, edge, ident, hb;
+    const float* X; const float* dY;
+    int cin, cout, relu_in, cout_pad, n_prob;
+    const int32_t* in_rows; const int32_t* out_rows;
+    float* slabs; float* db_slabs;
+    unsigned db_mask;
+    WdOps more;
+    int kind() const { return WD_KIND(ta, tb, quad, edge, ident, hb); }
+    int units() const { return pl.unit_start[pl.n_off]; }
+    int64_t workgroups() const { return (int64_t)units() * pl.nbi * pl.nbj; }
+    double wg_work() const { return (double)pl.per * pl.cbi * pl.cbj; }            // rules x block of one workgroup
+    size_t lds() const { return (quad ? 4 * 64 : 4 * ta * tb * 4 * 64 + 4 * 64) * sizeof(float); }
+};
+
+int launch_direct(const WdLaunch& r, scn_stream_t stream) {
+    const dim3 grid((unsigned)r.units(), 1, (unsigned)(r.pl.nbi * r.pl.nbj));
+    const bool ident = r.ident, edge = r.edge, hb = r.hb;
+#define LAUNCH_WD(TA_, TB_, Q_, E_, I_, H_)                                                                      \
+    do {                                                                                                         \
+        const size_t lds_ = ((Q_) ? 4 * 64 : 4 * (TA_) * (TB_) * 4 * 64 + 4 * 64) * sizeof(float);               \
+        static scn::DeviceOnce attr_set;                                                                            \
+        if (attr_set.needed()) {                                                                                         \
+            SCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_direct<TA_, TB_, Q_, E_, I_, H_>,                   \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                \
+            attr_set.done();                                                                                     \
+        }                                                                                                        \
+        hipLaunchKernelGGL((k_wgrad_direct<TA_, TB_, Q_, E_, I_, H_>), grid, dim3(256), lds_, S(stream), r.X, r.cin, \
+                           r.dY, r.cout, r.in_rows, r.out_rows, r.pl, r.slabs, r.relu_in, r.db_slabs, r.db_mask,  \
+                           r.cout_pad, r.more);                                                                  \
+    } while (0)
+#define PICK_I(TA_, TB_, Q_, E_, H_)                                                                             \
+    do { if (ident) LAUNCH_WD(TA_, TB_, Q_, E_, true, H_); else LAUNCH_WD(TA_, TB_, Q_, E_, false, H_); } while (0)
+#define PICK_EI(TA_, TB_, Q_)                                                                                    \
+    do {                                                                                                         \
+        if (hb) { if (edge) PICK_I(TA_, TB_, Q_, true, true); else PICK_I(TA_, TB_, Q_, false, true); }          \
+        else { if (edge) PICK_I(TA_, TB_, Q_, true, false); else PICK_I(TA_, TB_, Q_, false, false); }           \
+    } while (0)
+    if (r.quad) PICK_EI(4, 4, true);
+    else if (r.ta == 3) { if (ident) LAUNCH_WD(3, 3, false, false, true, false); else LAUNCH_WD(3, 3, false, false, false, false); }
+    else if (r.ta == 4 && r.tb == 4) PICK_EI(4, 4, false);
+    else if (r.ta == 4) PICK_EI(4, 2, false);
+    else if (r.tb == 4) PICK_EI(2, 4, false);
+    else PICK_EI(2, 2, false);
+#undef PICK_EI
+#undef PICK_I
+#undef LAUNCH_WD
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+// The grouped kernel a launch can join: 4 (k_wgrad_group<4>), 2 (k_wgrad_group<2>), 0: none (it launches on its own).
+int group_variant(const WdLaunch& r) {
+    if (r.hb || r.edge || r.n_prob > 2 || r.pl.n_off > WG_MAXV || r.pl.n_real > WG_MAXR) return 0;
+    return (r.ta == 2 && r.tb == 2 && !r.quad) ? 4 : 2;
+}
+
+// Deferred sums (scn_wgrad_defer_begin / _flush): per calling thread, the sums of the launches made in between -- and, with
+// grouping on (scn::wgrad_defer_group, set by scn_exec for a backward pass), their k_wgrad_direct launches as well.
+struct DeferState {
+    bool on = false, group = false;
+    std::vector<SumArgs> jobs; std::vector<int> blocks;
+    std::vector<WdLaunch> units;
+};
 thread_local DeferState g_defer;
+
+// The recorded unit launches of a pass.  The job with the most work picks the grouped kernel (its workgroups per CU are
+// what its standalone launch has: k_wgrad_group<4> for the 2 x 2 forms, <2> otherwise); the jobs that kernel can run join
+// it, largest workgroup first, then by workgroup count, so that the short units fill the last round of the long ones.  The
+// others -- and a group of one -- launch as they would have in place.
+int flush_units(scn_stream_t stream) {
+    std::vector<WdLaunch>& R = g_defer.units;
+    if (R.empty()) return SCN_OK;
+    size_t dom = 0;
+    for (size_t k = 1; k < R.size(); ++k)
+        if ((double)R[k].workgroups() * R[k].wg_work() > (double)R[dom].workgroups() * R[dom].wg_work()) dom = k;
+    const int var = group_variant(R[dom]);
+    std::vector<int> members;
+    for (size_t k = 0; k < R.size(); ++k) {
+        const int v = group_variant(R[k]);
+        if (var != 0 && v != 0 && v >= var) members.push_back((int)k);       // (<4> runs 2 x 2 only; <2> runs all of them)
+    }
+    if (members.size() < 2) members.clear();
+    std::vector<char> grouped(R.size(), 0);
+    for (int k : members) grouped[k] = 1;
+    for (size_t k = 0; k < R.size(); ++k)
+        if (!grouped[k]) {
+            const int rc = launch_direct(R[k], stream);
+            if (rc != SCN_OK) return rc;
+        }
+    std::stable_sort(members.begin(), members.end(), [&](int a, int b) {
+        if (R[a].wg_work() != R[b].wg_work()) return R[a].wg_work() > R[b].wg_work();
+        return R[a].workgroups() > R[b].workgroups();
+    });
+    for (size_t base = 0; base < members.size(); base += WG_MAX_JOBS) {
+        GroupJobs g;
+        memset(&g, 0, sizeof(g));
+        g.n = (int)(members.size() - base < WG_MAX_JOBS ? members.size() - base : WG_MAX_JOBS);
+        size_t lds = 0;
+        for (int q = 0; q < g.n; ++q) {
+            const WdLaunch& r = R[members[base + q]];
+            GJob& J = g.job[q];
+            for (int p = 0; p < 2; ++p) {
+                J.X[p] = p == 0 ? (const void*)r.X : (r.n_prob > 1 ? r.more.X[p] : nullptr);
+                J.dY[p] = p == 0 ? (const void*)r.dY : (r.n_prob > 1 ? r.more.dY[p] : nullptr);
+            }
+            J.in_rows = r.in_rows; J.out_rows = r.out_rows; J.slabs = r.slabs; J.db_slabs = r.db_slabs;
+            J.per = r.pl.per;
+            J.cin = r.cin; J.cout = r.cout; J.relu_in = r.relu_in; J.cout_pad = r.cout_pad;
+            J.n_off = r.pl.n_off; J.n_real = r.pl.n_real; J.nbi = r.pl.nbi; J.nbj = r.pl.nbj;
+            J.units = r.units(); J.kind = r.kind(); J.db_mask = r.db_mask;
+            for (int v = 0; v <= r.pl.n_off; ++v) J.unit_start[v] = r.pl.unit_start[v];
+            for (int o = 0; o <= r.pl.n_real; ++o) J.prefix[o] = r.pl.rule_start[o];   // = the real prefix (see GJob)
+            g.block_start[q + 1] = g.block_start[q] + (int)r.workgroups();
+            if (r.lds() > lds) lds = r.lds();
+        }
+        if (var == 4) {
+            hipLaunchKernelGGL(k_wgrad_group<4>, dim3(g.block_start[g.n]), dim3(256), lds, S(stream), g);
+        } else {
+            static scn::DeviceOnce attr_set;
+            if (attr_set.needed()) {
+                SCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_group<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            160 * 1024));
+                attr_set.done();
+            }
+            hipLaunchKernelGGL(k_wgrad_group<2>, dim3(g.block_start[g.n]), dim3(256), lds, S(stream), g);
+        }
+        SCN_LAUNCH_CHECK();
+    }
+    return SCN_OK;
+}
 }  // namespace
+
+namespace scn {
+int wgrad_defer_group(bool on) {
+    if (on && !g_defer.on) return SCN_EINVAL;
+    g_defer.group = on;
+    return SCN_OK;
+}
+}  // namespace scn
 
 static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const int32_t* in_rows,
                       const int32_t* out_rows, const int64_t* prefix_host, int n_off_real, float* dW, float* db,
@@ -860,6 +825,9 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
     const bool evec = edge && !hb && cin % sh.ta == 0 && cout % sh.tb == 0 && (all_ptrs & 15) == 0 &&
                       (cin * 4) % 16 == 0 && (cout * 4) % 16 == 0 && !scn::sw(scn::SW_WD_NO_EVEC).set;
     const int relu_in = ((flags & SCN_F_RELU_IN) ? 1 : 0) | (evec ? 2 : 0);
+    // sum of the units: V output channels per thread, G threads per element group so that ~>= 128k threads run
+    const int V = (cout % 4 == 0 && (((uintptr_t)dW | (uintptr_t)scratch) & 15) == 0) ? 4 : 1;
+    const bool deferred = g_defer.on && V == 4;  // the caller batches the sums of several launches (own scratch per launch)
     if (mfma16) {
         const int ta = tb_tiles(cin), tb = tb_tiles(cout);
 #define LAUNCH_WT(TA_, TB_, I_)                                                                                  \
@@ -878,40 +846,21 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
         else PICK_WT(4, 4);
 #undef PICK_WT
 #undef LAUNCH_WT
+        SCN_LAUNCH_CHECK();
     } else {
-#define LAUNCH_WD(TA_, TB_, Q_, E_, I_, H_)                                                                      \
-    do {                                                                                                         \
-        const size_t lds_ = ((Q_) ? 4 * 64 : 4 * (TA_) * (TB_) * 4 * 64 + 4 * 64) * sizeof(float);               \
-        static scn::DeviceOnce attr_set;                                                                            \
-        if (attr_set.needed()) {                                                                                         \
-            SCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_direct<TA_, TB_, Q_, E_, I_, H_>,                   \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                \
-            attr_set.done();                                                                                     \
-        }                                                                                                        \
-        hipLaunchKernelGGL((k_wgrad_direct<TA_, TB_, Q_, E_, I_, H_>), grid, dim3(256), lds_, S(stream), X, cin, \
-                           dY, cout, in_rows, out_rows, pl, (float*)scratch, relu_in, db_slabs, db_mask,         \
-                           cout_pad, more);                                                                      \
-    } while (0)
-#define PICK_I(TA_, TB_, Q_, E_, H_)                                                                             \
-    do { if (ident) LAUNCH_WD(TA_, TB_, Q_, E_, true, H_); else LAUNCH_WD(TA_, TB_, Q_, E_, false, H_); } while (0)
-#define PICK_EI(TA_, TB_, Q_)                                                                                    \
-    do {                                                                                                         \
-        if (hb) { if (edge) PICK_I(TA_, TB_, Q_, true, true); else PICK_I(TA_, TB_, Q_, false, true); }          \
-        else { if (edge) PICK_I(TA_, TB_, Q_, true, false); else PICK_I(TA_, TB_, Q_, false, false); }           \
-    } while (0)
-    if (sh.quad) PICK_EI(4, 4, true);
-    else if (sh.ta == 3) { if (ident) LAUNCH_WD(3, 3, false, false, true, false); else LAUNCH_WD(3, 3, false, false, false, false); }
-    else if (sh.ta == 4 && sh.tb == 4) PICK_EI(4, 4, false);
-    else if (sh.ta == 4) PICK_EI(4, 2, false);
-    else if (sh.tb == 4) PICK_EI(2, 4, false);
-    else PICK_EI(2, 2, false);
-#undef PICK_EI
-#undef PICK_I
-#undef LAUNCH_WD
+        WdLaunch r;
+        r.pl = pl;
+        r.ta = sh.ta; r.tb = sh.tb; r.quad = sh.quad; r.edge = edge; r.ident = ident; r.hb = hb;
+        if (sh.ta == 3) r.edge = false;          // (48-wide blocks: one instantiation, whole fragments by construction)
+        r.X = X; r.dY = dY; r.cin = cin; r.cout = cout; r.relu_in = relu_in; r.cout_pad = cout_pad; r.n_prob = n_prob;
+        r.in_rows = in_rows; r.out_rows = out_rows; r.slabs = (float*)scratch; r.db_slabs = db_slabs; r.db_mask = db_mask;
+        r.more = more;
+        if (deferred && g_defer.group) g_defer.units.push_back(r);        // launched by the flush, before the sums
+        else {
+            const int rc = launch_direct(r, stream);
+            if (rc != SCN_OK) return rc;
+        }
     }
-    SCN_LAUNCH_CHECK();
-    // sum of the units: V output channels per thread, G threads per element group so that ~>= 128k threads run
-    const int V = (cout % 4 == 0 && (((uintptr_t)dW | (uintptr_t)scratch) & 15) == 0) ? 4 : 1;
     const int64_t groups = (int64_t)n_off * cin * (cout / V);
     int G = 1;
     while (G < 16 && groups * G < 128 * 1024) G *= 2;
@@ -922,7 +871,7 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
     sa.cin = cin; sa.cout = cout; sa.cout_pad = cout_pad; sa.main_blocks = (int)cdiv(groups, 256 / G); sa.G = G;
     sa.db_mask = db_mask;
     const int blocks = sa.main_blocks + (db ? n_prob * cout : 0);
-    if (g_defer.on && V == 4) {                  // the caller batches the sums of several launches (own scratch per launch)
+    if (deferred) {
         g_defer.jobs.push_back(sa);
         g_defer.blocks.push_back(blocks);
         return SCN_OK;
@@ -935,16 +884,21 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
 
 extern "C" int scn_wgrad_defer_begin(void) {
     g_defer.on = true;                           // (a recorder left open by a failed pass is simply restarted)
+    g_defer.group = false;
     g_defer.jobs.clear();
     g_defer.blocks.clear();
+    g_defer.units.clear();
     return SCN_OK;
 }
 
 extern "C" int scn_wgrad_defer_flush(scn_stream_t stream) {
     SCN_REQUIRE(g_defer.on);
     g_defer.on = false;
+    g_defer.group = false;
+    int rc = flush_units(stream);                // the recorded unit launches first: the sums read their slabs
+    g_defer.units.clear();
     const size_t n = g_defer.jobs.size();
-    for (size_t base = 0; base < n; base += WD_SUM_MANY) {
+    for (size_t base = 0; rc == SCN_OK && base < n; base += WD_SUM_MANY) {
         SumJobs jobs;
         jobs.n = (int)(n - base < WD_SUM_MANY ? n - base : WD_SUM_MANY);
         jobs.block_start[0] = 0;
@@ -954,11 +908,12 @@ extern "C" int scn_wgrad_defer_flush(scn_stream_t stream) {
         }
         if (jobs.n == 1) hipLaunchKernelGGL(k_wgradd_sum<4>, dim3(jobs.block_start[1]), dim3(256), 0, S(stream), jobs.job[0]);
         else hipLaunchKernelGGL(k_wgradd_sum_many, dim3(jobs.block_start[jobs.n]), dim3(256), 0, S(stream), jobs);
-        SCN_LAUNCH_CHECK();
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = scn::fail(SCN_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
     g_defer.jobs.clear();
     g_defer.blocks.clear();
-    return SCN_OK;
+    return rc;
 }
 
 extern "C" int scn_wgrad_rules(const float* X, int cin, const float* dY, int cout, const int32_t* in_rows,
