@@ -65,7 +65,8 @@ extern "C" {
  *      additive within 5: + scn_rpn_targets, scn_rpn_sample_workspace_bytes / scn_rpn_sample_batchwise,
  *      scn_rpn_loss_scratch_bytes / scn_rpn_loss, scn_rpn_loss_scale (130 entry points);
  *      additive within 5: + scn_mask_overlap_draw, scn_mask_loss_scratch_bytes / scn_mask_loss, scn_mask_loss_bwd,
- *      scn_mask_pack (135 entry points) */
+ *      scn_mask_pack (135 entry points);
+ *      additive within 5: + scn_xent_scratch_bytes / scn_xent_fwd, scn_xent_bwd, scn_softmax_argmax (139 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -891,6 +892,36 @@ int scn_mask_loss_bwd(const float* grad_loss, const void* scratch, int64_t n_box
                       float* dlogits, scn_stream_t stream);
 int scn_mask_pack(const uint8_t* const* masks, const int64_t* n_gt, const int64_t* n_points, int batch, uint32_t* out_words,
                   scn_stream_t stream);
+
+/* ---- class and segmentation losses (ndsis/modules/loss.py ClassLoss and the segmentation loss: nn.CrossEntropyLoss(weight,
+ * ignore_index=-100, reduction='mean'); ndsis/modules/model.py ClassPredictor, SegmentationPredictor) ----
+ * Every call is graph-capturable: nothing is allocated, copied or waited for.  1 <= c <= 256, else SCN_EINVAL.
+ *
+ * scn_xent_fwd: logits fp32 [n][c] row-major, targets int64 [n], weights fp32 [c] or NULL (all 1).  A row is valid when its
+ * target is in 0 .. c-1 and differs from ignore_index.  A row whose target equals ignore_index is dropped, as torch does.  A
+ * row whose target is anything else outside 0 .. c-1 is dropped too and counted: *n_bad_targets (device int64, may be NULL) =
+ * the number of such rows of this call (torch raises a device assert there).
+ *   *loss = sum_valid w[t_i] (logsumexp(x_i) - x_i[t_i]) / sum_valid w[t_i]
+ * DEVIATION from torch: when the valid rows' weights sum to 0 -- no valid row at all, or n == 0 -- the loss is 0 and the
+ * gradient all zero, where torch returns NaN (0 / 0).  TrainSelector's fixed-capacity slots that drew nothing become ignored
+ * rows, so "rows, none valid" is this library's image of the reference's "no box selected", for which ClassLoss returns 0.
+ * The sums are in double: one partial per workgroup in a fixed order, then one finishing block (2 launches; 1 for n == 0
+ * and for n * lanes-per-row <= 2048, lanes-per-row = 1, 2, 4, 8 for c <= 32, 64, 128, 256: one block finishes itself).
+ * Reruns are bitwise identical.  scratch: scn_xent_scratch_bytes(n, c) bytes (-1: bad arguments), 8-byte aligned; it keeps
+ * the weight sum that scn_xent_bwd reads.
+ *
+ * scn_xent_bwd (1 launch): dlogits[i][j] = *grad_loss * w[t_i] * (softmax(x_i)[j] - [j == t_i]) / sum_valid w[t] for a valid
+ * row, exactly 0 for every other row.  The softmax is recomputed from the logits (nothing per row is kept); logits, targets,
+ * weights, ignore_index, n and c as given to scn_xent_fwd, scratch as it left it.
+ *
+ * scn_softmax_argmax (1 launch, none for n == 0): indices int64 [n] = the first index of the row's maximum, compared on the
+ * logits themselves (exact; rows without NaN); probabilities fp32 [n][c] = softmax of the row, or NULL. */
+int64_t scn_xent_scratch_bytes(int64_t n, int c);
+int scn_xent_fwd(const float* logits, int64_t n, int c, const int64_t* targets, const float* weights, int64_t ignore_index,
+                 void* scratch, float* loss, int64_t* n_bad_targets, scn_stream_t stream);
+int scn_xent_bwd(const float* grad_loss, const float* logits, int64_t n, int c, const int64_t* targets, const float* weights,
+                 int64_t ignore_index, const void* scratch, float* dlogits, scn_stream_t stream);
+int scn_softmax_argmax(const float* logits, int64_t n, int c, float* probabilities, int64_t* indices, scn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,8 @@ from .modules import (AddTable, AveragePooling, BatchNormLeakyReLU, BatchNormReL
 from .tensor import SparseConvNetTensor                                    # noqa: F401
 from .custom_operations import SparseGlobalPool, split_batch               # noqa: F401  (device forms of the reference's own helpers)
 from . import optim                                                         # noqa: F401  (optim.Adam: the reference's optimizer)
-from . import loss                                                          # noqa: F401  (loss.RpnLoss, loss.MaskLoss: the reference's RPN and mask losses)
+from . import loss                                                          # noqa: F401  (loss.RpnLoss, loss.MaskLoss, loss.ClassLoss, loss.CrossEntropyLoss: the reference's losses)
+from . import classhead                                                     # noqa: F401  (classhead.ClassBranch, classhead.SegmentationHead)
 
 __all__ = [
     "Metadata", "SparseConvNetTensor", "ioLayers", "InputLayer", "OutputLayer", "Sequential", "ConcatTable",

@@ -156,6 +156,10 @@ _SIGS = {
                                 p, p, p, p]),
     "scn_mask_loss_bwd": (C.c_int, [p, p, i64, i64, i32, p, p, p]),
     "scn_mask_pack": (C.c_int, [C.POINTER(p), C.POINTER(i64), C.POINTER(i64), i32, p, p]),
+    "scn_xent_scratch_bytes": (i64, [i64, i32]),
+    "scn_xent_fwd": (C.c_int, [p, i64, i32, p, p, i64, p, p, p, p]),
+    "scn_xent_bwd": (C.c_int, [p, p, i64, i32, p, p, i64, p, p, p]),
+    "scn_softmax_argmax": (C.c_int, [p, i64, i32, p, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)

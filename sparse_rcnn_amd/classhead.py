@@ -1,0 +1,192 @@
+"""Graph builders for the reference's class branch and segmentation head.
+
+``ClassBranch``: the topology the reference's sparse ``ClassNetwork`` (ndsis/modules/model.py:470-569) has under
+scannet_config/run.py:633-732 (the `sparse and not class_output_anchor` arm), expressed with this package's modules:
+
+  feature map (C ch at `stride`, one row per active site of the coarsest RPN level)
+    -> input_conv_layer   : 'B' level, 32 ch, stride 1: SubM 1^3 C->32 + 1 residual unit              (run.py:659-669)
+    -> roi_getter         : SparseRoiCut(TensorToTensor, clip_boxes=True, resize_boxes=stride): the sites inside each
+                            box (scene units / stride, clipped to the grid), InputLayer mode 0, batch_size = #boxes
+    -> output_conv_layer  : Convolution 32->64 2^3/2 + unit, Convolution 64->128 2^3/2 + unit          (run.py:681-696)
+    -> vectorice_layer    : SparseGlobalPool(torch.mean): one row per box, zeros for a box without sites
+    -> linear_layer       : ReLU, Linear(128, 64), ReLU, Linear(64, num_classes)                       (run.py:723-728)
+
+``SegmentationHead``: the reference's sparse ``SegmentationNetwork`` (model.py:449-467): SubM 1^3 C->num_classes with
+bias, then the OutputLayer: one row of class scores per point.
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import modules as M
+from . import roi
+from .custom_operations import SparseGlobalPool
+from .ioLayers import OutputLayer
+from .unet import units
+
+
+def reference_key_map(n_output_levels=2, num_units=1, n_linear=2):
+    """state_dict key of the reference's ClassNetwork -> this package's parameter name (`ClassBranch.named_oracle_params`).
+    Checked against the key list of a reference ClassNetwork built on this package (tests/golden/dropin_class_network.json)."""
+    out = {}
+    for t in ("weight", "bias"):
+        out[f"input_conv_layer.0.0.0.{t}"] = f"in.{t}"
+        for u in range(num_units):
+            for v, idx in enumerate((1, 3)):                     # Sequential(ReLU, SubM, ReLU, SubM) inside ConcatTable[1]
+                out[f"input_conv_layer.0.1.{u}.0.1.{idx}.{t}"] = f"in.res{u}.conv{v}.{t}"
+        for l in range(n_output_levels):
+            out[f"output_conv_layer.{l}.0.0.{t}"] = f"down{l}.{t}"
+            for u in range(num_units):
+                for v, idx in enumerate((1, 3)):
+                    out[f"output_conv_layer.{l}.1.{u}.0.1.{idx}.{t}"] = f"down{l}.res{u}.conv{v}.{t}"
+        for i in range(n_linear):
+            out[f"linear_layer.{2 * i + 1}.{t}"] = f"lin{i}.{t}"      # ReLU, Linear, ReLU, Linear: indices 1, 3
+    return out
+
+
+def _load_mapped(own, kmap, state_dict, prefix, mine, strict):
+    missing, used = [], set()
+    with torch.no_grad():
+        for rk, name in kmap.items():
+            t = state_dict.get(prefix + rk)
+            if t is None:
+                missing.append(prefix + rk)
+                continue
+            if t.dim() == 4 and t.shape[1] == 1:                 # SparseConvNet's grouped layout [fv, 1, nIn, nOut]
+                t = t.squeeze(1)
+            p = own[name]
+            if tuple(t.shape) != tuple(p.shape):
+                raise ValueError(f"{prefix + rk}: checkpoint shape {tuple(t.shape)} != {tuple(p.shape)} ({name})")
+            p.copy_(t)
+            used.add(prefix + rk)
+    unused = [k for k in state_dict if k.startswith(prefix) and k[len(prefix):].startswith(mine) and k not in used]
+    if strict and (missing or unused):
+        raise KeyError(f"reference checkpoint mismatch: missing {missing[:4]}... unused {unused[:4]}...")
+    return missing, unused
+
+
+def _unit_convs(block):
+    return [m for m in block[0][1] if isinstance(m, M.SubmanifoldConvolution)]
+
+
+class ClassBranch(nn.Module):
+    """forward(feature_map, boxes) -> (class_scores [BB, num_classes] fp32, selection = (RoiSelection, boxes per sample,
+    sites per sample)).  feature_map: SparseConvNetTensor of `feature_channels` channels whose sites are `stride` scene units
+    apart; boxes: list (one per sample) of fp32 [n, 2, 3] (start, stop) boxes in scene units (training: TrainSelector's
+    forward boxes; evaluation: the kept proposals).  A box without any site pools to a zero row: its scores are the Linear
+    stack's bias response, finite, and it adds nothing to the convolutions' gradients.
+    The branch computes in fp32: a bf16-stored feature map is widened once on entry, and the branch's own layers keep fp32
+    rows whatever `set_feature_storage` says (the ROI batch is a few thousand rows)."""
+
+    def __init__(self, feature_channels, stride, input_channels=32, output_channels=(64, 128), linear_channels=(64,),
+                 num_classes=18, num_units=1):
+        super().__init__()
+        self.stride, self.num_units = int(stride), int(num_units)
+        self.input_conv_layer = M.Sequential(M.SubmanifoldConvolution(3, feature_channels, input_channels, 1, True),
+                                             units(input_channels, num_units))
+        self.roi_getter = roi.SparseRoiCut(roi.TensorToTensorFeatureExtractorCombiner(), clip_boxes=True,
+                                           resize_boxes=self.stride, dense_inside=False)
+        levels, c = [], input_channels
+        for co in output_channels:
+            levels.append(M.Sequential(M.Convolution(3, c, co, 2, 2, True), units(co, num_units)))
+            c = co
+        self.output_conv_layer = M.Sequential(*levels)
+        self.vectorice_layer = SparseGlobalPool(torch.mean)
+        layers = []
+        for co in tuple(linear_channels) + (num_classes,):
+            layers += [nn.ReLU(inplace=bool(layers)), nn.Linear(c, co)]
+            c = co
+        self.linear_layer = nn.Sequential(*layers)
+        self.pooled_channels = tuple(output_channels)[-1] if len(output_channels) else input_channels
+        self.num_classes = int(num_classes)
+
+    def forward(self, feature_map, boxes):
+        prev = M.set_feature_storage(torch.float32)
+        try:
+            if feature_map.features.dtype != torch.float32:
+                feature_map = M.CastFeatures(torch.float32)(feature_map)
+            augmented = self.input_conv_layer(feature_map)
+            box_features, selection = self.roi_getter(augmented, boxes)
+            n_boxes = sum(int(c) for c in selection[1])
+            if box_features is None:                             # no box holds a site: every pooled row is zero
+                pooled = augmented.features.new_zeros((n_boxes, self.pooled_channels))
+            else:
+                pooled = self.vectorice_layer(self.output_conv_layer(box_features))
+        finally:
+            M.set_feature_storage(prev)
+        return self._linear(pooled), selection
+
+    def _linear(self, x):
+        """The ReLU / Linear stack (module_factory.py:700-716) on the library's row GEMM, as MaskBranch._linear."""
+        from . import functional as F
+        for m in self.linear_layer:
+            if isinstance(m, nn.Linear):
+                x = F.NetworkInNetworkFunction.apply(x, m.weight.t(), m.bias)
+            else:
+                x = F.ReLUFunction.apply(x)
+        return x
+
+    def named_oracle_params(self):
+        out = {}
+        ic = self.input_conv_layer
+        out["in.weight"], out["in.bias"] = ic[0].weight, ic[0].bias
+        for u, block in enumerate(ic[1]):
+            for v, cv in enumerate(_unit_convs(block)):
+                out[f"in.res{u}.conv{v}.weight"], out[f"in.res{u}.conv{v}.bias"] = cv.weight, cv.bias
+        for l, level in enumerate(self.output_conv_layer):
+            out[f"down{l}.weight"], out[f"down{l}.bias"] = level[0].weight, level[0].bias
+            for u, block in enumerate(level[1]):
+                for v, cv in enumerate(_unit_convs(block)):
+                    out[f"down{l}.res{u}.conv{v}.weight"], out[f"down{l}.res{u}.conv{v}.bias"] = cv.weight, cv.bias
+        for i, m in enumerate(m for m in self.linear_layer if isinstance(m, nn.Linear)):
+            out[f"lin{i}.weight"], out[f"lin{i}.bias"] = m.weight, m.bias
+        return out
+
+    def reference_key_map(self):
+        n_lin = len([m for m in self.linear_layer if isinstance(m, nn.Linear)])
+        return reference_key_map(len(self.output_conv_layer), self.num_units, n_lin)
+
+    def load_reference_state_dict(self, state_dict, prefix=None, strict=True):
+        """Load the class-network part of a checkpoint written by the REFERENCE (the ClassNetwork sits under `class_network.`
+        in InstanceSegmentationNetwork, model.py:31-114).  prefix=None: detected from the first key ending in
+        'input_conv_layer.0.0.0.weight' that has a 'linear_layer.1.weight' sibling (the mask network has none).
+        -> (missing reference keys, unused checkpoint keys under the prefix)."""
+        if prefix is None:
+            tail = "input_conv_layer.0.0.0.weight"
+            cands = [k[:-len(tail)] for k in state_dict if k.endswith(tail)]
+            prefix = next((c for c in cands if c + "linear_layer.1.weight" in state_dict), cands[0] if cands else "")
+        return _load_mapped(self.named_oracle_params(), self.reference_key_map(), state_dict, prefix,
+                            ("input_conv_layer.", "output_conv_layer.", "linear_layer."), strict)
+
+
+class SegmentationHead(nn.Module):
+    """forward(SparseConvNetTensor of `channels` channels at full resolution) -> fp32 class scores [points, num_classes]
+    (bf16-stored features are widened on entry)."""
+
+    def __init__(self, channels, num_classes=20):
+        super().__init__()
+        self.channel_changer = M.SubmanifoldConvolution(3, channels, num_classes, 1, True)
+        self.output_layer = OutputLayer(3)
+        self.num_classes = int(num_classes)
+
+    def forward(self, x):
+        if x.features.dtype != torch.float32:                    # bf16 storage: 20 columns have no bf16 slab form; widen the input
+            x = M.CastFeatures(torch.float32)(x)
+        return self.output_layer(self.channel_changer(x))
+
+    def named_oracle_params(self):
+        return {"weight": self.channel_changer.weight, "bias": self.channel_changer.bias}
+
+    @staticmethod
+    def reference_key_map():
+        return {"channel_changer.weight": "weight", "channel_changer.bias": "bias"}
+
+    def load_reference_state_dict(self, state_dict, prefix=None, strict=True):
+        """The reference's SegmentationNetwork (`segmentation_network.` in InstanceSegmentationNetwork)."""
+        if prefix is None:
+            tail = "channel_changer.weight"
+            # (the U-Net decoder's SkipConnectionReuniters have channel_changers too: under `module_list`)
+            prefix = next((k[:-len(tail)] for k in state_dict if k.endswith(tail) and "module_list" not in k), "")
+        return _load_mapped(self.named_oracle_params(), self.reference_key_map(), state_dict, prefix,
+                            ("channel_changer.",), strict)

@@ -607,3 +607,206 @@ class MaskLoss(nn.Module):
         for n in splits:
             pt_offs.append(pt_offs[-1] + n)
         return _MaskLossFunction.apply(scores, sel.src_row, sel.box_of, assoc, box_offs, labels, gt_offs, gt_mask, pt_offs, cw)
+
+
+# ---- class and segmentation losses --------------------------------------------------------------------------------------
+# The reference's class path (ndsis/modules/model.py LossFilter / ClassLossSelector :1017-1077, ClassPredictor :785-793,
+# SegmentationPredictor :885-893; ndsis/modules/loss.py ClassLoss :255-268 and the segmentation loss :94-97, both
+# nn.CrossEntropyLoss(weight, ignore_index=-100, reduction='mean')) on the device (csrc/scn_xent.hip):
+#
+#     class_scores [BB, C], gt_association  --ClassLossSelector-->  labels (one gather per sample, -100: dropped)
+#     --ClassLoss / CrossEntropyLoss-->  0-dim loss (scn_xent_fwd: 2 launches; backward scn_xent_bwd: 1 launch)
+#
+# Nothing waits on the host: rows are never compacted, a dropped row carries the target `ignore_index` instead.
+
+__all__ += ["CrossEntropyLoss", "ClassLoss", "LossFilter", "ClassLossSelector", "ClassPredictor", "SegmentationPredictor",
+            "softmax_argmax"]
+
+MAX_CLASSES = 256                          # csrc/scn_xent.hip kMaxClasses
+
+
+def _check_logits(logits, name):
+    logits = _device_f32(logits, name)
+    if logits.dim() != 2:
+        raise ValueError(f"{name}: [n, c] required, got {tuple(logits.shape)}")
+    if not 1 <= logits.shape[1] <= MAX_CLASSES:
+        raise L.ScnError(f"{name}: 1 to {MAX_CLASSES} classes required, got {logits.shape[1]}")
+    return logits
+
+
+class _XentFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, weight, ignore_index, owner):
+        n, c = logits.shape
+        lib = L.lib()
+        # one allocation, kept for backward: [n_bad_targets int64][loss fp32, pad][scratch]
+        buf = torch.empty(2 + (lib.scn_xent_scratch_bytes(n, c) + 7) // 8, dtype=torch.int64, device=logits.device)
+        base = buf.data_ptr()
+        L.check(lib.scn_xent_fwd(logits.data_ptr(), n, c, targets.data_ptr(), L.ptr(weight), ignore_index, base + 16,
+                                 base + 8, base, L.stream()))
+        owner.n_bad_targets = buf[0]
+        ctx.save_for_backward(logits, targets, buf)
+        ctx.weight, ctx.ignore_index = weight, ignore_index
+        return buf[1:2].view(torch.float32)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, targets, buf = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        n, c = logits.shape
+        d = torch.empty_like(logits)
+        gg = g if (g.dtype == torch.float32 and g.is_contiguous()) else g.float().contiguous()
+        L.check(L.lib().scn_xent_bwd(gg.data_ptr(), logits.data_ptr(), n, c, targets.data_ptr(), L.ptr(ctx.weight),
+                                     ctx.ignore_index, buf.data_ptr() + 16, d.data_ptr(), L.stream()))
+        return (d,) + (None,) * 4
+
+
+class CrossEntropyLoss(nn.Module):
+    """`nn.CrossEntropyLoss(weight, ignore_index, reduction='mean')` on the device: forward(logits [n, c] fp32, targets [n]
+    int64) -> 0-dim fp32 loss = sum_valid w[t] (logsumexp(x) - x[t]) / sum_valid w[t], with autograd to the logits.
+    1 <= c <= 256.  A row is valid when its target is in [0, c) and is not `ignore_index`.  A target outside [0, c) that is
+    not `ignore_index` (torch: a device assert) drops its row and is counted in `n_bad_targets` (int64 0-dim device tensor,
+    the count of the last call).  Without any valid row the loss and the gradient are 0 (torch: NaN): this library's padded
+    selector slots make "rows, none valid" its image of the reference's "no box selected", for which ClassLoss returns 0.
+    Sums in double in a fixed order: reruns are bitwise identical.  Nothing waits on the host."""
+
+    def __init__(self, weight=None, ignore_index=-100):
+        super().__init__()
+        self.weight = None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().contiguous()
+        self.ignore_index = int(ignore_index)
+        self.n_bad_targets = None
+
+    def forward(self, logits, targets):
+        logits = _check_logits(logits, "logits")
+        n, c = logits.shape
+        if not torch.is_tensor(targets) or targets.dtype != torch.int64 or targets.shape != (n,):
+            raise ValueError(f"targets: int64 [{n}] required")
+        if targets.device != logits.device:
+            raise L.ScnError(f"targets are on {targets.device}, the logits on {logits.device}")
+        w = self.weight
+        if w is not None:
+            if w.numel() != c:
+                raise ValueError(f"weight: {c} entries (one per class) required, got {w.numel()}")
+            if w.device != logits.device:
+                w = self.weight = w.to(logits.device)
+        return _XentFunction.apply(logits, targets.contiguous(), w, self.ignore_index, self)    # (sets self.n_bad_targets)
+
+
+class ClassLoss(nn.Module):
+    """`ClassLoss(class_weights)` (loss.py:255-268): forward(class_output list of [n_s, C], class_target list of [n_s]) ->
+    CrossEntropyLoss(class_weights, ignore_index=-100) over the concatenation; 0 without any row."""
+
+    def __init__(self, class_weights=None):
+        super().__init__()
+        self.loss = CrossEntropyLoss(weight=class_weights, ignore_index=-100)
+
+    @property
+    def n_bad_targets(self):
+        return self.loss.n_bad_targets
+
+    def forward(self, class_output, class_target):
+        class_output, class_target = list(class_output), list(class_target)
+        if not class_output:
+            raise ValueError("class_output: at least one sample required")
+        out = class_output[0] if len(class_output) == 1 else torch.cat(class_output, 0)
+        tgt = class_target[0] if len(class_target) == 1 else torch.cat(class_target, 0)
+        return self.loss(out, tgt)
+
+
+class LossFilter(nn.Module):
+    """`LossFilter(positive_threshold, negative_threshold=0)` (model.py:1017-1032): forward(max_overlap [P], argmax [P]) ->
+    (keep bool [P], gt_association int64 [P]).  keep = overlap >= positive_threshold, or < negative_threshold (then the
+    association is -1).  The reference returns the association of the kept rows only; here it keeps the proposals' length
+    (no count reaches the host) and the caller gives a dropped row the target `ignore_index`."""
+
+    def __init__(self, positive_threshold, negative_threshold=0):
+        super().__init__()
+        self.positive_threshold = positive_threshold
+        self.negative_threshold = negative_threshold
+
+    def forward(self, max_overlap, argmax_overlap):
+        keep = max_overlap >= self.positive_threshold
+        assoc = argmax_overlap
+        if self.negative_threshold:
+            negative = max_overlap < self.negative_threshold
+            keep = keep | negative
+            assoc = torch.where(negative, torch.full_like(assoc, -1), assoc)
+        return keep, assoc
+
+
+class ClassLossSelector(nn.Module):
+    """`ClassLossSelector(positive_threshold, negative_threshold=0, negative_label=-100)` (model.py:1035-1077):
+    forward(class_scores [BB, C], selection, descriptions or None, overlap descriptions, gt_labels_list) ->
+    (class scores per sample, labels per sample).  With selection descriptions (training) the labels are
+    pad(gt_labels, negative_label)[gt_association]; without (the loss over all proposals) the association is LossFilter's.
+    Kept rows are NOT compacted: a row the reference would drop keeps its place with the label -100, which ClassLoss
+    ignores -- the loss and the gradients are the reference's, and the returned lists have the proposals' length."""
+
+    IGNORE = -100
+
+    def __init__(self, positive_threshold, negative_threshold=0, negative_label=-100):
+        super().__init__()
+        self.loss_filter = LossFilter(positive_threshold, negative_threshold)
+        self.negative_label = negative_label
+
+    def single_sample_selection(self, gt_association, gt_labels):
+        padded = nn.functional.pad(gt_labels, (0, 1), value=self.negative_label)
+        # -1 reads the pad.  (OverlapCalculator gives argmax 0 to a sample without ground truth, whose overlap 0 is never
+        # positive; the clamp keeps that gather, and any other stray association, in bounds without a device assert)
+        return padded[gt_association.clamp(-1, gt_labels.shape[0] - 1)]
+
+    def forward(self, class_scores, selection, class_selector_description_list, pred_gt_max_argmax_tuple_list,
+                gt_labels_list):
+        _, box_sample_count, *_ = selection
+        box_sample_count = [int(c) for c in box_sample_count]
+        scores = torch.split(class_scores, box_sample_count)
+        gt_labels_list = list(gt_labels_list)
+        if class_selector_description_list is None:
+            labels = []
+            for (_, _, mx, am), gl in zip(pred_gt_max_argmax_tuple_list, gt_labels_list):
+                keep, assoc = self.loss_filter(mx, am)
+                lab = self.single_sample_selection(assoc, gl)
+                labels.append(torch.where(keep, lab, torch.full_like(lab, self.IGNORE)))
+        else:
+            labels = [self.single_sample_selection(d.gt_association if hasattr(d, "gt_association") else d[3], gl)
+                      for d, gl in zip(class_selector_description_list, gt_labels_list)]
+        for s, (sc, lab) in enumerate(zip(scores, labels)):
+            if sc.shape[0] != lab.shape[0]:
+                raise ValueError(f"sample {s}: {sc.shape[0]} class scores and {lab.shape[0]} labels")
+        return list(scores), labels
+
+
+def softmax_argmax(logits, probabilities=True):
+    """logits [n, c] fp32 -> (indices int64 [n]: the first index of the row's maximum, taken on the logits;
+    softmax probabilities fp32 [n, c] or None).  One launch (scn_softmax_argmax); none for n == 0."""
+    logits = _check_logits(logits.detach(), "logits")
+    n, c = logits.shape
+    idx = torch.empty(n, dtype=torch.int64, device=logits.device)
+    prob = torch.empty_like(logits) if probabilities else None
+    if n:
+        L.check(L.lib().scn_softmax_argmax(L.ptr(logits), n, c, L.ptr(prob), L.ptr(idx), L.stream()))
+    return idx, prob
+
+
+class ClassPredictor(nn.Module):
+    """`ClassPredictor()` (model.py:785-793): forward(class_predictions [BB, C], selection) -> (class indices per sample,
+    class probabilities per sample, class indices [BB])."""
+
+    def forward(self, class_predictions, selection):
+        _, box_sample_count, *_ = selection
+        counts = [int(c) for c in box_sample_count]
+        idx, prob = softmax_argmax(class_predictions)
+        return torch.split(idx, counts), torch.split(prob, counts), idx
+
+
+class SegmentationPredictor(nn.Module):
+    """`SegmentationPredictor(sparse=True)` (model.py:885-893): forward(scores [N, C]) -> (class [N], probabilities [N, C])."""
+
+    def __init__(self, sparse=True):
+        super().__init__()
+        if not sparse:
+            raise ValueError("SegmentationPredictor: the dense layout (classes first) is not provided")
+
+    def forward(self, tensor):
+        return softmax_argmax(tensor)

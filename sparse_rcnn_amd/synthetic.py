@@ -154,3 +154,20 @@ def make_instances(coords, boxes, n_classes=18, seed=5):
             m[i] = inside & ((((centre - ctr[i]) / r) ** 2).sum(1) <= 1.0)
         masks.append(torch.from_numpy(m))
     return labels, masks
+
+
+def make_segmentation(labels, masks, offset=2):
+    """Per-point semantic labels of a scene from its `make_instances` output: list (one per sample) of int64 [N_s] CPU
+    tensors, `offset + label` of the lowest-numbered instance that holds the point and -100 (the reference's
+    `background_label`, scannet_config/run.py:401: ignored by the segmentation loss) where none does."""
+    out = []
+    for lab, m in zip(labels, masks):
+        lab = torch.as_tensor(lab, dtype=torch.int64)
+        m = torch.as_tensor(m, dtype=torch.bool)
+        seg = torch.full((m.shape[1],), -100, dtype=torch.int64)
+        if m.shape[0]:
+            first = torch.argmax(m.to(torch.uint8), dim=0)       # the first True of the column (0 if none)
+            held = m.any(0)
+            seg[held] = offset + lab[first[held]]
+        out.append(seg)
+    return out

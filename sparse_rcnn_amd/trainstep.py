@@ -32,7 +32,7 @@ import torch
 from . import _lib as L
 from .dp import FlatParams, broadcast_params
 from .maskhead import MaskBranch
-from .synthetic import make_batch, make_boxes, make_instances
+from .synthetic import make_batch, make_boxes, make_instances, make_segmentation
 from .unet import Backbone
 
 REF_PLAN = (32, 48, 64, 80, 96, 112)      # the reference's own sparse U-Net plan, `arange * 16 + 32` (scannet_config/run.py:539-549,587-591)
@@ -81,9 +81,14 @@ def _backward(roots, grads):
 class SparseStepModel(torch.nn.Module):
     """Backbone (+ mask branch for cfg3) as one module, so that one flat parameter buffer covers the step."""
 
-    def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False):
+    def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False, with_class=False,
+                 with_segmentation=False):
         """with_rpn: False | "stand-in" (cfg3-rpn: one anchor level, 2 x 32 stack) | "reference" (ref-crop-rpn: the reference's two
-        anchor levels with 5 x 128 / 5 x 256 stacks, rpn.MultiLevelRpn)."""
+        anchor levels with 5 x 128 / 5 x 256 stacks, rpn.MultiLevelRpn).
+        with_class: the reference's class branch (classhead.ClassBranch) on the coarsest RPN level of the encoder -- the
+        reference's `class_output_index=-1` on a main network that ends at its last anchor level (run.py:581-584, 605-608).
+        with_segmentation: the reference's segmentation head (classhead.SegmentationHead, 20 classes) on the backbone output.
+        Both are constructed AFTER the other modules: under one seed the others start from the same values with or without."""
         super().__init__()
         self.backbone = Backbone(7, channels, batchnorm=batchnorm, bf16_blocks=storage)
         self.mask = MaskBranch(channels[0], 7, bf16_blocks=storage) if with_mask else None
@@ -103,6 +108,17 @@ class SparseStepModel(torch.nn.Module):
             self.rpn_levels = (len(channels) - 1,)
             self.rpn = DenseRpn(channels[-1], stride=2 ** (len(channels) - 1), autocast_bf16=bool(storage))
             self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:848-850 with ~64 proposals kept per scene
+        self.class_branch = self.segmentation = None
+        self.class_level = None
+        if with_class:
+            if self.rpn is None:
+                raise ValueError("with_class needs an RPN (the class branch reads its coarsest level)")
+            from .classhead import ClassBranch
+            self.class_level = self.rpn_levels[-1]
+            self.class_branch = ClassBranch(channels[self.class_level], 2 ** self.class_level)
+        if with_segmentation:
+            from .classhead import SegmentationHead
+            self.segmentation = SegmentationHead(channels[0], 20)
 
     def run_rpn(self, interims):
         lv = [interims[i] for i in self.rpn_levels]
@@ -112,7 +128,8 @@ class SparseStepModel(torch.nn.Module):
 class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
+                 class_loss=False, segmentation_loss=False):
         """rpn_loss (the `-rpn` workloads only): train the RPN on the reference's RPN loss (loss.RpnLoss with
         BatchwiseBboxTargetSelector(0.35, 0.15, 1/8), sigma 2; scannet_config/run.py:359-368,876-884) against the scene's
         synthetic boxes, in place of the fixed synthetic gradient on rpn_bbox / rpn_score.  Targets and draw are queued before
@@ -124,6 +141,18 @@ class SceneStep:
         column against its mask, synthetic.make_instances) is backpropagated with gradient 1 / batches_per_step.  This
         replaces both the seeded synthetic gradient on the mask logits and ref-crop-rpn's cut to the 24 best-scored
         proposals.  The loss stays on the device as `.mask_losses`.  Without it the mask branch gets the synthetic gradient.
+        class_loss (the `-rpn` workloads only): add the reference's class branch (classhead.ClassBranch on the coarsest RPN
+        level of the encoder) and train it on the reference's class loss (run.py:399,520-521,729-732): after the proposal
+        selection, loss.TrainSelector(0.1, 0, (32, 0, True)) draws up to 32 proposals per sample with IoU >= 0.1 -- from the
+        overlap descriptions the mask selector computed when both are on (model.py:170-183) -- and appends every ground-truth
+        box; the branch runs on those boxes, loss.ClassLossSelector + loss.ClassLoss give `.class_losses` (on the device),
+        back-propagated with 1 / batches_per_step.
+        segmentation_loss (the workloads with boxes: cfg3, cfg3-rpn, ref-crop-rpn): add the reference's segmentation head
+        (classhead.SegmentationHead, 20 classes) on the backbone output and train it on loss.CrossEntropyLoss against
+        synthetic.make_segmentation of the scene's instances.  Its gradient REPLACES the seeded N(0, 1) gradient on the
+        backbone output; the loss stays on the device as `.segmentation_losses`.
+        With several losses on, the roots are summed with weight 1: the reference's `Loss` as configured (multitask_loss=False,
+        every weight 1, loss.py:44-58, run.py:876-898).
         n_gt (the `-rpn` workloads): the ground-truth instances per sample both losses see are the first n_gt synthetic boxes
         (None: all of them; ref-crop-rpn has 256 per crop, which would put > 3000 boxes through the mask branch).
         optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
@@ -140,6 +169,11 @@ class SceneStep:
             raise ValueError("rpn_loss=True needs an RPN in the step (the -rpn workloads)")
         if mask_loss and not workload.endswith("-rpn"):
             raise ValueError("mask_loss=True needs an RPN in the step (the -rpn workloads)")
+        if class_loss and not workload.endswith("-rpn"):
+            raise ValueError("class_loss=True needs an RPN in the step (the -rpn workloads)")
+        if segmentation_loss and not nb:
+            raise ValueError("segmentation_loss=True needs a workload with boxes (cfg3, cfg3-rpn, ref-crop-rpn): the labels "
+                             "come from the scene's instances")
         if n_gt is not None and not workload.endswith("-rpn"):
             raise ValueError("n_gt applies to the ground truth of the -rpn workloads")
         if n_gt is not None and int(n_gt) < 1:
@@ -190,8 +224,12 @@ class SceneStep:
         # model.py:919-1014 draws by ground-truth overlap -- out of scope: here the 24 best-scored ones)
         self.mask_boxes = 24 if workload == "ref-crop-rpn" else None
         rpn_kind = "reference" if workload == "ref-crop-rpn" else ("stand-in" if self.with_rpn else False)
+        self.class_loss, self.segmentation_loss = bool(class_loss), bool(segmentation_loss)
+        if self.segmentation_loss and not self.n_boxes:
+            raise ValueError("segmentation_loss=True needs boxes (n_boxes > 0)")
         self.model = SparseStepModel(self.channels, bool(self.n_boxes), storage, rpn_kind, self.n_boxes,
-                                     batchnorm=workload.endswith("-bn")).to(self.device)
+                                     batchnorm=workload.endswith("-bn"), with_class=self.class_loss,
+                                     with_segmentation=self.segmentation_loss).to(self.device)
         if self.with_rpn:
             self._init_rpn()
         self.rpn_loss = bool(rpn_loss)
@@ -213,7 +251,22 @@ class SceneStep:
             self.mask_selector = TrainSelector(0.2, 0, (24, 0, True), seed=seed + 17)
             self.mask_criterion = MaskLoss(class_weights=None)
             self._mask_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
-            for k, sc in enumerate(self._scenes):      # instances built and packed once per scene
+        self.class_losses = self.segmentation_losses = None
+        self.class_out = self.segmentation_out = None
+        self.keep_class_grads = False          # (tests: retain the gradients that reach the class scores / segmentation logits)
+        if self.class_loss:
+            from .loss import ClassLoss, ClassLossSelector, TrainSelector
+            # run.py:399,520-521,729-732: positive_threshold 0.1, selection_tuple (32, 0, True); ClassLoss without weights
+            self.class_selector = TrainSelector(0.1, 0, (32, 0, True), seed=seed + 29)
+            self.class_loss_selector = ClassLossSelector(0.1)
+            self.class_criterion = ClassLoss(class_weights=None)
+            self._class_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
+        if self.segmentation_loss:
+            from .loss import CrossEntropyLoss
+            self.segmentation_criterion = CrossEntropyLoss(weight=None, ignore_index=-100)
+            self._seg_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
+        if self.mask_loss or self.class_loss or self.segmentation_loss:
+            for k, sc in enumerate(self._scenes):      # instances built (and packed, for the mask loss) once per scene
                 labels, masks = make_instances(sc["coords_cpu"], sc["gt_boxes"], n_classes=self.model.mask.classes,
                                                seed=seed + 1000 * k + 5)
                 flat = torch.cat(labels).to(self.device)
@@ -223,8 +276,11 @@ class SceneStep:
                     o += l.shape[0]
                 sc["gt_label"] = views
                 sc["gt_mask_cpu"] = masks
-                sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in masks])
+                if self.mask_loss:
+                    sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in masks])
                 sc["gt_dev"] = [b.float().to(self.device) for b in sc["gt_boxes"]]
+                if self.segmentation_loss:             # one label per point row, in the batch's row order (sample-major)
+                    sc["seg_target"] = torch.cat(make_segmentation(labels, masks)).to(self.device)
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
         self.adam = None
@@ -336,11 +392,26 @@ class SceneStep:
             rpn_prep = (ov, am, tg) + tuple(self.rpn_criterion.bbox_target_selector(ov))
         out = m.backbone(self.coords, fin, self.size, self.batch_size, metadata=md, after_encoder=hook)
         self._start_prefetch(k)      # (LATE_PREFETCH: the helper thread is started once this batch's forward kernels are queued)
-        gy = self._gys.get(k)
-        if gy is None or gy.shape != out.features.shape:
-            gy = self._gys[k] = torch.randn(out.features.shape, generator=self._gen).to(self.device)   # upstream grad dY ~ N(0,1)
-            self.n_active = sum(g.shape[0] for g in self._gys.values())
-        gys = gy if scale == 1.0 else gy * scale
+        if self.segmentation_loss:
+            # the reference's real gradient at the backbone output: the segmentation head's logits (fp32; bf16 storage widened)
+            # against the scene's per-point labels, in place of the seeded N(0, 1) direction
+            seg_logits = m.segmentation(out)
+            if seg_logits.dtype != torch.float32:
+                seg_logits = seg_logits.float()
+            if self.keep_class_grads:
+                seg_logits.retain_grad()
+            seg_target = self._scenes[k]["seg_target"]
+            self.segmentation_losses = self.segmentation_criterion(seg_logits, seg_target)
+            self.segmentation_out = (seg_logits, seg_target)
+            root0, gys = self.segmentation_losses, self._seg_grad
+            self.n_active = int(out.features.shape[0]) * self.batches_per_step
+        else:
+            gy = self._gys.get(k)
+            if gy is None or gy.shape != out.features.shape:
+                gy = self._gys[k] = torch.randn(out.features.shape, generator=self._gen).to(self.device)   # upstream grad dY ~ N(0,1)
+                self.n_active = sum(g.shape[0] for g in self._gys.values())
+            gys = gy if scale == 1.0 else gy * scale
+            root0 = out.features
         if self.weighting == "count":             # before backward: the bucketed path scales slices as it packs them
             import torch.distributed as dist
             self.flat.rank_weight = float(out.features.shape[0])
@@ -352,11 +423,11 @@ class SceneStep:
         if m.mask is None:
             if zero:
                 self.flat.zero_grad()
-            _backward([out.features], [gys])
+            _backward([root0], [gys])
             logits = None
         else:
             scene = (self.coords, fin, self.size, self.batch_size, self.splits)
-            boxes, roots, root_grads = self.boxes, [out.features], [gys]
+            boxes, roots, root_grads = self.boxes, [root0], [gys]
             if self.with_rpn:
                 # configs[2] as written (model.py:141-160): the proposals are this forward's -- dense heads on the coarsest
                 # encoder level, top-k + NMS on the device; the RPN losses' gradients arrive at rpn_bbox / rpn_score
@@ -365,12 +436,13 @@ class SceneStep:
                 rpn_bbox, rpn_score, anchors, sel_state = rpn_state["out"]
                 roi_score, boxes, roi_index = m.roi_selector.finish(sel_state)
                 self.rpn_out = (rpn_bbox, rpn_score, anchors, roi_score, boxes, roi_index)
-                descs = None
+                descs = overlaps = None
+                proposals = boxes
                 if self.mask_loss:
                     # model.py:172-196: OverlapCalculator + TrainSelector on this forward's proposals, one launch; the mask
                     # branch runs on the drawn proposals ++ every ground-truth box
                     sc = self._scenes[k]
-                    _, boxes, descs = self.mask_selector.select(boxes, sc["gt_dev"])
+                    overlaps, boxes, descs = self.mask_selector.select(boxes, sc["gt_dev"])
                     boxes = list(boxes)
                 elif self.mask_boxes is not None:     # (the reference's mask head trains on <= 24 selected proposals per sample)
                     boxes = [b[:self.mask_boxes] for b in boxes]
@@ -391,6 +463,22 @@ class SceneStep:
                                                   for t in (rpn_bbox, rpn_score))
                     roots += [rpn_bbox, rpn_score]
                     root_grads += [g if scale == 1.0 else g * scale for g in gr]
+            if self.class_loss:
+                # model.py:170-183: the class network's TrainSelector draws from the same overlap descriptions as the mask
+                # network's; the branch runs on its forward boxes (drawn proposals ++ every ground-truth box)
+                sc = self._scenes[k]
+                if overlaps is None:
+                    overlaps, cboxes, cdescs = self.class_selector.select(proposals, sc["gt_dev"])
+                else:
+                    cboxes, cdescs = self.class_selector(overlaps)
+                class_scores, csel = m.class_branch(m.backbone.unet.interims[m.class_level], list(cboxes))
+                if self.keep_class_grads:
+                    class_scores.retain_grad()
+                sel_scores, sel_labels = self.class_loss_selector(class_scores, csel, cdescs, overlaps, sc["gt_label"])
+                self.class_losses = self.class_criterion(sel_scores, sel_labels)
+                self.class_out = (class_scores, csel, cdescs, sel_labels)
+                roots.append(self.class_losses)
+                root_grads.append(self._class_grad)
             logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
             gm = self._gms.get(k)
             if self.mask_loss:
@@ -447,6 +535,40 @@ class SceneStep:
                         boxes = [b[:self.mask_boxes] for b in boxes]
                 logits, _ = m.mask(scene, out, boxes)
         return out, logits
+
+    def predict(self, k=0):
+        """The reference's evaluation chain (model.py:185-219) on micro-batch k under torch.no_grad(): backbone -> RPN ->
+        proposal selection -> class branch on all kept boxes -> ClassPredictor -> mask branch -> the mask column of each box's
+        PREDICTED class (roi.mask_predict).  Needs a step built with class_loss=True (the class branch exists only then).
+        -> dict with the reference's keys in the reference's spelling: `roi_bbox` (list of [n_s, 2, 3]), `class` (list of
+        int64 [n_s]), `class_propabilities` (list of [n_s, 18]), `mask` (list of fp32 [n_s, N_s]), and, when the step has the
+        segmentation head, `segmentation_class` (int64 [N]) / `segmentation_probabilites` ([N, 20])."""
+        m = self.model
+        if m.class_branch is None:
+            raise ValueError("predict() needs the class branch: build the step with class_loss=True")
+        from . import roi
+        from .loss import ClassPredictor, SegmentationPredictor
+        if k != self._k:
+            self._use_scene(k)
+        md = self._take_index(k)
+        self._start_prefetch(k)
+        with torch.no_grad():
+            out = m.backbone(self.coords, self.feats, self.size, self.batch_size, metadata=md)
+            interims = m.backbone.unet.interims
+            rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
+            _, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
+            boxes = list(boxes)
+            class_scores, csel = m.class_branch(interims[m.class_level], boxes)
+            class_indices, class_prob, class_raw = ClassPredictor()(class_scores, csel)
+            scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
+            logits, (sel, counts, splits) = m.mask(scene, out, boxes)
+            masks = roi.mask_predict(logits, sel, counts, splits, class_raw)
+            result = {"roi_bbox": boxes, "class": list(class_indices), "class_propabilities": list(class_prob), "mask": masks}
+            if m.segmentation is not None:
+                seg = m.segmentation(out)
+                result["segmentation_class"], result["segmentation_probabilites"] = SegmentationPredictor(True)(seg.float())
+            self.predict_out = (class_scores, logits, (sel, counts, splits))       # (for checks)
+        return result
 
     def step(self):
         n = self.batches_per_step
@@ -519,6 +641,15 @@ class SceneStep:
                   "boxes with points (scn_maskloss.hip)")
         elif self.n_gt:
             s += f"; ground truth: the first {self.n_gt} synthetic boxes per sample"
+        if self.class_loss:
+            s += ("; the class branch (SubM1 + 1 unit @32 on the stride-" + str(self.model.class_branch.stride) + " level, sparse "
+                  "ROI cut, 2^3/2 conv + unit @64 and @128, mean pool, Linear 128-64-18) trains on the reference's class loss: "
+                  "TrainSelector(0.1, 0, (32, 0, True)) draws <= 32 proposals with IoU >= 0.1 per sample and appends every "
+                  "ground-truth box, cross entropy against the associated instance's label (scn_xent.hip)")
+        if self.segmentation_loss:
+            s += ("; the segmentation head (SubM 1^3 to 20 classes, one row per point) trains on the reference's segmentation "
+                  "loss: cross entropy against the instances' labels + 2, -100 (ignored) outside every instance; its gradient "
+                  "replaces the synthetic one at the backbone output (scn_xent.hip)")
         if self.batches_per_step > 1:
             s += (f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
                   "voxels = all of them")
