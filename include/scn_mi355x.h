@@ -66,7 +66,9 @@ extern "C" {
  *      scn_rpn_loss_scratch_bytes / scn_rpn_loss, scn_rpn_loss_scale (130 entry points);
  *      additive within 5: + scn_mask_overlap_draw, scn_mask_loss_scratch_bytes / scn_mask_loss, scn_mask_loss_bwd,
  *      scn_mask_pack (135 entry points);
- *      additive within 5: + scn_xent_scratch_bytes / scn_xent_fwd, scn_xent_bwd, scn_softmax_argmax (139 entry points) */
+ *      additive within 5: + scn_xent_scratch_bytes / scn_xent_fwd, scn_xent_bwd, scn_softmax_argmax (139 entry points);
+ *      additive within 5: + scn_eval_mask_bits, scn_eval_pack_threshold, scn_eval_mask_iou, scn_eval_bbox_iou, scn_eval_match,
+ *      scn_eval_confusion (145 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -922,6 +924,53 @@ int scn_xent_fwd(const float* logits, int64_t n, int c, const int64_t* targets, 
 int scn_xent_bwd(const float* grad_loss, const float* logits, int64_t n, int c, const int64_t* targets, const float* weights,
                  int64_t ignore_index, const void* scratch, float* dlogits, scn_stream_t stream);
 int scn_softmax_argmax(const float* logits, int64_t n, int c, float* probabilities, int64_t* indices, scn_stream_t stream);
+
+/* ---- evaluation (ndsis/training/evaluation.py: MaskOverlapCalculator / BboxOverlapCalculator, PrecisionRecallCurve.
+ * calc_tp_indicator, ConfusionCalculator, BinaryMaskConfusionCalculator; ndsis/utils/mask.py:62-148) ----
+ * All integer results are exact; every mask IoU is one correctly rounded fp32 division of two exact integers and every box
+ * IoU follows bbox_overlap_prediction's operation order, so results are bit-equal to the reference and identical from run to
+ * run.  Offsets named *_offsets are HOST arrays of batch + 1 values (pair_offsets[b+1] - pair_offsets[b] = P_b * G_b); every
+ * other pointer is device memory.  Packed masks use scn_mask_pack's layout: sample b's [rows_b][ceil(N_b / 32)] uint32
+ * words, bit p % 32 of word p / 32 = point row p of the sample, bits beyond N_b zero.
+ *
+ * scn_eval_mask_bits (1 memset + 1 launch): logits fp32 [m][k], src_row / box_of int32 [m] (RoiSelection), class_of_box int64
+ * [n_boxes], bit_base int64 [n_boxes] = 32 * (first word of the box's mask row in out_words) - (first point row of the box's
+ * sample).  Bit = sigmoid(logits[r][class]) > mask_threshold with scn_mask_scatter's sigmoid and class validity rule; all
+ * n_words words are written.
+ * scn_eval_pack_threshold (1 launch): masks fp32 [p][n] > mask_threshold -> out_words [p][ceil(n / 32)].
+ * scn_eval_mask_iou (per 32 samples: row counts, tiles, finish): inter int32 [pairs] = popcount(pred & gt), pred_count int32
+ * [sum P], gt_count int32 [sum G], iou fp32 [pairs] (may be NULL) = float(inter) / float(|pred| + |gt| - inter), NaN for
+ * 0 / 0; pair_confusion (may be NULL; needs P_b == G_b) int64 [sum P][2][2] = [[tp, fp], [fn, tn]] of prediction i against
+ * ground truth i.  N_b < 2^31; the counts are exact for every such N_b, the quotient is the division of two exact integers
+ * for N_b <= 2^24 (beyond that the int -> fp32 conversions round first; the reference's fp32 sums stop being exact there too).
+ * scn_eval_bbox_iou (1 launch per 32 samples): boxes fp32 [n][2][3] (start, stop) -> iou fp32 [pairs].
+ * scn_eval_match (1 launch, one wave per problem): problem q = (problem_sample[q], problem_class[q] or -1 for all classes,
+ * problem_threshold[q]); pred_offsets / gt_offsets / pair_offsets are DEVICE int64 [batch + 1] here.  Its predictions are
+ * those of the sample with keep != 0 (keep uint8 [sum P], NULL: all) and pred_class == class, in their given order, its
+ * ground truths those with gt_class == class.  flags int8 at problem_out[q], P_b values: -1 not part of the problem, 1 true
+ * positive (the maximum IoU over the ground truths not yet matched, first index on a tie, is >= threshold; that ground truth
+ * is retired), 0 false positive (also when a NaN is among the remaining ground truths).  num_gt int32 [n_problems].
+ * max_gt = the largest G_b, at most 4096.
+ * scn_eval_confusion (2 memsets + 1 launch): confusion int64 [c][c] = counts of pred * c + gt over the rows with 0 <= gt < c;
+ * *n_bad_pred (may be NULL) = such rows whose pred is outside 0 .. c-1 (not counted in the matrix).  c <= 64. */
+int scn_eval_mask_bits(const float* logits, int64_t m, int k, const int32_t* src_row, const int32_t* box_of,
+                       const int64_t* class_of_box, int num_valid, float mask_threshold, const int64_t* bit_base,
+                       int64_t n_boxes, int64_t n_words, uint32_t* out_words, scn_stream_t stream);
+int scn_eval_pack_threshold(const float* masks, int64_t p, int64_t n, float mask_threshold, uint32_t* out_words,
+                            scn_stream_t stream);
+int scn_eval_mask_iou(const uint32_t* pred_words, const int64_t* pred_word_offsets, const uint32_t* gt_words,
+                      const int64_t* gt_word_offsets, const int64_t* pred_offsets, const int64_t* gt_offsets,
+                      const int64_t* pair_offsets, const int64_t* n_points, int batch, int32_t* inter, int32_t* pred_count,
+                      int32_t* gt_count, float* iou, int64_t* pair_confusion, scn_stream_t stream);
+int scn_eval_bbox_iou(const float* pred_boxes, const int64_t* pred_offsets, const float* gt_boxes, const int64_t* gt_offsets,
+                      const int64_t* pair_offsets, int batch, float* iou, scn_stream_t stream);
+int scn_eval_match(const float* iou, const int64_t* pred_offsets, const int64_t* gt_offsets, const int64_t* pair_offsets,
+                   int batch, int64_t max_gt, const uint8_t* keep, const int64_t* pred_class, const int64_t* gt_class,
+                   const int32_t* problem_sample, const int64_t* problem_class, const float* problem_threshold,
+                   const int64_t* problem_out, int n_problems, int any_class_problem, int8_t* flags, int32_t* num_gt,
+                   scn_stream_t stream);
+int scn_eval_confusion(const int64_t* pred, const int64_t* gt, int64_t n, int num_classes, int64_t* confusion,
+                       int64_t* n_bad_pred, scn_stream_t stream);
 
 #ifdef __cplusplus
 }

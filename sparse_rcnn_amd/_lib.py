@@ -160,6 +160,13 @@ _SIGS = {
     "scn_xent_fwd": (C.c_int, [p, i64, i32, p, p, i64, p, p, p, p]),
     "scn_xent_bwd": (C.c_int, [p, p, i64, i32, p, p, i64, p, p, p]),
     "scn_softmax_argmax": (C.c_int, [p, i64, i32, p, p, p]),
+    "scn_eval_mask_bits": (C.c_int, [p, i64, i32, p, p, p, i32, f32, p, i64, i64, p, p]),
+    "scn_eval_pack_threshold": (C.c_int, [p, i64, i64, f32, p, p]),
+    "scn_eval_mask_iou": (C.c_int, [p, C.POINTER(i64), p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                    C.POINTER(i64), i32, p, p, p, p, p, p]),
+    "scn_eval_bbox_iou": (C.c_int, [p, C.POINTER(i64), p, C.POINTER(i64), C.POINTER(i64), i32, p, p]),
+    "scn_eval_match": (C.c_int, [p, p, p, p, i32, i64, p, p, p, p, p, p, p, i32, i32, p, p, p]),
+    "scn_eval_confusion": (C.c_int, [p, p, i64, i32, p, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)

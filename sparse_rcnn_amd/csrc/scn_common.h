@@ -114,3 +114,23 @@ __device__ __forceinline__ unsigned long long scn_hash_slot(unsigned long long k
     h ^= h >> 33;
     return h & mask;
 }
+
+// ---- device functions shared by translation units that must agree bit for bit ----
+// sigmoid of a mask logit: k_mask_scatter (scn_elem.hip) writes it, k_eval_mask_bits (scn_eval.hip) thresholds it.
+__device__ __forceinline__ float scn_mask_sigmoid(float x) { return 1.f / (1.f + __expf(-x)); }
+
+// bbox_overlap_prediction (ndsis/utils/bbox.py:542-571) of one pair: a = (start as[3], stop ae[3], volume area_a), b = bx[7]
+// (start, stop, volume; volume = ((e0 - s0) * (e1 - s1)) * (e2 - s2)).  The reference's operation order, every operation
+// rounded once: k_mask_overlap_draw (scn_maskloss.hip) and k_eval_bbox_iou (scn_eval.hip) are bit-equal to it.
+__device__ __forceinline__ float scn_box_iou(const float* as, const float* ae, float area_a, const float* bx) {
+#pragma clang fp contract(off)
+    float inter = 1.f;                                       // prod over the dims of clamp(min_end - max_start, 0)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float lo = fmaxf(as[d], bx[d]), hi = fminf(ae[d], bx[3 + d]);
+        const float e = fmaxf((hi - lo), 0.f);
+        inter = d == 0 ? e : (inter * e);
+    }
+    const float uni = (area_a + bx[6]) - inter;
+    return (inter / uni);
+}

@@ -546,7 +546,7 @@ __global__ void k_mask_scatter(const float* __restrict__ scores, long long m, in
         const bool valid = cls >= 0 && (num_valid == 0 || cls < num_valid) && cls < k;
         if (!valid) continue;
         const float x = scores[r * k + cls];
-        out[row_base[box] + src_point[r]] = 1.f / (1.f + __expf(-x));
+        out[row_base[box] + src_point[r]] = scn_mask_sigmoid(x);
     }
 }
 

@@ -109,15 +109,7 @@ __global__ __launch_bounds__(kDrawThreads) void k_mask_overlap_draw(
                 for (int d = 0; d < 7; ++d) bx[d] = sb[j][d];
 #pragma unroll
                 for (int q = 0; q < kPropPerThread; ++q) {
-                    float inter = 1.f;                       // prod over the dims of clamp(min_end - max_start, 0)
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        const float lo = fmaxf(as[q][d], bx[d]), hi = fminf(ae[q][d], bx[3 + d]);
-                        const float e = fmaxf((hi - lo), 0.f);
-                        inter = d == 0 ? e : (inter * e);
-                    }
-                    const float uni = (area[q] + bx[6]) - inter;
-                    const float o = (inter / uni);
+                    const float o = scn_box_iou(as[q], ae[q], area[q], bx);
                     // overlaps.max(1): the first maximum wins; a NaN (0 / 0) wins over any number, as torch's max does
                     if (o > best[q] || (o != o && best[q] == best[q])) {
                         best[q] = o;

@@ -570,6 +570,81 @@ class SceneStep:
             self.predict_out = (class_scores, logits, (sel, counts, splits))       # (for checks)
         return result
 
+    def evaluate(self, scenes=None, *, score_threshold=0.9, mask_threshold=0.5, overlap_thresholds=(0.25, 0.5), eval_on_gt=True):
+        """The reference's `eval_model` (training.py:98-304; defaults scannet_config/run.py:917-934) on the step's own scenes
+        (`scenes`: micro-batch indices, default all): per micro-batch the chain of `predict()` under torch.no_grad(), but the
+        masks go logits -> packed bits -> popcount IoU (evaluation.mask_bits / mask_iou) and never exist as dense fp32;
+        `roi_score` is the ROI selector's.  With `eval_on_gt` the class branch and the mask branch also run on the ground-truth
+        boxes (model.py:194-238) and fill `gtbbox`, `gtmask`, `gtlabelmask`; the segmentation head, if the step has one, fills
+        `segment`.  Needs a step built with class_loss=True.  -> (combined_metrics, single_class_metrics) with the reference's
+        keys, `gtbbox_AP*` dropped as training.py:174-177 does; the accumulators stay on `self.eval_out`.  The metrics wait for
+        the host once per overlap accumulator and once per confusion accumulator; the forward waits where predict() does.
+        `scenes` may name the micro-batches in any order: the index structures are built by the forward itself, and an index
+        build that a previous step() prefetched is joined and dropped (the next step builds its own)."""
+        m = self.model
+        if m.class_branch is None:
+            raise ValueError("evaluate() needs the class branch: build the step with class_loss=True")
+        from . import evaluation as E
+        from .loss import ClassPredictor, SegmentationPredictor, pack_gt_masks
+        k_cls = m.mask.classes
+        bbox_calc = E.BboxOverlapCalculator(score_threshold=score_threshold)
+        mask_calc = E.MaskOverlapCalculator(mask_threshold, score_threshold=score_threshold)
+        names = ["bbox", "mask"] + (["gtbbox", "gtmask", "gtlabelmask"] if eval_on_gt else [])
+        acc = {n: E.OverlapAccumulator(bbox_calc if "bbox" in n else mask_calc) for n in names}
+        label_acc = E.ConfusionAccumulator(E.ConfusionCalculator(k_cls))
+        bin_acc = E.BinaryConfusionAccumulator(E.BinaryMaskConfusionCalculator(mask_threshold))
+        seg_acc = None
+        for k in (range(self.batches_per_step) if scenes is None else scenes):
+            if k != self._k:
+                self._use_scene(k)
+            sc = self._scenes[k]
+            self.finish()                      # a pending prefetch is for "the scene after the last one run", not for k
+            with torch.no_grad():
+                out = m.backbone(self.coords, self.feats, self.size, self.batch_size, metadata=None)
+                interims = m.backbone.unet.interims
+                rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
+                roi_score, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
+                roi_score, boxes = list(roi_score), list(boxes)
+                class_scores, csel = m.class_branch(interims[m.class_level], boxes)
+                class_indices, _, class_raw = ClassPredictor()(class_scores, csel)
+                gt_boxes, gt_label = sc["gt_dev"], sc["gt_label"]
+                if eval_on_gt:
+                    gt_class_scores, gcsel = m.class_branch(interims[m.class_level], gt_boxes)
+                    gt_class, _, gt_class_raw = ClassPredictor()(gt_class_scores, gcsel)
+                scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
+                logits, (sel, counts, splits) = m.mask(scene, out, boxes)
+                pred_bits = E.mask_bits(logits, sel, counts, splits, class_raw, 0, mask_threshold)
+                if "gt_mask" not in sc:
+                    sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in sc["gt_mask_cpu"]])
+                gt_mask = sc["gt_mask"]
+                acc["bbox"].add_batch(roi_score, boxes, gt_boxes, list(class_indices), gt_label)
+                acc["mask"].add_batch(roi_score, pred_bits, gt_mask, list(class_indices), gt_label)
+                if eval_on_gt:
+                    pseudo = [b.new_ones((len(b),)) for b in gt_boxes]
+                    glogits, (gsel, gcounts, gsplits) = m.mask(scene, out, gt_boxes)
+                    gt_bits = E.mask_bits(glogits, gsel, gcounts, gsplits, gt_class_raw, 0, mask_threshold)
+                    gtl_bits = E.mask_bits(glogits, gsel, gcounts, gsplits, torch.cat(list(gt_label)), 0, mask_threshold)
+                    acc["gtbbox"].add_batch(pseudo, gt_boxes, gt_boxes, list(gt_class), gt_label)
+                    label_acc.add_list_batch(list(gt_class), gt_label)
+                    acc["gtmask"].add_batch(pseudo, gt_bits, gt_mask, list(gt_class), gt_label)
+                    acc["gtlabelmask"].add_batch(pseudo, gtl_bits, gt_mask, gt_label, gt_label)
+                    bin_acc.add_batch(gtl_bits, gt_mask, gt_boxes, gt_label)
+                if m.segmentation is not None and "seg_target" in sc:
+                    seg_logits = m.segmentation(out).float()
+                    seg_class, _ = SegmentationPredictor(True)(seg_logits)
+                    seg_class_count = seg_logits.shape[1]
+                    if seg_acc is None:
+                        seg_acc = E.ConfusionAccumulator(E.ConfusionCalculator(int(seg_class_count)))
+                    seg_acc.add_batch(seg_class, sc["seg_target"])
+        helper = E.EvaluationHelper(list(overlap_thresholds), list(range(k_cls)))
+        combined, single_class, _, conf, oconf, binary = helper(
+            acc, {"segment": seg_acc} if seg_acc is not None else {}, {"gtbbox": label_acc} if eval_on_gt else {},
+            {"gtlabelmask": bin_acc} if eval_on_gt else {})
+        combined = {key: v for key, v in combined.items() if "gtbbox_AP" not in key}
+        self.eval_out = dict(overlap=acc, segment=seg_acc, gtbbox=label_acc if eval_on_gt else None,
+                             gtlabelmask=bin_acc if eval_on_gt else None, confusion=conf, overlap_confusion=oconf, binary=binary)
+        return combined, single_class
+
     def step(self):
         n = self.batches_per_step
         for k in range(n - 1):                    # training.py:436: (loss / batches_per_step).backward(), no update yet
