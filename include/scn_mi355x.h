@@ -68,7 +68,8 @@ extern "C" {
  *      scn_mask_pack (135 entry points);
  *      additive within 5: + scn_xent_scratch_bytes / scn_xent_fwd, scn_xent_bwd, scn_softmax_argmax (139 entry points);
  *      additive within 5: + scn_eval_mask_bits, scn_eval_pack_threshold, scn_eval_mask_iou, scn_eval_bbox_iou, scn_eval_match,
- *      scn_eval_confusion (145 entry points) */
+ *      scn_eval_confusion (145 entry points);
+ *      additive within 5: + scn_sample_stats, scn_sample_pack (147 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -971,6 +972,36 @@ int scn_eval_match(const float* iou, const int64_t* pred_offsets, const int64_t*
                    scn_stream_t stream);
 int scn_eval_confusion(const int64_t* pred, const int64_t* gt, int64_t n, int num_classes, int64_t* confusion,
                        int64_t* n_bad_pred, scn_stream_t stream);
+
+/* ---- training-sample conversion (ndsis/data/sparse_augmentation.py convert_sample :250-313 after augment_coords: get_masks
+ * :208-234, get_bbox :188-205, get_semantic_segmentation_labels :237-247, augment_features :152-185) ----
+ * A stored sample has N points with an instance id each, 0 .. I-1 or I = "no instance" (I = n_instances).  Neither call
+ * waits for the host; both are integer-exact or elementwise, so reruns give identical bits.
+ *
+ * scn_sample_stats (2 launches): discrete / table as scn_vox_discretize left them, start_host = the cut-out's start (what
+ * scn_vox_gather subtracts).  stats int32 [I + 1][8] per instance slot = (points, points with table >= 0, min x y z, max
+ * x y z of discrete - start over those kept points; INT32_MAX / INT32_MIN where there is none).  *n_bad_ids (device int32) =
+ * the points whose id is outside 0 .. I; they are in no slot.  Each workgroup collects in an LDS table of (I + 1) * 32 bytes
+ * and merges it with integer atomics.  I > SCN_SAMPLE_MAX_INSTANCES: SCN_ESIZE, nothing launched.  n < 1: SCN_EINVAL.
+ *
+ * scn_sample_pack (1 memset + 1 launch; nothing for m == 0), over the m kept rows `rows` (ascending, int32) in that order:
+ *   features fp32 [m][C], C = 3 use_color + use_ones + 3 use_normal = (colors[row] + color_noise, 1, normals[row] @ rotation
+ *     + normal_noise); rotation_host = the 3x3 almost_orthonormal (HOST, row-major), each product as fma(z, R2j, fma(y, R1j,
+ *     x * R0j)) like scn_vox_project; a noise pointer is device fp32 [3] or, with *_per_point != 0, [m][3] in kept-row order;
+ *     NULL = none.  The noise is added after the rotation, as the reference does.
+ *   seg_labels int64 [m] = seg_table[id of the row], seg_table device int64 [I + 1] (the mapped labels, then the background
+ *     label); both NULL: not wanted.  An id outside 0 .. I reads slot I.
+ *   mask_words uint32 [n_kept][ceil(m / 32)] = loss.PackedMasks' / scn_mask_pack's layout: bit p % 32 of word p / 32 of row
+ *     slot_of_instance[id] (device int32 [I + 1], -1 = instance not kept) is set for kept row p; every other bit, the bits
+ *     beyond m included, is zero.  n_kept == 0: slot_of_instance and mask_words may be NULL. */
+#define SCN_SAMPLE_MAX_INSTANCES 1023
+int scn_sample_stats(const int32_t* discrete, const int32_t* table, const int64_t* instance_ids, int64_t n, int n_instances,
+                     const int32_t* start_host, int32_t* stats, int32_t* n_bad_ids, scn_stream_t stream);
+int scn_sample_pack(const int32_t* rows, int64_t m, const float* colors, const float* normals, const int64_t* instance_ids,
+                    int n_instances, const float* rotation_host, const float* color_noise, int color_noise_per_point,
+                    const float* normal_noise, int normal_noise_per_point, int use_color, int use_ones, int use_normal,
+                    float* features, const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance,
+                    int64_t n_kept, uint32_t* mask_words, scn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ from .custom_operations import SparseGlobalPool, split_batch               # noq
 from . import optim                                                         # noqa: F401  (optim.Adam: the reference's optimizer)
 from . import loss                                                          # noqa: F401  (loss.RpnLoss, loss.MaskLoss, loss.ClassLoss, loss.CrossEntropyLoss: the reference's losses)
 from . import classhead                                                     # noqa: F401  (classhead.ClassBranch, classhead.SegmentationHead)
+from . import sample                                                        # noqa: F401  (sample.convert_sample, sample.collate: stored scene -> training batch)
 
 __all__ = [
     "Metadata", "SparseConvNetTensor", "ioLayers", "InputLayer", "OutputLayer", "Sequential", "ConcatTable",

@@ -167,6 +167,8 @@ _SIGS = {
     "scn_eval_bbox_iou": (C.c_int, [p, C.POINTER(i64), p, C.POINTER(i64), C.POINTER(i64), i32, p, p]),
     "scn_eval_match": (C.c_int, [p, p, p, p, i32, i64, p, p, p, p, p, p, p, i32, i32, p, p, p]),
     "scn_eval_confusion": (C.c_int, [p, p, i64, i32, p, p, p]),
+    "scn_sample_stats": (C.c_int, [p, p, p, i64, i32, p, p, p, p]),
+    "scn_sample_pack": (C.c_int, [p, i64, p, p, p, i32, p, p, i32, p, i32, i32, i32, i32, p, p, p, p, i64, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -181,6 +183,7 @@ PYRAMID_XCD_ORDER = 2
 PYRAMID_FUSED = 4
 PYRAMID_DESC_LEN = 8 + PYRAMID_MAX_LEVELS * PYRAMID_LEVEL_STRIDE
 COLSUM_BLOCKS = 512
+SAMPLE_MAX_INSTANCES = 1023      # SCN_SAMPLE_MAX_INSTANCES
 
 
 class ScnError(RuntimeError):

@@ -171,3 +171,30 @@ def make_segmentation(labels, masks, offset=2):
             seg[held] = offset + lab[first[held]]
         out.append(seg)
     return out
+
+
+def make_raw_sample(n_points=200_000, n_instances=40, voxel_size=0.02, grid=None, seed=1, n_raw_labels=41):
+    """One scene in the reference's STORED format (what `sample.convert_sample` takes, ndsis/data/data.py:6-8 without the
+    scene id): (coords fp32 [N,3] in metres, colors fp32 [N,3] in [-1,1], normals fp32 [N,3] unit, instance_ids int64 [N] with
+    values 0 .. n_instances (n_instances = no instance), semantic_instance_labels_raw int64 [n_instances] in
+    0 .. n_raw_labels-1), CPU tensors.  The surfaces are `make_scene`'s (about n_points points, 1.15 per voxel, mesh order), each
+    point moved to a random place inside its voxel and scaled by voxel_size; instance g = the points inside a box around a
+    random point (edges log-uniform grid/32 .. grid/5 voxels), the lowest-numbered box winning where boxes meet.  An instance
+    may have no point."""
+    rng = np.random.default_rng(seed + 77)
+    target = max(int(n_points / 1.15), 64)
+    if grid is None:
+        side = 64
+        while side < 1.6 * (target / 3) ** 0.5:
+            side *= 2
+        grid = (side, side, side // 2)
+    pts, feats, _ = make_scene(grid, target, dup=1.15, seed=seed)
+    coords = ((pts + rng.random(pts.shape)) * voxel_size).astype(np.float32)
+    ids = np.full(len(pts), n_instances, np.int64)
+    ctr = pts[rng.integers(0, len(pts), size=n_instances)].astype(np.float64)
+    edge = np.exp(rng.uniform(np.log(grid[0] / 32), np.log(grid[0] / 5), size=(n_instances, 3)))
+    for g in reversed(range(n_instances)):
+        ids[(np.abs(pts - ctr[g]) <= edge[g] / 2).all(1)] = g
+    labels_raw = rng.integers(0, n_raw_labels, size=n_instances).astype(np.int64)
+    return (torch.from_numpy(coords), torch.from_numpy(np.ascontiguousarray(feats[:, :3])),
+            torch.from_numpy(np.ascontiguousarray(feats[:, 4:7])), torch.from_numpy(ids), torch.from_numpy(labels_raw))

@@ -129,8 +129,14 @@ class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
-                 class_loss=False, segmentation_loss=False):
-        """rpn_loss (the `-rpn` workloads only): train the RPN on the reference's RPN loss (loss.RpnLoss with
+                 class_loss=False, segmentation_loss=False, batches=None):
+        """batches (the `-rpn` workloads only; default None = the synthetic scenes): `batches_per_step` collated batches
+        (`sample.collate` of `sample.convert_sample` outputs: the reference's batch dict) that take the place of the synthetic
+        scenes -- coordinates, features, spatial size, splits, ground-truth boxes, labels, packed instance masks and per-point
+        segmentation labels all come from the batch, so every loss, predict() and evaluate() run on converted data.  The
+        spatial size must be a multiple of 2^(levels - 1) of the workload's network, times 4 with class_loss (convert with
+        `required_size_factor`: 8, or 32, for the 4-level cfg3-rpn), else ValueError; instance labels must lie in 0 .. 17 and segmentation labels in 0 .. 19 or be -100.
+        rpn_loss (the `-rpn` workloads only): train the RPN on the reference's RPN loss (loss.RpnLoss with
         BatchwiseBboxTargetSelector(0.35, 0.15, 1/8), sigma 2; scannet_config/run.py:359-368,876-884) against the scene's
         synthetic boxes, in place of the fixed synthetic gradient on rpn_bbox / rpn_score.  Targets and draw are queued before
         the backbone forward; the two loss values stay on the device as `.rpn_losses`.
@@ -179,6 +185,14 @@ class SceneStep:
         if n_gt is not None and int(n_gt) < 1:
             raise ValueError("n_gt >= 1 required")
         self.n_gt = None if n_gt is None else int(n_gt)
+        if batches is not None:
+            if not workload.endswith("-rpn"):
+                raise ValueError("batches= applies to the -rpn workloads (the ground truth feeds the RPN, mask and class losses)")
+            if n_gt is not None:
+                raise ValueError("n_gt cuts the synthetic ground truth; a batch brings its own")
+            batches = list(batches)
+            if len(batches) != int(batches_per_step):
+                raise ValueError(f"batches: {int(batches_per_step)} collated batches required (batches_per_step), got {len(batches)}")
         self.workload, self.dtype, self.prefetch = workload, dtype, prefetch
         # lr=None: the workload's default (reported by describe() and in bench.py's line).  1e-6, and 1e-8 with an RPN in the
         # step: the SAME synthetic gradient on 3.7 M RPN outputs every step is a steady push, not noise -- at 1e-6 the score
@@ -209,7 +223,14 @@ class SceneStep:
             raise ValueError("dtype: f32 | bf16 | bf16-blocks")
         storage = {"f32": False, "bf16": "all", "bf16-blocks": True}[dtype]
         self._scenes = []
+        self.from_batches = batches is not None
+        # level constraint on a batch's spatial size: every 2^3/2 convolution halves an even size -- levels - 1 in the backbone,
+        # two more in the class branch, which cuts its boxes out of the coarsest level's grid
+        self._size_factor = 2 ** (len(self.channels) - 1) * (4 if class_loss else 1)
         for k in range(self.batches_per_step):
+            if self.from_batches:
+                self._scenes.append(self._scene_from_batch(batches[k], k))
+                continue
             coords, feats, size, bs, splits = make_batch(n_samples, self.grid, target or tg, dup=1.15, seed=seed + 1000 * k)
             boxes = make_boxes(coords, self.n_boxes, seed=seed + 1000 * k + 2) if self.n_boxes else None
             gt_boxes = boxes if (boxes is None or self.n_gt is None) else [b[:self.n_gt] for b in boxes]
@@ -267,6 +288,8 @@ class SceneStep:
             self._seg_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
         if self.mask_loss or self.class_loss or self.segmentation_loss:
             for k, sc in enumerate(self._scenes):      # instances built (and packed, for the mask loss) once per scene
+                if self.from_batches:                  # (a converted batch brought its instances: _scene_from_batch)
+                    continue
                 labels, masks = make_instances(sc["coords_cpu"], sc["gt_boxes"], n_classes=self.model.mask.classes,
                                                seed=seed + 1000 * k + 5)
                 flat = torch.cat(labels).to(self.device)
@@ -297,6 +320,28 @@ class SceneStep:
         self.out = self.logits = self.fin = None
 
     # ------------------------------------------------------------------------------------------------------------
+    def _scene_from_batch(self, batch, k):
+        """The scene dict of micro-batch k from a collated batch (sample.collate / the reference's collate_fn layout)."""
+        from .loss import PackedMasks, pack_gt_masks
+        coords, feats, size, batch_size, splits = batch["data"]
+        size = torch.as_tensor(size).to("cpu", torch.long)
+        factor = self._size_factor
+        if any(int(v) % factor or int(v) < factor for v in size):
+            raise ValueError(f"batches[{k}]: spatial size {tuple(int(v) for v in size)} is not a multiple of {factor} on every axis, "
+                             f"which the {len(self.channels)}-level network of '{self.workload}'"
+                             + (" with the class branch's two further 2^3/2 convolutions" if factor > 2 ** (len(self.channels) - 1)
+                                else "") + f" needs: convert the samples with required_size_factor={factor}")
+        if feats.shape[1] != 7:
+            raise ValueError(f"batches[{k}]: 7 feature columns (colour, ones, normal) required, got {feats.shape[1]}")
+        gt = [b.to(self.device, torch.float32) for b in batch["gt_bbox"]]
+        gt_mask = batch["gt_mask"]
+        if not isinstance(gt_mask, PackedMasks):
+            gt_mask = pack_gt_masks([mk.to(self.device) for mk in gt_mask])
+        return dict(coords_cpu=None, feats_cpu=None, size=size, batch_size=int(batch_size), splits=list(splits),
+                    coords=coords.to(self.device), feats=feats.to(self.device, torch.float32).contiguous(), boxes=gt, gt_boxes=gt,
+                    gt_dev=gt, gt_label=[l.to(self.device) for l in batch["gt_label"]], gt_mask=gt_mask, gt_mask_cpu=None,
+                    seg_target=batch["gt_segmentation"].to(self.device))
+
     def _use_scene(self, k):
         sc = self._scenes[k]
         self.coords_cpu, self.feats_cpu, self.size, self.batch_size, self.splits = (
@@ -672,7 +717,8 @@ class SceneStep:
             self._md_next = None
 
     def describe(self):
-        s = (f"BASELINE {self.baseline_entry}: {self.batch_size} synthetic ScanNet-shaped sample(s) per GPU, {self.n_active} "
+        s = (f"BASELINE {self.baseline_entry}: {self.batch_size} " + ("converted sample(s) per GPU (sample.convert_sample + collate),"
+             if self.from_batches else "synthetic ScanNet-shaped sample(s) per GPU,") + f" {self.n_active} "
              f"active voxels (grid {self.grid[0]}x{self.grid[1]}x{self.grid[2]}, 1.15 points/voxel), U-Net "
              + "-".join(map(str, self.channels)) + ", 2 pre-act residual blocks/level, 2^3/2 conv+deconv"
              + (", BatchNormReLU in the residual units (training mode, fp64 statistics; layer-by-layer path)"

@@ -42,6 +42,17 @@ def augment_coords(coords, *, rot_and_scale, sub_pixel_offset, spatial_size=None
     Returns (coords_batch_rows int64 device [M,4] = (x, y, z, batch_index), is_inside bool device [N],
     spatial_size int64 CPU [3], complete_shift fp32 CPU [3]) -- the first three columns / the other values are what the
     reference's augment_coords returns (:121-126)."""
+    return _augment_coords(coords, rot_and_scale=rot_and_scale, sub_pixel_offset=sub_pixel_offset, spatial_size=spatial_size,
+                           shift=shift, start_positions=start_positions, batch_index=batch_index)[:4]
+
+
+def _augment_coords(coords, *, rot_and_scale, sub_pixel_offset, spatial_size=None, shift=None, start_positions=None,
+                    batch_index=0, before_wait=None):
+    """augment_coords, and as a fifth value what sample.convert_sample goes on with: `rows` (rules.in_rows: the kept rows,
+    ascending, int32), `discrete` int32 [N,3] (before the move), `table` int32 [1,N] (row or -1) and `start` (host list: what
+    was subtracted).  start_positions may be a function of `discrete` (the random cut-out's draw).  before_wait(discrete,
+    table, start) runs once the cut-out is queued and before the host waits for the kept-row count: what it queues is
+    finished when that wait returns."""
     lib = L.lib()
     P = coords.to(torch.float32).contiguous()
     if not P.is_cuda or P.dim() != 2 or P.shape[1] != 3:
@@ -62,6 +73,10 @@ def augment_coords(coords, *, rot_and_scale, sub_pixel_offset, spatial_size=None
             sh = [int(s) for s in torch.as_tensor(shift).expand(3).tolist()]
             start, test = [-s for s in sh], [0, 0, 0]
         elif start_positions is not None:
+            if callable(start_positions):             # sample.random_cut_start: needs the voxels before the cut-out
+                L.check(lib.scn_vox_discretize(L.ptr(aug), n, L.ptr(shift_max), None, None, L.ptr(discrete), L.ptr(table),
+                                               L.stream()))
+                start_positions = start_positions(discrete)
             start = [int(s) for s in torch.as_tensor(start_positions).expand(3).tolist()]
             test = start
         else:
@@ -73,6 +88,8 @@ def augment_coords(coords, *, rot_and_scale, sub_pixel_offset, spatial_size=None
         start = [-s for s in sh]
         L.check(lib.scn_vox_discretize(L.ptr(aug), n, L.ptr(shift_max), None, None, L.ptr(discrete), L.ptr(table),
                                        L.stream()))
+    if before_wait is not None:
+        before_wait(discrete, table, start)
     rules = compact_rules(table, 1, n)
     rows = rules.in_rows                               # ascending kept rows (one host wait for their number)
     m = rows.shape[0]
@@ -84,7 +101,7 @@ def augment_coords(coords, *, rot_and_scale, sub_pixel_offset, spatial_size=None
         size_out = torch.tensor(size, dtype=torch.int64)
     else:                                              # discrete.max(0) = trunc(max(aug) + shift): trunc is monotonic
         size_out = (host[3:] + host[:3]).to(torch.int64) + 2 * torch.tensor(sh, dtype=torch.int64)
-    return out, table[0] >= 0, size_out, complete_shift
+    return out, table[0] >= 0, size_out, complete_shift, dict(rows=rows, discrete=discrete, table=table, start=start)
 
 
 def collate_coords(rows_list):
