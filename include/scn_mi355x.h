@@ -69,7 +69,9 @@ extern "C" {
  *      additive within 5: + scn_xent_scratch_bytes / scn_xent_fwd, scn_xent_bwd, scn_softmax_argmax (139 entry points);
  *      additive within 5: + scn_eval_mask_bits, scn_eval_pack_threshold, scn_eval_mask_iou, scn_eval_bbox_iou, scn_eval_match,
  *      scn_eval_confusion (145 entry points);
- *      additive within 5: + scn_sample_stats, scn_sample_pack (147 entry points) */
+ *      additive within 5: + scn_sample_stats, scn_sample_pack (147 entry points);
+ *      additive within 5: + scn_wgrad_step_begin / _hold / _flush / _discard, scn_wgrad_group_counts; switch
+ *      SCN_EXEC_GROUP_STEP (152 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -434,6 +436,32 @@ int scn_wgrad_bias_rules(const float* X, int cin, const float* dY, int cout, con
  * gradients of a network level (27 sum launches of ~7 us per backbone step become 8). */
 int scn_wgrad_defer_begin(void);
 int scn_wgrad_defer_flush(scn_stream_t stream);
+/* Step scope of the weight gradients (call site: executor.step_weight_gradients, the context SceneStep.forward_backward puts
+ * around its backward).  Nothing reads a parameter gradient before the optimizer step, so the weight-gradient launches of
+ * ALL backward passes of a step can run after the last pass: one k_wgrad_group grid per kernel variant (~15 rounds of
+ * units instead of 3-4 per pass: the ragged end of a grid is paid once) and one launch for all the unit sums.
+ *   scn_wgrad_step_begin()      opens the scope on the calling thread; an open scope is restarted and what it recorded is
+ *                               dropped (as scn_wgrad_defer_begin after a failed pass).  Holding is off.
+ *   scn_wgrad_step_hold(on)     on != 0: from now on a scn_wgrad_defer_flush on this thread launches nothing and hands the
+ *                               pass's recorded unit launches and sums to the scope; 0: passes flush as without a scope.
+ *                               Returns 1 when holding is in effect, else 0 (no scope open, or the developer switch
+ *                               SCN_EXEC_GROUP_STEP=0).  The caller sets it around the passes whose weight gradients it can
+ *                               deliver late.
+ *   scn_wgrad_step_flush(s)     closes the scope and launches what it holds on stream s: per job the plan, the units, the
+ *                               slabs, the instantiation and the fixed-order sum of the standalone launch -- same bits.
+ *   scn_wgrad_step_discard()    closes the scope and drops what it holds (a failed step).
+ * Until the flush has been queued the caller keeps everything the held launches read or write untouched: the operand slabs,
+ * the rule lists, the gradient buffers and a scratch region of its OWN per pass.  The job tables of a flush (any number of
+ * jobs; the argument form of a pass's flush carries six) go through a per-device ring of pinned host slots, each guarded by an
+ * event, and one hipMemcpyAsync on s: these few buffers are the one thing the library allocates itself. */
+int scn_wgrad_step_begin(void);
+int scn_wgrad_step_hold(int on);
+int scn_wgrad_step_flush(scn_stream_t stream);
+int scn_wgrad_step_discard(void);
+/* Launch counts since the last reset (process-wide; tests and profiles): out[0] k_wgrad_group<4> launches, out[1]
+ * k_wgrad_group<2> launches, out[2] weight-gradient unit launches on their own (k_wgrad_direct, k_wgrad_tb), out[3] unit-sum
+ * launches (k_wgradd_sum*).  reset != 0: zero them after reading.  out may be NULL. */
+void scn_wgrad_group_counts(int64_t out[4], int reset);
 int64_t scn_wgrad_scratch_bytes2(int cin, int cout, const int64_t* prefix_host, int n_off);
 int scn_wgrad_bias_rules2(const float* X0, const float* dY0, const float* X1, const float* dY1, int cin, int cout,
                           const int32_t* in_rows, const int32_t* out_rows, const int64_t* prefix_host, int n_off,

@@ -349,6 +349,10 @@ extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn
     // Grouped weight gradients: with deferred sums, the fp32 weight gradients' unit launches are recorded too and run at the
     // end of the pass as grouped launches (one per pass for the package's plans), before the sums.  Same plans, units and
     // sums: same bits.  SCN_EXEC_GROUP_WGRAD=0: each launches in place.  Not with the launch timing (it brackets ops).
+    // Under a step scope that holds (scn_wgrad_step_hold, set by the caller around this pass) the flush below launches nothing:
+    // units and sums go to the step's lists and scn_wgrad_step_flush runs them with those of the other passes, so the
+    // caller keeps `bufs`, `grads` and `scratch` of this pass untouched until then.  Also after a failed op: the caller
+    // discards the scope (scn_wgrad_step_discard).
     const scn::SwitchVal group_sw = scn::sw(scn::SW_EXEC_GROUP_WGRAD);
     const bool group = defer && !(group_sw.set && group_sw.i == 0) && !g_timing.on;
     Ctx c{levels, n_levels, bufs, params, grads, scratch, arrival, stream};

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include <string.h>
+#include <mutex>
 #include <vector>
 
 #include "scn_common.h"
@@ -163,15 +164,43 @@ __device__ __forceinline__ void wd_range(const GJob& j, int ov, int o, int prob,
 #define WD_KIND(TA_, TB_, Q_, E_, I_, H_) \
     ((TA_) | ((TB_) << 3) | ((Q_) ? 1 << 6 : 0) | ((E_) ? 1 << 7 : 0) | ((I_) ? 1 << 8 : 0) | ((H_) ? 1 << 9 : 0))
 
-// VAR 4: the 2 x 2 K-mode forms only (the C = 32 levels, 4 workgroups per CU, 98 VGPRs); VAR 2: every fp32 form without
-// EDGE, held to 2 workgroups per CU -- what the 4 x 4 forms have alone -- by amdgpu_waves_per_eu (227 VGPRs, no spill; the
+// VAR 4: the 2 x 2 K-mode forms only (the C = 32 levels, 4 workgroups per CU: the bound is 128 VGPRs;
+// 98 in the argument form, 102 in the table form); VAR 2: every fp32 form without
+// EDGE, held to 2 workgroups per CU -- what the 4 x 4 forms have alone -- by amdgpu_waves_per_eu (227 VGPRs of 256, no spill; the
 // unconstrained union took 292 registers).  EDGE and bf16-row forms are wider (up to 290 registers) and launch on their own.
-template <int VAR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VAR, VAR))) void k_wgrad_group(GroupJobs g) {
+//
+// Two sources of the job table.  GroupJobs: up to WG_MAX_JOBS jobs by value in the kernel arguments (a pass's flush).
+// GroupTable: any number of jobs in device memory (a step's flush, scn_wgrad_step_flush: ~25 jobs of a cfg2 step would be
+// 15 KB of arguments); the host writes the table into a pinned ring slot and copies it on the launch stream (TableRing).
+// The workgroup finds its job by a linear walk over <= 6 prefix entries, or by binary search over the table's.
+struct GroupTable { const GJob* job; const int* block_start; int n; };
+
+__device__ __forceinline__ int wg_find(const GroupJobs& g, int b) {
     int j = 0;
-    while (j + 1 < g.n && (int)blockIdx.x >= g.block_start[j + 1]) ++j;
-    const GJob& J = g.job[j];
-    const int local = (int)blockIdx.x - g.block_start[j];
+    while (j + 1 < g.n && b >= g.block_start[j + 1]) ++j;
+    return j;
+}
+// (The table is written before the launch and read-only in it: it is read through the constant address space, as the
+//  kernel arguments are, so that a job's fields arrive by scalar loads and the register budget of the argument form holds.)
+#define WG_CONST(T_, p_) ((const __attribute__((address_space(4))) T_*)(p_))
+__device__ __forceinline__ int wg_find(const GroupTable& t, int b) {
+    int lo = 0, hi = t.n;                                            // block_start[lo] <= b < block_start[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (b >= WG_CONST(int, t.block_start)[mid]) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ const GJob& wg_job(const GroupJobs& g, int j) { return g.job[j]; }
+__device__ __forceinline__ int wg_start(const GroupJobs& g, int j) { return g.block_start[j]; }
+__device__ __forceinline__ const GJob& wg_job(const GroupTable& t, int j) { return *(const GJob*)(WG_CONST(GJob, t.job) + j); }
+__device__ __forceinline__ int wg_start(const GroupTable& t, int j) { return WG_CONST(int, t.block_start)[j]; }
+
+template <int VAR, typename SRC = GroupJobs>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VAR, VAR))) void k_wgrad_group(SRC g) {
+    const int j = wg_find(g, (int)blockIdx.x);
+    const GJob& J = wg_job(g, j);
+    const int local = (int)blockIdx.x - wg_start(g, j);
     const int zb = local / J.units, unit = local - zb * J.units;     // the standalone grid runs x (units) fastest
     const float* __restrict__ X_0 = (const float*)J.X[0];
     const float* __restrict__ dY_0 = (const float*)J.dY[0];
@@ -528,6 +557,18 @@ __global__ __launch_bounds__(256) void k_wgradd_sum_many(SumJobs jobs) {
     wgradd_sum_body<4>(jobs.job[j], (int)blockIdx.x - jobs.block_start[j]);
 }
 
+// ... of any number of launches, the jobs in device memory (the sums of a whole step, scn_wgrad_step_flush; same table ring
+// as the grouped unit launches): binary search over the block prefix.
+__global__ __launch_bounds__(256) void k_wgradd_sum_many_tab(const SumArgs* __restrict__ job,
+                                                             const int* __restrict__ block_start, int n) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int)blockIdx.x >= block_start[mid]) lo = mid; else hi = mid;
+    }
+    wgradd_sum_body<4>(job[lo], (int)blockIdx.x - block_start[lo]);
+}
+
 namespace {
 struct Shape { int ta, tb; bool quad; };
 
@@ -656,7 +697,12 @@ struct WdLaunch {
     size_t lds() const { return (quad ? 4 * 64 : 4 * ta * tb * 4 * 64 + 4 * 64) * sizeof(float); }
 };
 
+// Launch counts since the last reset (scn_wgrad_group_counts): k_wgrad_group<4>, k_wgrad_group<2>, weight-gradient unit
+// launches on their own (k_wgrad_direct, k_wgrad_tb), unit-sum launches.
+std::atomic<int64_t> g_counts[4];
+
 int launch_direct(const WdLaunch& r, scn_stream_t stream) {
+    g_counts[2].fetch_add(1, std::memory_order_relaxed);
     const dim3 grid((unsigned)r.units(), 1, (unsigned)(r.pl.nbi * r.pl.nbj));
     const bool ident = r.ident, edge = r.edge, hb = r.hb;
 #define LAUNCH_WD(TA_, TB_, Q_, E_, I_, H_)                                                                      \
@@ -707,7 +753,103 @@ struct DeferState {
 };
 thread_local DeferState g_defer;
 
-// The recorded unit launches of a pass.  The job with the most work picks the grouped kernel (its workgroups per CU are
+// Step scope (scn_wgrad_step_begin / _hold / _flush): above the pass scope, per calling thread.  While it holds, the flush of
+// a pass launches nothing: its recorded unit launches and sums move here, and scn_wgrad_step_flush runs the whole step's.
+struct StepState {
+    bool open = false, hold = false;
+    std::vector<SumArgs> jobs; std::vector<int> blocks;
+    std::vector<WdLaunch> units;
+    void clear() { jobs.clear(); blocks.clear(); units.clear(); }
+};
+thread_local StepState g_step;
+
+// Job tables of the step flush: a ring of pinned host slots, each with its device copy, ONE ring per device for the whole
+// process (behind a mutex that a flush holds from taking a slot to recording its event: a thread that comes and goes leaves
+// nothing behind).  A flush writes its tables into the next slot and queues ONE hipMemcpyAsync on the launch stream; the
+// slot's event, recorded behind the launches that read the device copy, guards both halves against the flush that takes
+// the slot again N flushes later (by then it has long completed: the wait is a formality, not a host wait of the step).
+// The buffers belong to the library and live as long as the process (a few times 64 KB per device that ran a step scope);
+// a slot is reallocated only when a table outgrows it.
+struct TableRing {
+    static constexpr int N = 4;
+    struct Slot { char* host = nullptr; char* dev = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
+    std::mutex mu;
+    Slot slot[N];
+    int next = 0;
+    int release(Slot& s) {
+        if (s.busy) SCN_HIP(hipEventSynchronize(s.ev));
+        s.busy = false;
+        if (s.host) SCN_HIP(hipHostFree(s.host));
+        s.host = nullptr;
+        if (s.dev) SCN_HIP(hipFree(s.dev));
+        s.dev = nullptr;
+        s.cap = 0;
+        return SCN_OK;
+    }
+    int take(size_t bytes, Slot** out) {                       // (under `mu`, on the ring's device)
+        Slot& s = slot[next];
+        next = (next + 1) % N;
+        if (!s.ev) SCN_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+        if (s.busy) SCN_HIP(hipEventSynchronize(s.ev));
+        s.busy = false;
+        if (s.cap < bytes) {
+            const int rc = release(s);
+            if (rc != SCN_OK) return rc;
+            const size_t cap = (bytes + 65535) & ~(size_t)65535;
+            SCN_HIP(hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault));
+            SCN_HIP(hipMalloc((void**)&s.dev, cap));
+            s.cap = cap;
+        }
+        *out = &s;
+        return SCN_OK;
+    }
+};
+constexpr int RING_DEVICES = 64;
+TableRing g_rings[RING_DEVICES];
+
+void fill_gjob(const WdLaunch& r, GJob& J) {
+    for (int p = 0; p < 2; ++p) {
+        J.X[p] = p == 0 ? (const void*)r.X : (r.n_prob > 1 ? r.more.X[p] : nullptr);
+        J.dY[p] = p == 0 ? (const void*)r.dY : (r.n_prob > 1 ? r.more.dY[p] : nullptr);
+    }
+    J.in_rows = r.in_rows; J.out_rows = r.out_rows; J.slabs = r.slabs; J.db_slabs = r.db_slabs;
+    J.per = r.pl.per;
+    J.cin = r.cin; J.cout = r.cout; J.relu_in = r.relu_in; J.cout_pad = r.cout_pad;
+    J.n_off = r.pl.n_off; J.n_real = r.pl.n_real; J.nbi = r.pl.nbi; J.nbj = r.pl.nbj;
+    J.units = r.units(); J.kind = r.kind(); J.db_mask = r.db_mask;
+    for (int v = 0; v <= r.pl.n_off; ++v) J.unit_start[v] = r.pl.unit_start[v];
+    for (int o = 0; o <= r.pl.n_real; ++o) J.prefix[o] = r.pl.rule_start[o];   // = the real prefix (see GJob)
+}
+
+// longest unit first, then by workgroup count: the short units fill the last round of the long ones
+void sort_members(const std::vector<WdLaunch>& R, std::vector<int>& members) {
+    std::stable_sort(members.begin(), members.end(), [&](int a, int b) {
+        if (R[a].wg_work() != R[b].wg_work()) return R[a].wg_work() > R[b].wg_work();
+        return R[a].workgroups() > R[b].workgroups();
+    });
+}
+
+template <typename SRC>
+int launch_group(int var, const SRC& g, unsigned blocks, size_t lds, scn_stream_t stream) {
+    if (var == 4) {
+        g_counts[0].fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL((k_wgrad_group<4, SRC>), dim3(blocks), dim3(256), lds, S(stream), g);
+    } else {
+        static scn::DeviceOnce attr_set;
+        if (attr_set.needed()) {
+            SCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_group<2, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
+            attr_set.done();
+        }
+        g_counts[1].fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL((k_wgrad_group<2, SRC>), dim3(blocks), dim3(256), lds, S(stream), g);
+    }
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+// The recorded unit launches of a pass that flushes at its own end (no step scope holds; flush_step below is the step's
+// rule: one grid per variant).  The job with the most work picks the grouped kernel (its workgroups per CU are
 // what its standalone launch has: k_wgrad_group<4> for the 2 x 2 forms, <2> otherwise); the jobs that kernel can run join
 // it, largest workgroup first, then by workgroup count, so that the short units fill the last round of the long ones.  The
 // others -- and a group of one -- launch as they would have in place.
@@ -731,10 +873,7 @@ int flush_units(scn_stream_t stream) {
             const int rc = launch_direct(R[k], stream);
             if (rc != SCN_OK) return rc;
         }
-    std::stable_sort(members.begin(), members.end(), [&](int a, int b) {
-        if (R[a].wg_work() != R[b].wg_work()) return R[a].wg_work() > R[b].wg_work();
-        return R[a].workgroups() > R[b].workgroups();
-    });
+    sort_members(R, members);
     for (size_t base = 0; base < members.size(); base += WG_MAX_JOBS) {
         GroupJobs g;
         memset(&g, 0, sizeof(g));
@@ -742,35 +881,98 @@ int flush_units(scn_stream_t stream) {
         size_t lds = 0;
         for (int q = 0; q < g.n; ++q) {
             const WdLaunch& r = R[members[base + q]];
-            GJob& J = g.job[q];
-            for (int p = 0; p < 2; ++p) {
-                J.X[p] = p == 0 ? (const void*)r.X : (r.n_prob > 1 ? r.more.X[p] : nullptr);
-                J.dY[p] = p == 0 ? (const void*)r.dY : (r.n_prob > 1 ? r.more.dY[p] : nullptr);
-            }
-            J.in_rows = r.in_rows; J.out_rows = r.out_rows; J.slabs = r.slabs; J.db_slabs = r.db_slabs;
-            J.per = r.pl.per;
-            J.cin = r.cin; J.cout = r.cout; J.relu_in = r.relu_in; J.cout_pad = r.cout_pad;
-            J.n_off = r.pl.n_off; J.n_real = r.pl.n_real; J.nbi = r.pl.nbi; J.nbj = r.pl.nbj;
-            J.units = r.units(); J.kind = r.kind(); J.db_mask = r.db_mask;
-            for (int v = 0; v <= r.pl.n_off; ++v) J.unit_start[v] = r.pl.unit_start[v];
-            for (int o = 0; o <= r.pl.n_real; ++o) J.prefix[o] = r.pl.rule_start[o];   // = the real prefix (see GJob)
+            fill_gjob(r, g.job[q]);
             g.block_start[q + 1] = g.block_start[q] + (int)r.workgroups();
             if (r.lds() > lds) lds = r.lds();
         }
-        if (var == 4) {
-            hipLaunchKernelGGL(k_wgrad_group<4>, dim3(g.block_start[g.n]), dim3(256), lds, S(stream), g);
-        } else {
-            static scn::DeviceOnce attr_set;
-            if (attr_set.needed()) {
-                SCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_group<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024));
-                attr_set.done();
-            }
-            hipLaunchKernelGGL(k_wgrad_group<2>, dim3(g.block_start[g.n]), dim3(256), lds, S(stream), g);
-        }
-        SCN_LAUNCH_CHECK();
+        const int rc = launch_group(var, g, (unsigned)g.block_start[g.n], lds, stream);
+        if (rc != SCN_OK) return rc;
     }
     return SCN_OK;
+}
+
+// The recorded unit launches and sums of a STEP (scn_wgrad_step_flush): one k_wgrad_group launch per variant -- <4> takes the
+// 2 x 2 K-mode forms, <2> every other fp32 form without EDGE, each job under the instantiation, the plan and the slabs of its
+// standalone launch, longest unit first across the whole step -- then ONE launch for all the sums.  EDGE and bf16-row forms,
+// and a variant with a single job, launch on their own.  The job tables travel through one slot of the table ring:
+// [GJob x n2][GJob x n4][SumArgs x ns][int x (n2 + 1)][int x (n4 + 1)][int x (ns + 1)], one copy.
+int flush_step(scn_stream_t stream) {
+    const std::vector<WdLaunch>& R = g_step.units;
+    std::vector<int> m2, m4;
+    for (size_t k = 0; k < R.size(); ++k) {
+        const int v = group_variant(R[k]);
+        if (v == 4) m4.push_back((int)k);
+        else if (v == 2) m2.push_back((int)k);
+    }
+    if (m2.size() < 2) m2.clear();
+    if (m4.size() < 2) m4.clear();
+    std::vector<char> grouped(R.size(), 0);
+    for (int k : m2) grouped[k] = 1;
+    for (int k : m4) grouped[k] = 1;
+    for (size_t k = 0; k < R.size(); ++k)
+        if (!grouped[k]) {
+            const int rc = launch_direct(R[k], stream);
+            if (rc != SCN_OK) return rc;
+        }
+    sort_members(R, m2);
+    sort_members(R, m4);
+    const size_t n2 = m2.size(), n4 = m4.size(), ns = g_step.jobs.size();
+    if (n2 + n4 + ns == 0) return SCN_OK;
+    auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t o2 = 0, o4 = up(o2 + n2 * sizeof(GJob)), os = up(o4 + n4 * sizeof(GJob));
+    const size_t b2 = up(os + ns * sizeof(SumArgs)), b4 = up(b2 + (n2 + 1) * sizeof(int));
+    const size_t bs = up(b4 + (n4 + 1) * sizeof(int)), bytes = up(bs + (ns + 1) * sizeof(int));
+    int dev_id = 0;
+    SCN_HIP(hipGetDevice(&dev_id));
+    SCN_REQUIRE(dev_id >= 0 && dev_id < RING_DEVICES);
+    TableRing& ring = g_rings[dev_id];
+    std::lock_guard<std::mutex> ring_lock(ring.mu);
+    TableRing::Slot* slot = nullptr;
+    int rc = ring.take(bytes, &slot);
+    if (rc != SCN_OK) return rc;
+    char* h = slot->host;
+    memset(h, 0, bytes);
+    size_t lds2 = 0, lds4 = 0;
+    int* s2 = (int*)(h + b2);
+    for (size_t q = 0; q < n2; ++q) {
+        const WdLaunch& r = R[m2[q]];
+        fill_gjob(r, ((GJob*)(h + o2))[q]);
+        s2[q + 1] = s2[q] + (int)r.workgroups();
+        if (r.lds() > lds2) lds2 = r.lds();
+    }
+    int* s4 = (int*)(h + b4);
+    for (size_t q = 0; q < n4; ++q) {
+        const WdLaunch& r = R[m4[q]];
+        fill_gjob(r, ((GJob*)(h + o4))[q]);
+        s4[q + 1] = s4[q] + (int)r.workgroups();
+        if (r.lds() > lds4) lds4 = r.lds();
+    }
+    int* ss = (int*)(h + bs);
+    for (size_t q = 0; q < ns; ++q) {
+        memcpy(h + os + q * sizeof(SumArgs), &g_step.jobs[q], sizeof(SumArgs));
+        ss[q + 1] = ss[q] + g_step.blocks[q];
+    }
+    SCN_HIP(hipMemcpyAsync(slot->dev, h, bytes, hipMemcpyHostToDevice, S(stream)));
+    // from here on the slot is in use by the stream: the event goes behind whatever was queued, also after a failed launch
+    const char* d = slot->dev;
+    if (n2) {
+        GroupTable t{(const GJob*)(d + o2), (const int*)(d + b2), (int)n2};
+        rc = launch_group(2, t, (unsigned)s2[n2], lds2, stream);
+    }
+    if (rc == SCN_OK && n4) {
+        GroupTable t{(const GJob*)(d + o4), (const int*)(d + b4), (int)n4};
+        rc = launch_group(4, t, (unsigned)s4[n4], lds4, stream);
+    }
+    if (rc == SCN_OK && ns) {
+        g_counts[3].fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL(k_wgradd_sum_many_tab, dim3((unsigned)ss[ns]), dim3(256), 0, S(stream),
+                           (const SumArgs*)(d + os), (const int*)(d + bs), (int)ns);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = scn::fail(SCN_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    }
+    if (hipEventRecord(slot->ev, S(stream)) == hipSuccess) slot->busy = true;
+    else if (rc == SCN_OK) rc = scn::fail(SCN_EHIP, "%shipEventRecord failed for a job-table slot", "");
+    return rc;
 }
 }  // namespace
 
@@ -847,6 +1049,7 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
 #undef PICK_WT
 #undef LAUNCH_WT
         SCN_LAUNCH_CHECK();
+        g_counts[2].fetch_add(1, std::memory_order_relaxed);
     } else {
         WdLaunch r;
         r.pl = pl;
@@ -879,6 +1082,7 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
     if (V == 4) hipLaunchKernelGGL(k_wgradd_sum<4>, dim3(blocks), dim3(256), 0, S(stream), sa);
     else hipLaunchKernelGGL(k_wgradd_sum<1>, dim3(blocks), dim3(256), 0, S(stream), sa);
     SCN_LAUNCH_CHECK();
+    g_counts[3].fetch_add(1, std::memory_order_relaxed);
     return SCN_OK;
 }
 
@@ -895,6 +1099,15 @@ extern "C" int scn_wgrad_defer_flush(scn_stream_t stream) {
     SCN_REQUIRE(g_defer.on);
     g_defer.on = false;
     g_defer.group = false;
+    if (g_step.open && g_step.hold) {            // a step scope holds the pass's launches back: scn_wgrad_step_flush runs them
+        g_step.units.insert(g_step.units.end(), g_defer.units.begin(), g_defer.units.end());
+        g_step.jobs.insert(g_step.jobs.end(), g_defer.jobs.begin(), g_defer.jobs.end());
+        g_step.blocks.insert(g_step.blocks.end(), g_defer.blocks.begin(), g_defer.blocks.end());
+        g_defer.units.clear();
+        g_defer.jobs.clear();
+        g_defer.blocks.clear();
+        return SCN_OK;
+    }
     int rc = flush_units(stream);                // the recorded unit launches first: the sums read their slabs
     g_defer.units.clear();
     const size_t n = g_defer.jobs.size();
@@ -908,12 +1121,48 @@ extern "C" int scn_wgrad_defer_flush(scn_stream_t stream) {
         }
         if (jobs.n == 1) hipLaunchKernelGGL(k_wgradd_sum<4>, dim3(jobs.block_start[1]), dim3(256), 0, S(stream), jobs.job[0]);
         else hipLaunchKernelGGL(k_wgradd_sum_many, dim3(jobs.block_start[jobs.n]), dim3(256), 0, S(stream), jobs);
+        g_counts[3].fetch_add(1, std::memory_order_relaxed);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = scn::fail(SCN_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
     g_defer.jobs.clear();
     g_defer.blocks.clear();
     return rc;
+}
+
+// Step scope: see include/scn_mi355x.h.
+extern "C" int scn_wgrad_step_begin(void) {
+    g_step.open = true;                          // (a scope left open by a failed step is restarted: what it recorded is dropped)
+    g_step.hold = false;
+    g_step.clear();
+    return SCN_OK;
+}
+
+extern "C" int scn_wgrad_step_hold(int on) {
+    const scn::SwitchVal v = scn::sw(scn::SW_EXEC_GROUP_STEP);
+    g_step.hold = on != 0 && g_step.open && !(v.set && v.i == 0);
+    return g_step.hold ? 1 : 0;
+}
+
+extern "C" int scn_wgrad_step_flush(scn_stream_t stream) {
+    SCN_REQUIRE(g_step.open);
+    g_step.open = g_step.hold = false;
+    const int rc = flush_step(stream);
+    g_step.clear();
+    return rc;
+}
+
+extern "C" int scn_wgrad_step_discard(void) {
+    g_step.open = g_step.hold = false;
+    g_step.clear();
+    return SCN_OK;
+}
+
+extern "C" void scn_wgrad_group_counts(int64_t out[4], int reset) {
+    for (int k = 0; k < 4; ++k) {
+        if (out) out[k] = g_counts[k].load(std::memory_order_relaxed);
+        if (reset) g_counts[k].store(0, std::memory_order_relaxed);
+    }
 }
 
 extern "C" int scn_wgrad_rules(const float* X, int cin, const float* dY, int cout, const int32_t* in_rows,

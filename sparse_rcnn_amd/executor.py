@@ -18,8 +18,10 @@ channel plans the two-source NetworkInNetwork kernel does not take, empty levels
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
 
 import torch
 
@@ -436,7 +438,9 @@ def _layout(specs, ns):
     return offs, tot
 
 
-def _run(stage, ops, levels, table, ptab, gtab, dev, side=False):
+def _run(stage, ops, levels, table, ptab, gtab, dev, side=False, own_scratch=None):
+    if own_scratch is not None:                # a pass inside `step_weight_gradients` (never a timed or a side-stream one)
+        return _run_plain(stage, ops, levels, table, ptab, gtab, dev, False, own_scratch)
     from . import profiling
     t = profiling.TIMER
     if t is not None and t.exec_timing():      # a sampled step of bench.py: the C call brackets its tile-convolution launches
@@ -449,12 +453,16 @@ def _run(stage, ops, levels, table, ptab, gtab, dev, side=False):
     return _run_plain(stage, ops, levels, table, ptab, gtab, dev, side)
 
 
-def _run_plain(stage, ops, levels, table, ptab, gtab, dev, side=False):
+def _run_plain(stage, ops, levels, table, ptab, gtab, dev, side=False, own_scratch=None):
     lib = L.lib()
     arr, _, ns = levels
     sb, ac = i64(0), i64(0)
     L.check(lib.scn_exec_requirements(ops, len(ops), arr, len(ns), C.byref(sb), C.byref(ac)))
-    scratch = L.scratch(sb.value, dev)
+    if own_scratch is not None:                # the unit slabs of this pass live until the step's flush: its own allocation
+        scratch = torch.empty(max(sb.value, 256), dtype=torch.uint8, device=dev)
+        own_scratch.append(scratch)
+    else:
+        scratch = L.scratch(sb.value, dev)
     arrival = L.arrival(max(ac.value, 1), dev)
     if side and SIDE_LEAVES:
         key = (dev.index, L.stream())
@@ -469,6 +477,99 @@ def _run_plain(stage, ops, levels, table, ptab, gtab, dev, side=False):
         return
     L.check(lib.scn_exec_run(ops, len(ops), arr, len(ns), table, ptab, gtab, scratch.data_ptr(), scratch.numel(),
                              arrival.data_ptr(), L.stream()))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# step scope of the weight gradients
+# ----------------------------------------------------------------------------------------------------------------------
+_step_scope = threading.local()
+LAST_STEP_SCOPE = {"passes": 0, "delivered": 0}    # what the last scope that closed held back (tests)
+
+
+class _StepScope:
+    def __init__(self):
+        self.deliver = []           # (parameter, view of the flat gradient buffer of its pass)
+        self.pending = set()        # id of every parameter in `deliver`: a second pass that uses it runs in place
+        self.keep = []              # everything the held-back launches read or write, until the flush has been queued
+        self.passes = 0             # backward passes whose weight gradients were held back
+
+
+def step_scope_passes():
+    """Passes held back by the scope open on this thread (None: no scope is open)."""
+    sc = getattr(_step_scope, "scope", None)
+    return None if sc is None else sc.passes
+
+
+@contextlib.contextmanager
+def step_weight_gradients():
+    """Run the weight gradients of every compiled stage whose backward falls inside the block as ONE grid per kernel variant
+    and one sum launch, after the last backward pass (scn_wgrad_step_begin / _flush): no consumer reads
+    a parameter gradient before the optimizer step.  Inside the block the backward of an eligible stage (`_step_eligible`)
+    returns None for its parameters; at exit, once the flush has been queued on the current stream, `p.grad` is assigned for
+    each of them.  Every other stage runs as without the block.  For `loss.backward()` / `torch.autograd.backward` callers that
+    read `.grad` afterwards -- `torch.autograd.grad` would see None.  Not under torch's DistributedDataParallel or anything else
+    that hooks the AccumulateGrad nodes themselves: such hooks are invisible here and would never fire for a held-back parameter.  Per thread (a backward that autograd runs on another
+    thread sees no scope and runs in place), not nestable; an exception inside drops what was recorded and is re-raised."""
+    if getattr(_step_scope, "scope", None) is not None:
+        raise RuntimeError("executor.step_weight_gradients is not nestable")
+    lib = L.lib()
+    L.check(lib.scn_wgrad_step_begin())
+    sc = _step_scope.scope = _StepScope()
+    try:
+        yield sc
+    except BaseException:
+        _step_scope.scope = None
+        lib.scn_wgrad_step_discard()
+        raise
+    _step_scope.scope = None
+    try:
+        L.check(lib.scn_wgrad_step_flush(L.stream()))
+    except BaseException:
+        lib.scn_wgrad_step_discard()
+        raise
+    LAST_STEP_SCOPE["passes"], LAST_STEP_SCOPE["delivered"] = sc.passes, len(sc.deliver)
+    with torch.no_grad():
+        for p, view in sc.deliver:              # (the flush is queued: on this stream every later reader sees them written)
+            if p.grad is None:
+                p.grad = view
+            else:
+                # a later pass of the block that ran in place (the same parameter used twice, or reached through another
+                # path) has put its gradient there meanwhile: add, as AccumulateGrad would have -- two terms, same bits
+                p.grad.add_(view)
+    # one stream: what the held-back launches read may go back to the caching allocator now that they are queued
+    sc.keep.clear()
+    sc.deliver.clear()
+
+
+def _step_eligible(stage, kept, needs, pending=()):
+    """The parameters of a backward pass inside `step_weight_gradients` whose gradients can be delivered at its exit:
+    [(position in the returned gradients, parameter)], or None when the stage has to run in place -- bf16 storage, the
+    executor's launch timing or the side stream on, gradient mode on (a double backward), a W or b that is not the module's own
+    leaf tensor (a channel-padded stage sees padded views from `_wb`), a parameter that has a `.grad` already (a later
+    micro-batch: autograd accumulates), one that a pass held back earlier in the same block will deliver (`pending`: one
+    network applied twice in a graph, two backward calls in one block -- the second use runs in place and the exit adds the
+    two) or one that carries hooks (the bucketed all-reduce needs its gradients during backward)."""
+    if stage.bf16 or SIDE_LEAVES or torch.is_grad_enabled():
+        return None
+    from . import profiling
+    t = profiling.TIMER
+    if t is not None and t.exec_timing():
+        return None
+    out, k = [], 0
+    for mi, (m, _) in enumerate(stage.mods):
+        for which, p in ((0, m.weight), (1, m.bias)):
+            j = 2 * mi + which
+            if p is None:                       # (phys[j] was None as well: save_for_backward skipped it)
+                return None
+            if kept[k] is not p or not p.is_leaf:
+                return None
+            k += 1
+            if not needs[j]:
+                continue
+            if p.grad is not None or id(p) in pending or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
+                return None
+            out.append((j, p))
+    return out
 
 
 LAST_FORWARD = {"lean": False, "ws_bytes": 0}      # what the last stage forward did (tests)
@@ -589,6 +690,25 @@ class StageFunction(torch.autograd.Function):
         gb = flat.data_ptr()
         for k, o in enumerate(goffs):
             gtab[k] = gb + 4 * o
+        scope = getattr(_step_scope, "scope", None)
+        late = None
+        if scope is not None:
+            late = _step_eligible(stage, kept, ctx.needs_input_grad[3 + stage.n_inputs:], scope.pending)
+        if late is not None and L.lib().scn_wgrad_step_hold(1) == 1:
+            # the C side holds this pass's weight-gradient launches and sums back until the scope's flush: the pass gets a
+            # scratch allocation of its own, and the scope keeps what those launches touch
+            own = []
+            try:
+                _run(stage, stage.bwd_arr, levels, table, ptab, gtab, dev, own_scratch=own)
+            finally:
+                L.lib().scn_wgrad_step_hold(0)
+            scope.keep.append((kept, ws, dout, flat, own, levels, table, gtab))
+            for j, p in late:
+                v = views[j]
+                scope.deliver.append((p, flat[v[0]:v[0] + v[1]].view(v[2])))
+                scope.pending.add(id(p))
+            scope.passes += 1
+            return (None, None, None, *dins, *([None] * len(views)))
         _run(stage, stage.bwd_arr, levels, table, ptab, gtab, dev, side=True)
         grads = [None if v is None else flat[v[0]:v[0] + v[1]].view(v[2]) for v in views]
         del kept

@@ -70,7 +70,13 @@ LATE_PREFETCH = _os.environ.get("SCN_LATE_PREFETCH", "1") != "0"
 BACKWARD_INLINE = _os.environ.get("SCN_BACKWARD_INLINE", "1") != "0"
 
 
-def _backward(roots, grads):
+def _backward(roots, grads, step_scope=False):
+    """step_scope: inside executor.step_weight_gradients -- the weight gradients of the compiled stages run as one grid per
+    kernel variant after the last backward pass and arrive in `.grad` when the call returns."""
+    if step_scope:
+        from . import executor
+        with executor.step_weight_gradients():
+            return _backward(roots, grads)
     if BACKWARD_INLINE:
         with torch.autograd.set_multithreading_enabled(False):
             torch.autograd.backward(roots, grads)
@@ -129,8 +135,12 @@ class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
-                 class_loss=False, segmentation_loss=False, batches=None):
-        """batches (the `-rpn` workloads only; default None = the synthetic scenes): `batches_per_step` collated batches
+                 class_loss=False, segmentation_loss=False, batches=None, step_group=True):
+        """step_group: run the fp32 weight gradients of a step as one grid per kernel variant after the last backward pass
+        (executor.step_weight_gradients; one rank, no gradient buckets).  It keeps every stage's workspaces and unit slabs alive
+        until then -- the cfg2 step's working set grows from 1.04 to 2.03 GB -- so False is the way to fit a scene that only fits
+        with the per-pass form.
+        batches (the `-rpn` workloads only; default None = the synthetic scenes): `batches_per_step` collated batches
         (`sample.collate` of `sample.convert_sample` outputs: the reference's batch dict) that take the place of the synthetic
         scenes -- coordinates, features, spatial size, splits, ground-truth boxes, labels, packed instance masks and per-point
         segmentation labels all come from the batch, so every loss, predict() and evaluate() run on converted data.  The
@@ -208,6 +218,7 @@ class SceneStep:
         if weighting not in ("equal", "count"):
             raise ValueError("weighting: equal | count")
         self.weighting = weighting
+        self.step_group = bool(step_group)
         self.batches_per_step = int(batches_per_step)
         if self.batches_per_step < 1:
             raise ValueError("batches_per_step >= 1")
@@ -468,7 +479,7 @@ class SceneStep:
         if m.mask is None:
             if zero:
                 self.flat.zero_grad()
-            _backward([root0], [gys])
+            _backward([root0], [gys], step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
             logits = None
         else:
             scene = (self.coords, fin, self.size, self.batch_size, self.splits)
@@ -554,7 +565,7 @@ class SceneStep:
             # (an empty crop -- no proposal caught a point: the mask branch contributes nothing on this rank)
             if zero:
                 self.flat.zero_grad()
-            _backward(roots, root_grads)
+            _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
         self.out, self.logits, self.fin = out, logits, fin
 
     def forward_only(self, k=0):
@@ -782,6 +793,9 @@ class SceneStep:
         else:
             s += (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + plain SGD on the flat parameter buffer, lr {self.lr:g} "
                   "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)")
+        if self.step_group and not self.flat.buckets and self.dtype == "f32" and self.batches_per_step == 1:
+            s += ("; fp32 weight gradients of the whole step in one grid per kernel variant after the last backward pass "
+                  "(workspaces and unit slabs live until then; step_group=False: per pass)")
         if self.prefetch:
             s += "; rulebooks of batch i+1 built on a helper thread during batch i"
         return s
