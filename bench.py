@@ -2,7 +2,13 @@
 """Headline benchmark: active-voxels/sec, forward + backward of the ScanNet U-Net backbone (BASELINE.json configs[1]):
 ~150k active voxels per scene, 32->64->128->256 channels, 3^3 submanifold + 2^3/2 conv/deconv, fp32.
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg5] [--dtype f32|bf16] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg5] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set-up, W warm-up steps, K timed steps, the dump if asked for, the
+result line (with the `roofline` / `kernels` figures its HIP events took on the timed steps themselves).  `--full` adds
+every measurement that takes a run of its own, after the timed steps and outside `ms_per_step`: the evaluation-only child
+process, the index build alone, the step without prefetch, forward only, changing scenes, the drop-in module path, the
+bf16 side leg and the CPU baseline.
 
 N > 1, either way:
   * `python bench.py --gpus N ...` with no torchrun environment: this process makes NO GPU call and starts N fresh child
@@ -43,7 +49,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)       # >= 10 warm-up, >= 50 timed iterations
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take every side measurement that needs a run of its own "
+                         "(`forward_only` with its fresh-process child, `index_build`, `ms_per_step_no_prefetch`, "
+                         "`changing_scenes`, `dropin`, the `bf16` leg, `cpu_baseline`); the --no-... options below leave "
+                         "single ones out of it.  Off by default: the headline figures are the same either way")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the timed CPU baseline")
     ap.add_argument("--target", type=int, default=None, help="active voxels per scene (default: the workload's)")
     ap.add_argument("--workload", choices=("cfg2", "cfg2-bn", "cfg3", "cfg3-rpn", "cfg5", "ref", "ref-crop", "ref-crop-rpn"), default="cfg2",
                     help="cfg2 = the configuration the metric is quoted on (default); cfg2-bn = cfg2 with BatchNormReLU in the "
@@ -66,12 +77,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-prefetch", dest="prefetch", action="store_false",
                     help="build the index structures inside the forward pass instead of one batch ahead")
     ap.add_argument("--dropin", dest="dropin", action="store_true", default=True,
-                    help="(default) also time the layer-by-layer module path the reference's module_factory builds (lazy "
-                         "Metadata, no helper thread) and report it as `dropin` next to the headline")
+                    help="(default, with --full) also time the layer-by-layer module path the reference's module_factory builds "
+                         "(lazy Metadata, no helper thread) and report it as `dropin` next to the headline")
     ap.add_argument("--no-dropin", dest="dropin", action="store_false")
     ap.add_argument("--no-bf16-leg", dest="bf16_leg", action="store_false",
-                    help="skip the short bf16-storage side leg (cfg2 in bf16: ms/step + k_conv_tb roofline) of the default run")
-    ap.add_argument("--no-extras", action="store_true", help="skip the index-build / no-prefetch side measurements")
+                    help="skip the short bf16-storage side leg (cfg2 in bf16: ms/step + k_conv_tb roofline) of a --full run")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the side measurements on the GPU (all but the CPU baseline)")
     ap.add_argument("--buckets", type=int, default=4,
                     help="slices of the flat gradient buffer all-reduced from the gradient hooks while backward runs (N > 1); "
                          "0: one all-reduce after backward")
@@ -96,6 +108,14 @@ def parse_args(argv=None):
     elif a.bf16_blocks:
         a.dtype = "bf16-blocks"
     return a
+
+
+def side_legs(args, world=1):
+    """Which measurements beyond the timed steps a run takes; a plain run (no --full) takes none.
+    -> {"gpu": the legs of side_measurements, "fresh_child": the evaluation-only child process, "cpu_baseline": ...}"""
+    gpu = bool(args.full and not args.no_extras)
+    return {"gpu": gpu, "fresh_child": gpu and args.gpus == 1 and world == 1,
+            "cpu_baseline": bool(args.full and world == 1 and not args.no_cpu_baseline)}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -336,9 +356,11 @@ def run(args):
     per_rank = [dict(rank=r, ms_per_step=v[0], n_active=int(v[1]), allreduce_ms_exposed=None if v[2] < 0 else v[2],
                      n_roi_rows=int(v[3])) for r, v in enumerate(t.tolist() for t in per_rank)]
 
-    # ---- side measurements outside the timed region (rank 0's numbers; every rank runs them so collectives stay matched)
+    # ---- side measurements outside the timed region, --full only (rank 0's numbers; every rank runs them so collectives
+    # stay matched)
     extras = {}
-    if not args.no_extras:
+    legs = side_legs(args, world)
+    if legs["gpu"]:
         extras = side_measurements(job, args, world, dist, torch)
 
     if rank == 0:
@@ -347,7 +369,7 @@ def run(args):
             "metric": "active-voxels/sec fwd+bwd, ScanNet U-Net backbone",
             "value": total_vox * args.steps / dt,
             "unit": "active-voxels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
             "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "scaling_note": "1 scene per GPU: N ranks process a batch of N scenes per step; against the same batch on one "
@@ -393,7 +415,7 @@ def run(args):
                                   "tflops": v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] else None,
                                   "algorithmic_GBps": v["bytes"] / (v["ms"] * 1e-3) / 1e9 if v["ms"] else None}
                               for k, v in ks.items()}
-        if world == 1 and not args.no_cpu_baseline:
+        if legs["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline(job.coords_cpu, job.feats_cpu, job.channels)
         else:
             out["cpu_baseline"] = None
@@ -798,7 +820,7 @@ def main():
         sys.exit(forward_only_child(args))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_extras:
+    if side_legs(args)["fresh_child"] and "WORLD_SIZE" not in os.environ:
         # the evaluation-only process runs first and alone: as a child of a process that holds a HIP context of its own the
         # same forward took 3 ms longer per step at 600 k voxels (two contexts time-sliced on one GPU)
         _FRESH = forward_only_fresh(args)

@@ -77,3 +77,32 @@ def test_bench_accepts_the_option():
     assert a.steps == 7 and a.dump_outputs == "out"
     d = bench.parse_args([])
     assert d.dump_outputs is None and d.lr == 0.0
+
+
+def test_a_plain_run_takes_no_side_leg_and_full_takes_them_all(monkeypatch):
+    """`--full` is off by default; without it no leg beyond the timed steps runs, whatever the --no-... options say, and the
+    evaluation-only child is not started; with it every leg runs unless its own --no-... option leaves it out."""
+    none = {"gpu": False, "fresh_child": False, "cpu_baseline": False}
+    assert bench.parse_args([]).full is False
+    for argv in ([], ["--gpus", "1", "--steps", "5", "--warmup", "2"], ["--no-extras"], ["--no-cpu-baseline"], ["--dropin"],
+                 ["--gpus", "2"], ["--dump-outputs", "d"]):
+        assert bench.side_legs(bench.parse_args(argv)) == none, argv
+    assert bench.side_legs(bench.parse_args(["--full"])) == {"gpu": True, "fresh_child": True, "cpu_baseline": True}
+    assert bench.side_legs(bench.parse_args(["--full", "--no-extras"])) == {"gpu": False, "fresh_child": False, "cpu_baseline": True}
+    assert bench.side_legs(bench.parse_args(["--full", "--no-cpu-baseline"])) == {"gpu": True, "fresh_child": True, "cpu_baseline": False}
+    # N ranks: every rank takes the GPU legs (their collectives stay matched); no child process, no CPU baseline
+    assert bench.side_legs(bench.parse_args(["--full", "--gpus", "2"]), world=2) == {"gpu": True, "fresh_child": False, "cpu_baseline": False}
+
+    started = []
+    monkeypatch.setattr(bench, "_FRESH", None)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "forward_only_fresh", lambda args: started.append("child") or {"ms_per_step": 1.0})
+    monkeypatch.setattr(bench, "run", lambda args: started.append("run") or 0)
+    for argv, want in ((["--gpus", "1", "--steps", "5", "--warmup", "2"], ["run"]), (["--full"], ["child", "run"])):
+        del started[:]
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        try:
+            bench.main()
+        except SystemExit as e:
+            assert e.code == 0
+        assert started == want, (argv, started)

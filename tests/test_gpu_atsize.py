@@ -1186,3 +1186,25 @@ def test_bench_dump_outputs_of_the_timed_step_are_reproducible(gpu, tmp_path):
         scale = max(float(np.abs(a).max()), 1e-30)
         assert float(np.abs(a - b).max()) / scale <= FEAT_TOL, name
     assert total <= 64 * 2 ** 20
+
+
+def test_bench_plain_run_stops_at_its_headline(gpu):
+    """`bench.py --gpus 1 --steps N --warmup W` with no other option: the result line of the timed steps (value, ms_per_step,
+    the roofline its events took on those steps) and none of the legs that take runs of their own -- those are `--full`'s."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--target", "30000"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["metric"].startswith("active-voxels/sec") and d["unit"] == "active-voxels/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["roofline"]["kernel"] == "k_conv_ts" and 0 < d["roofline"]["frac"] < 1
+    assert d["cpu_baseline"] is None
+    for leg in ("index_build", "index_build_ms", "ms_per_step_no_prefetch", "forward_only", "forward_only_ms", "changing_scenes",
+                "dropin", "bf16"):
+        assert leg not in d, leg

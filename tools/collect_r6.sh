@@ -6,7 +6,7 @@ O=$R/gpurun_out/r6
 mkdir -p $O
 cd $R
 PART=${1:-all}
-b() { name=$1; shift; python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; echo "bench $name rc=$?"; }
+b() { name=$1; shift; python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; echo "bench $name rc=$?"; }
 if [ $PART = all ] || [ $PART = bench ]; then
 b default
 b cfg2_bf16 --dtype bf16 --steps 100 --warmup 20 --no-cpu-baseline
@@ -21,8 +21,8 @@ b ref_crop --workload ref-crop --steps 100 --warmup 20 --no-cpu-baseline
 b ref_crop_rpn --workload ref-crop-rpn --steps 40 --warmup 10 --no-cpu-baseline
 b ref_crop_rpn_bf16 --workload ref-crop-rpn --dtype bf16 --steps 40 --warmup 10 --no-cpu-baseline
 b cfg2_bn --workload cfg2-bn --steps 60 --warmup 15 --no-cpu-baseline
-SCN_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n2_gloo_one_gpu.json 2> $O/bench_n2.err; echo "bench n2 rc=$?"
-SCN_BENCH_BACKEND=gloo python bench.py --gpus 2 --workload cfg3-rpn --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n2_gloo_cfg3rpn_bf16.json 2> $O/bench_n2b.err; echo "bench n2 cfg3-rpn rc=$?"
+SCN_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n2_gloo_one_gpu.json 2> $O/bench_n2.err; echo "bench n2 rc=$?"
+SCN_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --workload cfg3-rpn --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n2_gloo_cfg3rpn_bf16.json 2> $O/bench_n2b.err; echo "bench n2 cfg3-rpn rc=$?"
 SCN_BENCH_FORCE_DIST=1 SCN_DP_FORCE_BUCKETS=1 python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-extras > $O/bench_rccl_one_rank.json 2> $O/bench_rccl.err; echo "bench rccl-1 rc=$?"
 python tools/index_fused_ab.py 30 2>&1 | grep -v amdgpu.ids > $O/index_fused_ab.txt; echo "index ab rc=$?"
 python tools/long_run.py 400 2>&1 | grep -v amdgpu.ids > $O/long_run.txt; echo "long run rc=$?"
