@@ -71,7 +71,8 @@ extern "C" {
  *      scn_eval_confusion (145 entry points);
  *      additive within 5: + scn_sample_stats, scn_sample_pack (147 entry points);
  *      additive within 5: + scn_wgrad_step_begin / _hold / _flush / _discard, scn_wgrad_group_counts; switch
- *      SCN_EXEC_GROUP_STEP (152 entry points) */
+ *      SCN_EXEC_GROUP_STEP (152 entry points);
+ *      additive within 5: + scn_roialign_fwd / _bwd, scn_dense_maxpool_fwd / _bwd (156 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -1030,6 +1031,36 @@ int scn_sample_pack(const int32_t* rows, int64_t m, const float* colors, const f
                     const float* normal_noise, int normal_noise_per_point, int use_color, int use_ones, int use_normal,
                     float* features, const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance,
                     int64_t n_kept, uint32_t* mask_words, scn_stream_t stream);
+
+/* ---- dense RoiAlign and the unclamped dense max pool of the reference's dense class branch (ndsis/modules/
+ * roi_select_dense.py:28-141 RoiAlign with clip_boxes=True; nn.MaxPool3d(2)) -- csrc/scn_roialign.hip, fp32 ----
+ * F fp32 [batch X Y Z][c], channels-last, row ((b X + x) Y + y) Z + z; size_host = (X, Y, Z) and extract_host = (ex, ey, ez),
+ * each >= 2, int64 [3] on the HOST.  boxes fp32 [n_boxes][2][3] = (start, stop) in cells, already transformed and clipped to
+ * [0, size - 1]; sample_of_box int32 [n_boxes], ascending, in 0 .. batch - 1.  Out fp32 [n_boxes ex ey ez][c], row
+ * ((r ex + i) ey + j) ez + k.  Per axis sample i sits at c_i = min(i * ((stop - start) / (e - 1)) + start, stop), every
+ * operation rounded once; it reads cells floor(c_i) and ceil(c_i) with weights 1 - w and w, w = c_i - floor(c_i); a corner's
+ * weight is (wx * wy) * wz.  `table` is DEVICE memory of 4 * n_boxes * (3 * (ex + ey + ez) + 2 * (X + Y + Z)) bytes that the
+ * forward fills (the cells, clamped to the volume, and the weights of every (box, axis, sample); per (box, axis, cell) the
+ * first sample that touches the cell and how many consecutive ones do) and the backward reads.  Extents <= 1024, sizes <= 65536.
+ * scn_roialign_fwd: 3 launches, none for n_boxes == 0.
+ * scn_roialign_bwd: 1 launch (n_boxes == 0: one memset).  dF fp32 [batch X Y Z][c], EVERY row written, 0 where no sample
+ * reads the cell.  A gather per (cell, channel) in a fixed order -- the boxes of the cell's sample ascending, within a box the
+ * touching samples i, j, k ascending, nested (sum over k, times the y weight, sum over j, times the x weight, sum over i) --
+ * without atomics: reruns give identical bits.
+ * scn_dense_maxpool_fwd / _bwd (1 launch each, none for n_boxes == 0): X fp32 [n_boxes ex ey ez][c] -> Y fp32
+ * [n_boxes ex/2 ey/2 ez/2][c], extent_host = (ex, ey, ez) int64 [3] on the HOST, every extent even.  Y = the maximum of the 8
+ * children, NOT clamped at 0 (scn_pool_fwd is); argmax uint8, one per element of Y = the child (dx * 2 + dy) * 2 + dz that
+ * gave it, the first one on a tie, a NaN child wins.  The backward writes every element of dX: dY at that child, 0 at the
+ * other seven.  Neither call waits for the host. */
+int scn_roialign_fwd(const float* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                     const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host, void* table, float* Out,
+                     scn_stream_t stream);
+int scn_roialign_bwd(const float* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch,
+                     const int64_t* size_host, int c, const int64_t* extract_host, float* dF, scn_stream_t stream);
+int scn_dense_maxpool_fwd(const float* X, int64_t n_boxes, const int64_t* extent_host, int c, float* Y, uint8_t* argmax,
+                          scn_stream_t stream);
+int scn_dense_maxpool_bwd(const float* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host, int c,
+                          float* dX, scn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,10 @@ _SIGS = {
     "scn_eval_confusion": (C.c_int, [p, p, i64, i32, p, p, p]),
     "scn_sample_stats": (C.c_int, [p, p, p, i64, i32, p, p, p, p]),
     "scn_sample_pack": (C.c_int, [p, i64, p, p, p, i32, p, p, i32, p, i32, i32, i32, i32, p, p, p, p, i64, p, p]),
+    "scn_roialign_fwd": (C.c_int, [p, i32, C.POINTER(i64), i32, p, p, i64, C.POINTER(i64), p, p, p]),
+    "scn_roialign_bwd": (C.c_int, [p, p, p, i64, i32, C.POINTER(i64), i32, C.POINTER(i64), p, p]),
+    "scn_dense_maxpool_fwd": (C.c_int, [p, i64, C.POINTER(i64), i32, p, p, p]),
+    "scn_dense_maxpool_bwd": (C.c_int, [p, p, i64, C.POINTER(i64), i32, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)

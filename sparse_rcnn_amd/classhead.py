@@ -11,6 +11,21 @@ scannet_config/run.py:633-732 (the `sparse and not class_output_anchor` arm), ex
     -> vectorice_layer    : SparseGlobalPool(torch.mean): one row per box, zeros for a box without sites
     -> linear_layer       : ReLU, Linear(128, 64), ReLU, Linear(64, num_classes)                       (run.py:723-728)
 
+``DenseClassBranch``: the same ClassNetwork on its DENSE arm, the one the reference's committed configuration takes
+(scannet_config/run.py:340 `dense_class = True`, so `class_output_anchor=True` :603 and `cut_shape = (16, 16, 16)` :636-638): it
+reads the dense volume an anchor level's dilation stack produced (model.py:435-437), here the channels-last slab
+rpn.DenseRpn keeps:
+
+  volume slab [B X Y Z, C] (the fully active grid of the anchor level)
+    -> input_conv_layer   : 1^3 C->32 + 1 residual unit on the whole volume
+    -> roi_getter         : roi.RoiAlign(cut_shape, clip_boxes=True, resize_boxes=stride): every box trilinear to 16^3
+                            (scn_roialign_fwd) -- the slab of the fully active grid 16^3 with batch R
+    -> dense max pool 2   : the plain maximum, no clamp (scn_dense_maxpool_fwd; scn.MaxPooling clamps at 0)
+    -> output_conv_layer  : Convolution 32->64 2^3/2 + unit, Convolution 64->128 2^3/2 + unit on the fully active box grids
+                            8^3, 4^3, 2^3 -- a dense same-convolution is a submanifold convolution on a fully active grid (rpn.py)
+    -> vectorice_layer    : mean over the 2^3 sites of a box
+    -> linear_layer       : ReLU, Linear(128, 64), ReLU, Linear(64, num_classes)
+
 ``SegmentationHead``: the reference's sparse ``SegmentationNetwork`` (model.py:449-467): SubM 1^3 C->num_classes with
 bias, then the OutputLayer: one row of class scores per point.
 """
@@ -157,6 +172,142 @@ class ClassBranch(nn.Module):
             cands = [k[:-len(tail)] for k in state_dict if k.endswith(tail)]
             prefix = next((c for c in cands if c + "linear_layer.1.weight" in state_dict), cands[0] if cands else "")
         return _load_mapped(self.named_oracle_params(), self.reference_key_map(), state_dict, prefix,
+                            ("input_conv_layer.", "output_conv_layer.", "linear_layer."), strict)
+
+
+def dense_reference_key_map(n_output_levels=2, num_units=1, n_linear=2):
+    """state_dict key of the reference's DENSE ClassNetwork -> this package's parameter name
+    (`DenseClassBranch.named_oracle_params`).  The dense residual is a `DenseResidual` whose convolutions sit at
+    `inner_block.{1,3}`; index 0 of `output_conv_layer` is the parameterless max pool, so level l sits at l + 1.  Checked against
+    the key lists of reference networks built on the CPU (tests/golden/dense_class_keys.json)."""
+    out = {}
+    for t in ("weight", "bias"):
+        out[f"input_conv_layer.0.0.0.{t}"] = f"in.{t}"
+        for u in range(num_units):
+            for v, idx in enumerate((1, 3)):
+                out[f"input_conv_layer.0.1.{u}.inner_block.{idx}.{t}"] = f"in.res{u}.conv{v}.{t}"
+        for l in range(n_output_levels):
+            out[f"output_conv_layer.{l + 1}.0.0.{t}"] = f"down{l}.{t}"
+            for u in range(num_units):
+                for v, idx in enumerate((1, 3)):
+                    out[f"output_conv_layer.{l + 1}.1.{u}.inner_block.{idx}.{t}"] = f"down{l}.res{u}.conv{v}.{t}"
+        for i in range(n_linear):
+            out[f"linear_layer.{2 * i + 1}.{t}"] = f"lin{i}.{t}"
+    return out
+
+
+def conv3d_to_slab_weight(w):
+    """nn.Conv3d weight [co, ci, a, b, c] -> this package's W[(a K + b) K + c, ci, co] (rpn.py; K = 1, 2 or 3)."""
+    co, ci = w.shape[:2]
+    return w.permute(2, 3, 4, 1, 0).reshape(-1, ci, co)
+
+
+def slab_to_conv3d_weight(W, k):
+    """The inverse of `conv3d_to_slab_weight` for a K^3 kernel."""
+    _, ci, co = W.shape
+    return W.reshape(k, k, k, ci, co).permute(4, 3, 0, 1, 2)
+
+
+BOX_BUCKET = 32
+
+
+class DenseClassBranch(nn.Module):
+    """forward(volume_slab [B X Y Z, feature_channels], size (X, Y, Z), batch, boxes) -> (class_scores [R, num_classes] fp32,
+    (bbox_tensor [R, 2, 3] in cells, boxes per sample, size)): the middle entry is what ClassLossSelector / ClassPredictor read.
+    boxes: list (one per sample) of fp32 [n, 2, 3] (start, stop) boxes in scene units; `stride` scene units per cell.
+    The branch computes in fp32, as ClassBranch does.
+
+    The box count changes every training step and the index structures of a fully active grid depend on its batch, so R is
+    rounded up to a multiple of BOX_BUCKET and ONE Metadata is kept per bucket: the padding boxes' rows enter the first strided
+    convolution as zeros (functional.DenseMaxPoolFunction writes them), their pooled rows are dropped before the linear
+    layers, so their output gradient is zero and they add nothing to any weight gradient; boxes never share a site, so
+    they change no real box's result."""
+
+    def __init__(self, feature_channels, stride, input_channels=32, output_channels=(64, 128), linear_channels=(64,),
+                 num_classes=18, num_units=1, cut_shape=(16, 16, 16)):
+        super().__init__()
+        self.stride, self.num_units = stride, int(num_units)
+        self.cut_shape = tuple(int(c) for c in cut_shape)
+        down = 2 ** (1 + len(output_channels))
+        if any(c % down or c < down for c in self.cut_shape):
+            raise ValueError(f"DenseClassBranch: cut_shape {self.cut_shape} must be a multiple of {down} (max pool 2 and "
+                             f"{len(output_channels)} 2^3/2 convolutions)")
+        self.input_conv_layer = M.Sequential(M.SubmanifoldConvolution(3, feature_channels, input_channels, 1, True),
+                                             units(input_channels, num_units))
+        self.roi_getter = roi.RoiAlign(self.cut_shape, clip_boxes=True, resize_boxes=stride)
+        levels, c = [], input_channels
+        for co in output_channels:
+            levels.append(M.Sequential(M.Convolution(3, c, co, 2, 2, True), units(co, num_units)))
+            c = co
+        self.output_conv_layer = M.Sequential(*levels)
+        self.vectorice_layer = SparseGlobalPool(torch.mean)
+        layers = []
+        for co in tuple(linear_channels) + (num_classes,):
+            layers += [nn.ReLU(inplace=bool(layers)), nn.Linear(c, co)]
+            c = co
+        self.linear_layer = nn.Sequential(*layers)
+        self.num_classes = int(num_classes)
+        self._md = {}                         # (kind, size, batch, device) -> fully active Metadata
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_md"] = {}
+        return d
+
+    def _metadata(self, size, batch, device):
+        from .rpn import fully_active_metadata
+        key = (tuple(int(v) for v in size), int(batch), str(device))
+        md = self._md.get(key)
+        if md is None:
+            md = self._md[key] = fully_active_metadata(key[0], key[1], device)
+        return md
+
+    @staticmethod
+    def bucket(n_boxes):
+        return -(-int(n_boxes) // BOX_BUCKET) * BOX_BUCKET
+
+    def forward(self, volume_slab, size, batch, boxes, metadata=None):
+        """metadata: the volume's fully active Metadata if the caller has it (DenseRpn.volume[3]); else built once and kept."""
+        from . import functional as F
+        from .tensor import SparseConvNetTensor
+        size = tuple(int(v) for v in size)
+        prev = M.set_feature_storage(torch.float32)
+        try:
+            if volume_slab.dtype != torch.float32:
+                volume_slab = volume_slab.float()
+            md = metadata if metadata is not None else self._metadata(size, batch, volume_slab.device)
+            augmented = self.input_conv_layer(SparseConvNetTensor(volume_slab, md, torch.as_tensor(size, dtype=torch.long)))
+            box_slab, selection = self.roi_getter.forward_slab(augmented.features, size, batch, boxes)
+            r = selection[0].shape[0]
+            if r == 0:
+                return volume_slab.new_zeros((0, self.num_classes)), selection
+            rb = self.bucket(r)
+            half = tuple(c // 2 for c in self.cut_shape)
+            pooled = F.DenseMaxPoolFunction.apply(box_slab, r, self.cut_shape, rb)
+            box_md = self._metadata(half, rb, volume_slab.device)
+            x = SparseConvNetTensor(pooled, box_md, torch.as_tensor(half, dtype=torch.long))
+            vectors = self.vectorice_layer(self.output_conv_layer(x))[:r]
+        finally:
+            M.set_feature_storage(prev)
+        return self._linear(vectors), selection
+
+    _linear = ClassBranch._linear
+    named_oracle_params = ClassBranch.named_oracle_params
+
+    def reference_key_map(self):
+        n_lin = len([m for m in self.linear_layer if isinstance(m, nn.Linear)])
+        return dense_reference_key_map(len(self.output_conv_layer), self.num_units, n_lin)
+
+    def load_reference_state_dict(self, state_dict, prefix=None, strict=True):
+        """Load the class-network part of a checkpoint written by the REFERENCE with its dense class network (`class_network.`
+        in InstanceSegmentationNetwork).  nn.Conv3d weights [co, ci, a, b, c] become W[(a K + b) K + c, ci, co].  prefix=None:
+        detected as in ClassBranch.  -> (missing reference keys, unused checkpoint keys under the prefix)."""
+        if prefix is None:
+            tail = "input_conv_layer.0.0.0.weight"
+            cands = [k[:-len(tail)] for k in state_dict if k.endswith(tail)]
+            prefix = next((c for c in cands if c + "linear_layer.1.weight" in state_dict), cands[0] if cands else "")
+        converted = {k: (conv3d_to_slab_weight(v) if k.startswith(prefix) and v.dim() == 5 else v) for k, v in state_dict.items()}
+        return _load_mapped(self.named_oracle_params(), self.reference_key_map(), converted, prefix,
                             ("input_conv_layer.", "output_conv_layer.", "linear_layer."), strict)
 
 

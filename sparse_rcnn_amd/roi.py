@@ -527,3 +527,87 @@ def mask_loss_select(mask_scores, sel: RoiSelection, box_sample_count, batch_spl
         return pred, gt, rows.tolist(), torch.cat(labels_out)
     kr = keep_row.bool()
     return pred[kr], gt[kr], rows[kept].tolist(), torch.cat(labels_out)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Dense RoiAlign (ndsis/modules/roi_select_dense.py:28-141 on csrc/scn_roialign.hip)
+# ------------------------------------------------------------------------------------------------------------------------
+def transform_boxes_interpolation(bbox_batch, spatial_size, clip=True, resize=None):
+    """BBoxTransformerInterpolation.forward (roi_select_bbox_transform.py:50-84): list of fp32 [n_i, 2, 3] boxes ->
+    (bbox_tensor fp32 [R, 2, 3] on the device, per-sample counts, per-box sample index int64 on the host).  The reference's
+    operations in its order, each rounded once: `/ resize` (the Divider, scalar or one value per axis), `+ (-0.5)` (the pixel
+    offset), and with clip `min(., size - 1).clamp(min=0)` (OffsetClipper(-1))."""
+    L.lib()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    counts = [len(b) for b in bbox_batch]
+    # (a Python list, not torch.repeat_interleave: see transform_boxes)
+    assoc = torch.tensor([s for s, c in enumerate(counts) for _ in range(c)], dtype=torch.long)
+    if not sum(counts):
+        return torch.zeros((0, 2, 3), dtype=torch.float32, device=dev), counts, assoc
+    t = torch.cat([b.reshape(-1, 2, 3) for b in bbox_batch]).to(device=dev, dtype=torch.float32)
+    if resize is not None:
+        t = t / torch.as_tensor(resize, dtype=torch.float32, device=dev)
+    t = t + torch.tensor(-0.5, dtype=torch.float32, device=dev)
+    if clip:
+        top = torch.tensor([float(int(s) - 1) for s in spatial_size], dtype=torch.float32, device=dev)
+        t = torch.min(t, top).clamp(min=0)
+    return t.contiguous(), counts, assoc
+
+
+class RoiAlign(torch.nn.Module):
+    """``RoiAlign(extract_shape, padding=None, clip_boxes=False, resize_boxes=None)`` (roi_select_dense.py:28-53), the
+    reference's signature and return value: forward(featuremap [B, C, X, Y, Z], bbox_batch) -> (box_features
+    [R, C, ex, ey, ez], (bbox_tensor, counts, scene_shape)).  A `torch.channels_last_3d` featuremap is used in place (its
+    memory IS the slab [B X Y Z, C]); any other layout is copied once.  box_features is the permuted view of the
+    [R, ex, ey, ez, C] buffer the kernel wrote.
+
+    Only what the reference constructs is built (model.py:523-525: clip_boxes=True, no padding): with clip_boxes=False an
+    unclipped negative coordinate WRAPS in the reference's advanced indexing (index -1 reads the last cell) -- behaviour nobody
+    can want bit for bit -- and its padding path (`RoiAlignInner.pad`) never runs in the reference's configurations; both
+    raise NotImplementedError."""
+
+    def __init__(self, extract_shape, padding=None, clip_boxes=False, resize_boxes=None):
+        super().__init__()
+        if padding is not None:
+            raise NotImplementedError("RoiAlign(padding=...): the reference's padding path (RoiAlignInner.pad) never runs in its "
+                                      "configurations (model.py:523-525 builds RoiAlign without padding); not built")
+        if not clip_boxes:
+            raise NotImplementedError("RoiAlign(clip_boxes=False): unclipped boxes index outside the volume -- negative indices "
+                                      "wrap in the reference -- and the device kernels require coordinates in [0, size - 1]; "
+                                      "the reference only constructs clip_boxes=True (model.py:523-525)")
+        self.extract_shape = tuple(int(e) for e in extract_shape)
+        if len(self.extract_shape) != 3 or any(e < 2 for e in self.extract_shape):
+            raise ValueError("RoiAlign: extract_shape needs three entries >= 2")
+        self.resize_boxes = resize_boxes
+
+    def forward_slab(self, slab, size, batch, bbox_batch):
+        """The same on the channels-last slab [B X Y Z, C] -> (box slab [R ex ey ez, C], (bbox_tensor, counts, size))."""
+        from .functional import RoiAlignFunction
+        size = tuple(int(s) for s in size)
+        bbox_tensor, counts, assoc = transform_boxes_interpolation(bbox_batch, size, True, self.resize_boxes)
+        r = bbox_tensor.shape[0]
+        if r == 0:                                           # no box: no launch
+            return slab.new_zeros((0, slab.shape[1])), (bbox_tensor, counts, size)
+        sample = assoc.to(device=slab.device, dtype=torch.int32)
+        out = RoiAlignFunction.apply(slab, bbox_tensor, sample, int(batch), size, self.extract_shape)
+        return out, (bbox_tensor, counts, size)
+
+    def forward(self, featuremap, bbox_batch):
+        if featuremap.dim() != 5:
+            raise ValueError("RoiAlign: featuremap [B, C, X, Y, Z] required")
+        b, c = featuremap.shape[:2]
+        scene_shape = featuremap.shape[2:]
+        # channels_last_3d: permute(0, 2, 3, 4, 1) is contiguous already and reshape is a view; else one copy
+        slab = featuremap.permute(0, 2, 3, 4, 1).reshape(-1, c)
+        out, (bbox_tensor, counts, _) = self.forward_slab(slab, scene_shape, b, bbox_batch)
+        ex = self.extract_shape
+        box_features = out.view(-1, ex[0], ex[1], ex[2], c).permute(0, 4, 1, 2, 3)
+        return box_features, (bbox_tensor, counts, scene_shape)
+
+    @staticmethod
+    def split(feature_map, split_sections):
+        return torch.split(feature_map, split_sections)
+
+    @staticmethod
+    def select(feature_map, indices):
+        return feature_map[indices]

@@ -80,6 +80,18 @@ REF_ANCHOR_LEVELS_VOXELS = tuple(tuple(tuple(v / REF_VOXEL_M for v in a) for a i
 DEFAULT_ANCHORS = ((12.0, 12.0, 12.0), (24.0, 24.0, 24.0), (48.0, 48.0, 32.0), (96.0, 96.0, 48.0))
 
 
+def fully_active_metadata(size, batch, device):
+    """Metadata of the grid `size` with EVERY site of every sample active, rows in (b, x, y, z) order -- row r is cell r of the
+    channels-last volume [B, X, Y, Z, C].  Depends on the shape only (DenseRpn.dense_metadata and classhead.DenseClassBranch
+    keep what they built)."""
+    from .metadata import Metadata
+    X, Y, Z = (int(v) for v in size)
+    g = torch.stack(torch.meshgrid(torch.arange(batch), torch.arange(X), torch.arange(Y), torch.arange(Z), indexing="ij"),
+                    -1).reshape(-1, 4)
+    coords = g[:, [1, 2, 3, 0]].contiguous().to(torch.int64)          # (x, y, z, batch), batch-major rows
+    return Metadata(3).build_native((X, Y, Z), coords.to(device), batch, 4, 1, 3)
+
+
 class DenseRpn(nn.Module):
     """`DenseRpn(channels, stride)`: SparseToDense -> dilation stack -> AnchorNetworkConv-style head.
     forward(level_tensor) -> (rpn_bbox [B, N, 2, 3] = (position delta, log-size delta), rpn_score [B, N] raw,
@@ -92,14 +104,18 @@ class DenseRpn(nn.Module):
     SPARSE_FIRST = True
 
     def __init__(self, channels, stride=8, width=32, num_dilations=2, anchors=DEFAULT_ANCHORS, autocast_bf16=False, engine=None,
-                 keep_inside=True, allowed_border=0):
-        """keep_inside: return only the anchors that lie inside the scene (+ allowed_border), as the reference's
+                 keep_inside=True, allowed_border=0, keep_volume=False):
+        """keep_volume (off: nothing changes): keep the stack's output volume -- after its last ReLU, before the head -- of the
+        last forward as `self.volume` = (fp32 slab [B X Y Z, width], size, batch, its fully active Metadata): what the
+        reference's dense class branch reads (`class_output_anchor`, model.py:435-437).  Engine "tiles" only.
+        keep_inside: return only the anchors that lie inside the scene (+ allowed_border), as the reference's
         `rpn_bbox_score_splitter` does (anchor.py:103-113,177-197; `allowed_border=0`, scannet_config/run.py:841) -- deltas,
         scores and anchors compacted in anchor order.  The reference's own shape is width 128 / 256 and num_dilations 5
         (run.py:525-536,609): the defaults here are the light stand-in of `--workload cfg3-rpn` (trainstep.py)."""
         super().__init__()
         self.engine = engine
         self.keep_inside, self.allowed_border = bool(keep_inside), float(allowed_border)
+        self.keep_volume, self.volume = bool(keep_volume), None
         self.channels, self.stride, self.width = int(channels), int(stride), int(width)
         self.to_dense = M.SparseToDense(3, self.channels)
         layers, cin = [], self.channels
@@ -118,6 +134,7 @@ class DenseRpn(nn.Module):
     def __getstate__(self):
         d = self.__dict__.copy()                 # (the fully active Metadata objects: device index structures, rebuilt on use)
         d["_dense_md"], d["_anchor_cache"], d["_flag_host"] = {}, {}, {}
+        d["volume"] = None
         return d
 
     def anchors_for(self, shape, device):
@@ -164,15 +181,10 @@ class DenseRpn(nn.Module):
     def dense_metadata(self, size, batch, device):
         """Metadata of the grid `size` with EVERY site of every sample active, rows in (b, x, y, z) order -- row r is cell
         r of the channels-last volume [B, X, Y, Z, C].  Depends on the shape only: built once, kept."""
-        from .metadata import Metadata
         key = (tuple(size), int(batch), str(device))
         md = self._dense_md.get(key)
         if md is None:
-            X, Y, Z = size
-            g = torch.stack(torch.meshgrid(torch.arange(batch), torch.arange(X), torch.arange(Y), torch.arange(Z), indexing="ij"),
-                            -1).reshape(-1, 4)
-            coords = g[:, [1, 2, 3, 0]].contiguous().to(torch.int64)          # (x, y, z, batch), batch-major rows
-            md = self._dense_md[key] = Metadata(3).build_native(size, coords.to(device), batch, 4, 1, 3)
+            md = self._dense_md[key] = fully_active_metadata(size, batch, device)
         return md
 
     def _forward_tiles(self, level_tensor):
@@ -213,6 +225,8 @@ class DenseRpn(nn.Module):
         x = x.float()
         if relu_in:
             x = F.ReLUFunction.apply(x)
+        if self.keep_volume:
+            self.volume = (x, size, B, dmd)
         Wh = self.head.weight.reshape(self.head.out_channels, self.head.in_channels).t()
         raw = F.NetworkInNetworkFunction.apply(x, Wh, self.head.bias)           # [B X Y Z, A * 7]: spatial-major, anchor-minor
         out = self._finish(raw.view(B, -1, 7), size)
@@ -229,6 +243,8 @@ class DenseRpn(nn.Module):
     def forward(self, level_tensor):
         if (self.engine or self.ENGINE) == "tiles" and level_tensor.features.is_cuda:
             return self._forward_tiles(level_tensor)
+        if self.keep_volume:
+            raise L.ScnError("DenseRpn(keep_volume=True) keeps the channels-last slab of engine 'tiles'; engine 'miopen' has none")
         dense = self.to_dense(level_tensor)                  # [B, C, X', Y', Z'] (bf16 when the slab is bf16-stored)
         if self.autocast_bf16:
             with torch.autocast("cuda", dtype=torch.bfloat16):
@@ -275,10 +291,17 @@ class MultiLevelRpn(nn.Module):
     levels: [(channels, stride, width, anchors [A, 3] in voxels)];  forward(level_tensors) -> (rpn_bbox [B, N, 2, 3],
     rpn_score [B, N], anchors [N, 2, 3]) over the inside anchors of all levels."""
 
-    def __init__(self, levels, num_dilations=5, autocast_bf16=False, engine=None, allowed_border=0):
+    def __init__(self, levels, num_dilations=5, autocast_bf16=False, engine=None, allowed_border=0, keep_volume=False,
+                 class_output_index=0):
+        """keep_volume / class_output_index (off: nothing changes): the level `class_output_index` keeps its stack's output
+        volume (DenseRpn(keep_volume=True)), read back as `self.volume`; 0 is the reference's index with segmentation
+        (scannet_config/run.py:605-607)."""
         super().__init__()
+        self.class_output_index = int(class_output_index)
         self.levels = nn.ModuleList(DenseRpn(c, stride, width, num_dilations, tuple(map(tuple, a)), autocast_bf16, engine,
-                                             keep_inside=False) for (c, stride, width, a) in levels)
+                                             keep_inside=False,
+                                             keep_volume=bool(keep_volume) and i == self.class_output_index % len(levels))
+                                    for i, (c, stride, width, a) in enumerate(levels))
         self.allowed_border = float(allowed_border)
         self._cache = {}
 
@@ -286,6 +309,10 @@ class MultiLevelRpn(nn.Module):
         d = self.__dict__.copy()
         d["_cache"] = {}
         return d
+
+    @property
+    def volume(self):
+        return self.levels[self.class_output_index].volume
 
     def forward(self, level_tensors):
         outs = [rpn(t) for rpn, t in zip(self.levels, level_tensors)]

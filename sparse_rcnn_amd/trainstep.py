@@ -93,6 +93,9 @@ class SparseStepModel(torch.nn.Module):
         anchor levels with 5 x 128 / 5 x 256 stacks, rpn.MultiLevelRpn).
         with_class: the reference's class branch (classhead.ClassBranch) on the coarsest RPN level of the encoder -- the
         reference's `class_output_index=-1` on a main network that ends at its last anchor level (run.py:581-584, 605-608).
+        with_class="dense": the reference's DENSE class branch (classhead.DenseClassBranch; run.py:340 `dense_class = True`)
+        on the dense volume the RPN's dilation stack of anchor level 0 produces (`class_output_anchor`, run.py:603-607): the RPN
+        keeps that volume (keep_volume) and the class loss's gradient reaches the stack.
         with_segmentation: the reference's segmentation head (classhead.SegmentationHead, 20 classes) on the backbone output.
         Both are constructed AFTER the other modules: under one seed the others start from the same values with or without."""
         super().__init__()
@@ -107,21 +110,27 @@ class SparseStepModel(torch.nn.Module):
             self.rpn_levels = (2, 3)
             self.rpn = MultiLevelRpn([(channels[2], 4, 128, REF_ANCHOR_LEVELS_VOXELS[0]),
                                       (channels[3], 8, 256, REF_ANCHOR_LEVELS_VOXELS[1])], num_dilations=5,
-                                     autocast_bf16=bool(storage))
+                                     autocast_bf16=bool(storage), **(dict(keep_volume=True) if with_class == "dense" else {}))
             self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:847-853: 1024 / 256 / 0.5
         elif with_rpn:               # one anchor path on the coarsest level (run.py:524: num_anchor_pathes = 1), stride 2^(L-1)
             from .rpn import DenseRpn, RoiSelector
             self.rpn_levels = (len(channels) - 1,)
-            self.rpn = DenseRpn(channels[-1], stride=2 ** (len(channels) - 1), autocast_bf16=bool(storage))
+            self.rpn = DenseRpn(channels[-1], stride=2 ** (len(channels) - 1), autocast_bf16=bool(storage),
+                                **(dict(keep_volume=True) if with_class == "dense" else {}))
             self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:848-850 with ~64 proposals kept per scene
         self.class_branch = self.segmentation = None
         self.class_level = None
         if with_class:
             if self.rpn is None:
                 raise ValueError("with_class needs an RPN (the class branch reads its coarsest level)")
-            from .classhead import ClassBranch
-            self.class_level = self.rpn_levels[-1]
-            self.class_branch = ClassBranch(channels[self.class_level], 2 ** self.class_level)
+            from .classhead import ClassBranch, DenseClassBranch
+            if with_class == "dense":
+                src = self.rpn.levels[self.rpn.class_output_index] if hasattr(self.rpn, "levels") else self.rpn
+                self.class_level = self.rpn_levels[self.rpn.class_output_index if hasattr(self.rpn, "levels") else 0]
+                self.class_branch = DenseClassBranch(src.width, src.stride)
+            else:
+                self.class_level = self.rpn_levels[-1]
+                self.class_branch = ClassBranch(channels[self.class_level], 2 ** self.class_level)
         if with_segmentation:
             from .classhead import SegmentationHead
             self.segmentation = SegmentationHead(channels[0], 20)
@@ -130,12 +139,23 @@ class SparseStepModel(torch.nn.Module):
         lv = [interims[i] for i in self.rpn_levels]
         return self.rpn(lv if len(lv) > 1 else lv[0])
 
+    def run_class(self, interims, boxes):
+        """The class branch on `boxes`: the sparse arm reads the encoder level, the dense arm the volume the RPN kept in the
+        same forward (run_rpn comes first)."""
+        from .classhead import DenseClassBranch
+        if isinstance(self.class_branch, DenseClassBranch):
+            if self.rpn.volume is None:
+                raise L.ScnError("the dense class branch reads the RPN's kept volume: run_rpn first")
+            slab, size, batch, md = self.rpn.volume
+            return self.class_branch(slab, size, batch, boxes, metadata=md)
+        return self.class_branch(interims[self.class_level], boxes)
+
 
 class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
-                 class_loss=False, segmentation_loss=False, batches=None, step_group=True):
+                 class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False):
         """step_group: run the fp32 weight gradients of a step as one grid per kernel variant after the last backward pass
         (executor.step_weight_gradients; one rank, no gradient buckets).  It keeps every stage's workspaces and unit slabs alive
         until then -- the cfg2 step's working set grows from 1.04 to 2.03 GB -- so False is the way to fit a scene that only fits
@@ -144,7 +164,7 @@ class SceneStep:
         (`sample.collate` of `sample.convert_sample` outputs: the reference's batch dict) that take the place of the synthetic
         scenes -- coordinates, features, spatial size, splits, ground-truth boxes, labels, packed instance masks and per-point
         segmentation labels all come from the batch, so every loss, predict() and evaluate() run on converted data.  The
-        spatial size must be a multiple of 2^(levels - 1) of the workload's network, times 4 with class_loss (convert with
+        spatial size must be a multiple of 2^(levels - 1) of the workload's network, times 4 with class_loss on the sparse arm (convert with
         `required_size_factor`: 8, or 32, for the 4-level cfg3-rpn), else ValueError; instance labels must lie in 0 .. 17 and segmentation labels in 0 .. 19 or be -100.
         rpn_loss (the `-rpn` workloads only): train the RPN on the reference's RPN loss (loss.RpnLoss with
         BatchwiseBboxTargetSelector(0.35, 0.15, 1/8), sigma 2; scannet_config/run.py:359-368,876-884) against the scene's
@@ -163,6 +183,10 @@ class SceneStep:
         overlap descriptions the mask selector computed when both are on (model.py:170-183) -- and appends every ground-truth
         box; the branch runs on those boxes, loss.ClassLossSelector + loss.ClassLoss give `.class_losses` (on the device),
         back-propagated with 1 / batches_per_step.
+        dense_class (with class_loss): the class branch is the reference's DENSE one (classhead.DenseClassBranch, run.py:340
+        `dense_class = True`): RoiAlign to 16^3 out of the volume the RPN's dilation stack produced, so the class loss trains
+        that stack too; everything around it (selector, ClassLossSelector, ClassLoss, predict(), evaluate()) is the same.  A
+        batch's spatial size then needs no factor beyond the backbone's.  False: the sparse arm, unchanged.
         segmentation_loss (the workloads with boxes: cfg3, cfg3-rpn, ref-crop-rpn): add the reference's segmentation head
         (classhead.SegmentationHead, 20 classes) on the backbone output and train it on loss.CrossEntropyLoss against
         synthetic.make_segmentation of the scene's instances.  Its gradient REPLACES the seeded N(0, 1) gradient on the
@@ -187,6 +211,8 @@ class SceneStep:
             raise ValueError("mask_loss=True needs an RPN in the step (the -rpn workloads)")
         if class_loss and not workload.endswith("-rpn"):
             raise ValueError("class_loss=True needs an RPN in the step (the -rpn workloads)")
+        if dense_class and not class_loss:
+            raise ValueError("dense_class=True chooses the class branch's arm: it needs class_loss=True")
         if segmentation_loss and not nb:
             raise ValueError("segmentation_loss=True needs a workload with boxes (cfg3, cfg3-rpn, ref-crop-rpn): the labels "
                              "come from the scene's instances")
@@ -236,8 +262,10 @@ class SceneStep:
         self._scenes = []
         self.from_batches = batches is not None
         # level constraint on a batch's spatial size: every 2^3/2 convolution halves an even size -- levels - 1 in the backbone,
-        # two more in the class branch, which cuts its boxes out of the coarsest level's grid
-        self._size_factor = 2 ** (len(self.channels) - 1) * (4 if class_loss else 1)
+        # two more in the SPARSE class branch, which cuts its boxes out of the coarsest level's grid (the dense one resamples
+        # every box to its own 16^3 grid: the volume's stride is one of the backbone's)
+        self.dense_class = bool(dense_class)
+        self._size_factor = 2 ** (len(self.channels) - 1) * (4 if class_loss and not dense_class else 1)
         for k in range(self.batches_per_step):
             if self.from_batches:
                 self._scenes.append(self._scene_from_batch(batches[k], k))
@@ -260,7 +288,8 @@ class SceneStep:
         if self.segmentation_loss and not self.n_boxes:
             raise ValueError("segmentation_loss=True needs boxes (n_boxes > 0)")
         self.model = SparseStepModel(self.channels, bool(self.n_boxes), storage, rpn_kind, self.n_boxes,
-                                     batchnorm=workload.endswith("-bn"), with_class=self.class_loss,
+                                     batchnorm=workload.endswith("-bn"),
+                                     with_class="dense" if self.dense_class else self.class_loss,
                                      with_segmentation=self.segmentation_loss).to(self.device)
         if self.with_rpn:
             self._init_rpn()
@@ -527,7 +556,7 @@ class SceneStep:
                     overlaps, cboxes, cdescs = self.class_selector.select(proposals, sc["gt_dev"])
                 else:
                     cboxes, cdescs = self.class_selector(overlaps)
-                class_scores, csel = m.class_branch(m.backbone.unet.interims[m.class_level], list(cboxes))
+                class_scores, csel = m.run_class(m.backbone.unet.interims, list(cboxes))
                 if self.keep_class_grads:
                     class_scores.retain_grad()
                 sel_scores, sel_labels = self.class_loss_selector(class_scores, csel, cdescs, overlaps, sc["gt_label"])
@@ -614,7 +643,7 @@ class SceneStep:
             rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
             _, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
             boxes = list(boxes)
-            class_scores, csel = m.class_branch(interims[m.class_level], boxes)
+            class_scores, csel = m.run_class(interims, boxes)
             class_indices, class_prob, class_raw = ClassPredictor()(class_scores, csel)
             scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
             logits, (sel, counts, splits) = m.mask(scene, out, boxes)
@@ -661,11 +690,11 @@ class SceneStep:
                 rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
                 roi_score, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
                 roi_score, boxes = list(roi_score), list(boxes)
-                class_scores, csel = m.class_branch(interims[m.class_level], boxes)
+                class_scores, csel = m.run_class(interims, boxes)
                 class_indices, _, class_raw = ClassPredictor()(class_scores, csel)
                 gt_boxes, gt_label = sc["gt_dev"], sc["gt_label"]
                 if eval_on_gt:
-                    gt_class_scores, gcsel = m.class_branch(interims[m.class_level], gt_boxes)
+                    gt_class_scores, gcsel = m.run_class(interims, gt_boxes)
                     gt_class, _, gt_class_raw = ClassPredictor()(gt_class_scores, gcsel)
                 scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
                 logits, (sel, counts, splits) = m.mask(scene, out, boxes)
@@ -774,9 +803,14 @@ class SceneStep:
         elif self.n_gt:
             s += f"; ground truth: the first {self.n_gt} synthetic boxes per sample"
         if self.class_loss:
-            s += ("; the class branch (SubM1 + 1 unit @32 on the stride-" + str(self.model.class_branch.stride) + " level, sparse "
-                  "ROI cut, 2^3/2 conv + unit @64 and @128, mean pool, Linear 128-64-18) trains on the reference's class loss: "
-                  "TrainSelector(0.1, 0, (32, 0, True)) draws <= 32 proposals with IoU >= 0.1 per sample and appends every "
+            cb = self.model.class_branch
+            s += (("; the DENSE class branch (1^3 conv + 1 unit @32 on the stride-" + str(cb.stride) + " volume of the RPN's dilation "
+                   "stack, RoiAlign to " + "x".join(map(str, cb.cut_shape)) + " (scn_roialign.hip), max pool 2 without clamp, "
+                   "2^3/2 conv + unit @64 and @128 on fully active box grids, mean pool, Linear 128-64-18) trains the stack too, "
+                   "on the reference's class loss: ") if self.dense_class else
+                  ("; the class branch (SubM1 + 1 unit @32 on the stride-" + str(cb.stride) + " level, sparse "
+                   "ROI cut, 2^3/2 conv + unit @64 and @128, mean pool, Linear 128-64-18) trains on the reference's class loss: "))
+            s += ("TrainSelector(0.1, 0, (32, 0, True)) draws <= 32 proposals with IoU >= 0.1 per sample and appends every "
                   "ground-truth box, cross entropy against the associated instance's label (scn_xent.hip)")
         if self.segmentation_loss:
             s += ("; the segmentation head (SubM 1^3 to 20 classes, one row per point) trains on the reference's segmentation "
