@@ -72,7 +72,8 @@ extern "C" {
  *      additive within 5: + scn_sample_stats, scn_sample_pack (147 entry points);
  *      additive within 5: + scn_wgrad_step_begin / _hold / _flush / _discard, scn_wgrad_group_counts; switch
  *      SCN_EXEC_GROUP_STEP (152 entry points);
- *      additive within 5: + scn_roialign_fwd / _bwd, scn_dense_maxpool_fwd / _bwd (156 entry points) */
+ *      additive within 5: + scn_roialign_fwd / _bwd, scn_dense_maxpool_fwd / _bwd (156 entry points);
+ *      additive within 5: + scn_anchor_up_fwd / _bwd (158 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -1061,6 +1062,30 @@ int scn_dense_maxpool_fwd(const float* X, int64_t n_boxes, const int64_t* extent
                           scn_stream_t stream);
 int scn_dense_maxpool_bwd(const float* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host, int c,
                           float* dX, scn_stream_t stream);
+
+/* ---- the permutation half of the reference's up-sampling RPN heads (ndsis/modules/anchor_network.py:127-219
+ * AnchorNetworkUpsample; anchor.py:167-192 rpn_permuter + rpn_bbox_score_splitter) -- csrc/scn_anchor_up.hip, fp32 ----
+ * One call per anchor level.  P fp32 [batch X Y Z][ncol]: the level's channels-last slab times the packed head weights, row
+ * ((b X + x) Y + y) Z + z; size_host = (X, Y, Z), int64 [3] on the HOST.  groups_host int64 [n_groups][6] on the HOST, per
+ * group (s0, s1, s2, A_g, first column, first index in the all-anchor order): the group's transposed convolution has kernel =
+ * stride = (s0, s1, s2) and A_g anchors; its s0 s1 s2 A_g 7 columns start at `first column` -- the groups' columns tile
+ * [0, ncol) in group order -- and column first + ((a s1 + b) s2 + c) (A_g 7) + anchor 7 + k holds component k (0..5 box
+ * deltas, 6 the score) of `anchor` at the fine cell (x s0 + a, y s1 + b, z s2 + c).  The group's anchors take the
+ * all-anchor indices first index + fine cell * A_g + anchor, fine cells row-major over (X s0, Y s1, Z s2), z fastest.
+ * dest int32 [n_all] on the device, shared by every sample and every level: the anchor's rank among the n_inside anchors
+ * inside the scene, -1 outside (any other value outside [0, n_inside) counts as -1).
+ * scn_anchor_up_fwd: rpn_bbox fp32 [batch][n_inside][2][3] and rpn_score fp32 [batch][n_inside]; the level writes the
+ * records of its own inside anchors and leaves every other byte alone.  1 launch (none for batch == 0 or n_inside == 0).
+ * scn_anchor_up_bwd: dP fp32 [batch X Y Z][ncol], EVERY element written exactly once: the incoming value where dest >= 0, 0
+ * where it is -1; d_bbox / d_score may be NULL (= zeros).  A gather without atomics: reruns give identical bits.  1 launch.
+ * Both only copy.  A bad group table, size or count returns SCN_EINVAL before anything is launched.  Neither waits for the host. */
+#define SCN_ANCHOR_UP_MAX_GROUPS 16
+int scn_anchor_up_fwd(const float* P, int batch, const int64_t* size_host, int ncol, const int64_t* groups_host, int n_groups,
+                      const int32_t* dest, int64_t n_all, int64_t n_inside, float* rpn_bbox, float* rpn_score,
+                      scn_stream_t stream);
+int scn_anchor_up_bwd(const float* d_bbox, const float* d_score, int batch, const int64_t* size_host, int ncol,
+                      const int64_t* groups_host, int n_groups, const int32_t* dest, int64_t n_all, int64_t n_inside,
+                      float* dP, scn_stream_t stream);
 
 #ifdef __cplusplus
 }

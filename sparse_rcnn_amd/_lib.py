@@ -178,6 +178,8 @@ _SIGS = {
     "scn_roialign_bwd": (C.c_int, [p, p, p, i64, i32, C.POINTER(i64), i32, C.POINTER(i64), p, p]),
     "scn_dense_maxpool_fwd": (C.c_int, [p, i64, C.POINTER(i64), i32, p, p, p]),
     "scn_dense_maxpool_bwd": (C.c_int, [p, p, i64, C.POINTER(i64), i32, p, p]),
+    "scn_anchor_up_fwd": (C.c_int, [p, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, p, i64, i64, p, p, p]),
+    "scn_anchor_up_bwd": (C.c_int, [p, p, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, p, i64, i64, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -193,6 +195,7 @@ PYRAMID_FUSED = 4
 PYRAMID_DESC_LEN = 8 + PYRAMID_MAX_LEVELS * PYRAMID_LEVEL_STRIDE
 COLSUM_BLOCKS = 512
 SAMPLE_MAX_INSTANCES = 1023      # SCN_SAMPLE_MAX_INSTANCES
+ANCHOR_UP_MAX_GROUPS = 16        # SCN_ANCHOR_UP_MAX_GROUPS
 
 
 class ScnError(RuntimeError):

@@ -1299,3 +1299,52 @@ class DenseMaxPoolFunction(torch.autograd.Function):
         dX = _new((r * per * 8, c), dY)
         L.check(L.lib().scn_dense_maxpool_bwd(L.ptr(dY), L.ptr(arg), r, _host3(extent), c, L.ptr(dX), L.stream()))
         return dX, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------------
+# The permutation half of the reference's up-sampling RPN heads (anchor_network.py:127-219; scn_anchor_up.hip)
+# ------------------------------------------------------------------------------------------------------
+class AnchorUpFunction(torch.autograd.Function):
+    """forward(plan, batch, P_0, ..., P_{L-1}) -> (rpn_bbox [B, N_in, 2, 3], rpn_score [B, N_in]) over the inside anchors of all
+    levels: P_l [B X_l Y_l Z_l, Ncol_l] is level l's slab times its packed head weights; one scn_anchor_up_fwd per level writes
+    the level's records straight into the two outputs (every inside anchor belongs to exactly one level).  `plan`
+    (rpn.AnchorNetworkUpsample builds and keeps it per scene shape): .n_all, .n_inside, .dest int32 [n_all] on the
+    device, .levels = [(size (X, Y, Z), ncol, group table int64 [G][6] on the host, G)].  The backward is one
+    scn_anchor_up_bwd per level: dP_l written once everywhere, 0 at the anchors outside the scene, an absent gradient is zeros."""
+
+    @staticmethod
+    def forward(ctx, plan, batch, *Ps):
+        if len(Ps) != len(plan.levels):
+            raise ValueError(f"AnchorUp: {len(plan.levels)} levels planned, {len(Ps)} given")
+        Ps = [_f32(P) for P in Ps]
+        B = int(batch)
+        for P, (size, ncol, _, _) in zip(Ps, plan.levels):
+            if tuple(P.shape) != (B * size[0] * size[1] * size[2], ncol):
+                raise ValueError(f"AnchorUp: P {tuple(P.shape)} is not [{B} x {size[0]} x {size[1]} x {size[2]}, {ncol}]")
+        if plan.dest.dtype != torch.int32 or plan.dest.shape[0] != plan.n_all or plan.dest.device != Ps[0].device:
+            raise ValueError("AnchorUp: dest int32 [n_all] on the slabs' device required")
+        rpn_bbox = _new((B, plan.n_inside, 2, 3), Ps[0])
+        rpn_score = _new((B, plan.n_inside), Ps[0])
+        for P, (size, ncol, groups, n_groups) in zip(Ps, plan.levels):
+            L.check(L.lib().scn_anchor_up_fwd(L.ptr(P), B, _host3(size), ncol, groups, n_groups, L.ptr(plan.dest), plan.n_all,
+                                              plan.n_inside, L.ptr(rpn_bbox), L.ptr(rpn_score), L.stream()))
+        ctx.plan, ctx.batch = plan, B
+        ctx.set_materialize_grads(False)
+        return rpn_bbox, rpn_score
+
+    @staticmethod
+    def backward(ctx, d_bbox, d_score):
+        plan = ctx.plan
+        d_bbox = None if d_bbox is None else _f32(d_bbox)
+        d_score = None if d_score is None else _f32(d_score)
+        B = ctx.batch
+        out = []
+        for i, (size, ncol, groups, n_groups) in enumerate(plan.levels):
+            if not ctx.needs_input_grad[2 + i]:
+                out.append(None)
+                continue
+            dP = torch.empty((B * size[0] * size[1] * size[2], ncol), dtype=torch.float32, device=plan.dest.device)
+            L.check(L.lib().scn_anchor_up_bwd(L.ptr(d_bbox), L.ptr(d_score), B, _host3(size), ncol, groups, n_groups,
+                                              L.ptr(plan.dest), plan.n_all, plan.n_inside, L.ptr(dP), L.stream()))
+            out.append(dP)
+        return (None, None, *out)

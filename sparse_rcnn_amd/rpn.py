@@ -5,6 +5,9 @@ head"): the proposals of a step come out of the SAME forward that feeds the mask
         --dilation stack (Conv3d 3^3 + ReLU; engine "tiles", the default: this library's tile kernels on a fully active grid;
           engine "miopen": torch.nn.functional.conv3d -- SURVEY §2 row 8 leaves the dense RPN to PyTorch)-->
         --1x1x1 head--> per anchor 6 box deltas + 1 score          (anchor_network.py:73-124 `AnchorNetworkConv`)
+          or, MultiLevelRpn(extra_stride_levels=...), the reference's committed choice: per level one transposed convolution
+          (kernel = stride) per group of anchors, on a grid finer than the level's (anchor_network.py:127-219
+          `AnchorNetworkUpsample`): one row GEMM per level + the scatter of scn_anchor_up.hip
         --anchors that leave the scene dropped: deltas / scores / anchors compacted (anchor.py:103-113, :177-197)-->
         --RoiSelector: detach, sigmoid, top-k (scn_topk_boxes), decode + clip the selected anchors, greedy NMS (scn_nms_bits), keep `post`-->
         list of fp32 boxes [n_i, 2, 3] per sample                    (proposal_selector.py:23-89; bbox.py:139-165,367-398)
@@ -25,6 +28,7 @@ Two engines evaluate those layers (same parameters, same mathematics):
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -76,6 +80,46 @@ REF_VOXEL_M = 0.0375
 REF_ANCHOR_LEVELS_VOXELS = tuple(tuple(tuple(v / REF_VOXEL_M for v in a) for a in lv)
                                  for lv in (REF_RAW_ANCHORS_M[:3], REF_RAW_ANCHORS_M[3:]))
 
+
+def strides_anchors(anchors, basis, min=1, max=None, order=None):
+    """`get_strides_anchors` (scannet_config/network.py:24-33): the extra stride of an anchor is round(basis / its edges),
+    clipped to [min, max]; anchors with the same stride form a group.  anchors [A, 3] -> (the groups' anchors, a list of
+    [A_g, 3] arrays in the order of the sorted unique strides, strides int64 [G, 3], order: the position of every grouped anchor
+    in `anchors`).  The strides, the groups and their members are a function of the anchors.  The order of the members INSIDE
+    a group is not: the reference takes numpy's default argsort of the group index, which is not a stable sort (numpy's
+    vectorised sort puts the two anchors of the reference's group (1, 1, 1) of level 1 in descending order and leaves the two
+    of (1, 1, 3) ascending), and so does this function unless `order` fixes it."""
+    anchors = np.asarray(anchors, dtype=np.float64)
+    inverse_raw = (basis / anchors).round().astype(np.int64).clip(min=min, max=max)
+    strides, inverse, counts = np.unique(inverse_raw, return_inverse=True, return_counts=True, axis=0)
+    inverse = inverse.reshape(-1)
+    if order is None:
+        order = np.argsort(inverse)
+    else:
+        order = np.asarray(order, dtype=np.int64)
+        if sorted(order.tolist()) != list(range(len(anchors))) or (np.diff(inverse[order]) < 0).any():
+            raise ValueError("strides_anchors: `order` does not list the anchors group by group")
+    return np.split(anchors[order], np.cumsum(counts[:-1]), axis=0), strides, order
+
+
+# the member order of the reference's groups as its configuration produces it (what a checkpoint's `A_g * 7` output channels
+# follow): recorded from a run of scannet_config/network.py, fixed here because numpy's default sort does not promise it
+REF_UPSAMPLE_ANCHOR_ORDER = ((1, 2, 0), (10, 9, 7, 8, 6, 5, 4, 3, 0, 2, 1))
+
+
+def _ref_upsample_tables():
+    strides, groups = [], []
+    for lv, basis, order in zip((REF_RAW_ANCHORS_M[:3], REF_RAW_ANCHORS_M[3:]), (0.6, 1.2), REF_UPSAMPLE_ANCHOR_ORDER):  # network.py:36-41
+        g, s, _ = strides_anchors(lv, basis, order=order)
+        strides.append(tuple(tuple(int(v) for v in row) for row in s))
+        groups.append(tuple(tuple(tuple(float(v) for v in a) for a in (np.asarray(grp) / REF_VOXEL_M)) for grp in g))
+    return tuple(strides), tuple(groups)
+
+
+# the reference's up-sampling heads (run.py:532-537, 830-833): per anchor level the extra strides of its groups and the groups'
+# anchors in voxels -- level 0: (1,1,1) x 2 anchors, (2,2,1) x 1; level 1: nine groups, 11 anchors
+REF_EXTRA_STRIDE_LEVELS, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS = _ref_upsample_tables()
+
 # anchor edge lengths in voxels at the one anchor level (stride 8); the synthetic boxes of cfg 3 have edges 8-96
 DEFAULT_ANCHORS = ((12.0, 12.0, 12.0), (24.0, 24.0, 24.0), (48.0, 48.0, 32.0), (96.0, 96.0, 48.0))
 
@@ -104,8 +148,10 @@ class DenseRpn(nn.Module):
     SPARSE_FIRST = True
 
     def __init__(self, channels, stride=8, width=32, num_dilations=2, anchors=DEFAULT_ANCHORS, autocast_bf16=False, engine=None,
-                 keep_inside=True, allowed_border=0, keep_volume=False):
-        """keep_volume (off: nothing changes): keep the stack's output volume -- after its last ReLU, before the head -- of the
+                 keep_inside=True, allowed_border=0, keep_volume=False, with_head=True):
+        """with_head=False (MultiLevelRpn with up-sampling heads): no 1x1 head is constructed and `forward` hands over the
+        stack's output slab, (fp32 slab [B X Y Z, width], size, batch, pinned cell flags); engine "tiles" only.
+        keep_volume (off: nothing changes): keep the stack's output volume -- after its last ReLU, before the head -- of the
         last forward as `self.volume` = (fp32 slab [B X Y Z, width], size, batch, its fully active Metadata): what the
         reference's dense class branch reads (`class_output_anchor`, model.py:435-437).  Engine "tiles" only.
         keep_inside: return only the anchors that lie inside the scene (+ allowed_border), as the reference's
@@ -125,7 +171,8 @@ class DenseRpn(nn.Module):
         self.stack = nn.Sequential(*layers)
         self.register_buffer("anchor_sizes", torch.tensor(anchors, dtype=torch.float32))
         self.n_anchors = len(anchors)
-        self.head = nn.Conv3d(cin, self.n_anchors * 7, 1)    # anchor_network.py:88-92: num_anchors x (2 x num_dims + 1)
+        # anchor_network.py:88-92: num_anchors x (2 x num_dims + 1)
+        self.head = nn.Conv3d(cin, self.n_anchors * 7, 1) if with_head else None
         self.autocast_bf16 = bool(autocast_bf16)
         self._anchor_cache = {}
         self._dense_md = {}
@@ -227,22 +274,30 @@ class DenseRpn(nn.Module):
             x = F.ReLUFunction.apply(x)
         if self.keep_volume:
             self.volume = (x, size, B, dmd)
+        if self.head is None:
+            return x, size, B, self._flags_to_host(flag)
         Wh = self.head.weight.reshape(self.head.out_channels, self.head.in_channels).t()
         raw = F.NetworkInNetworkFunction.apply(x, Wh, self.head.bias)           # [B X Y Z, A * 7]: spatial-major, anchor-minor
         out = self._finish(raw.view(B, -1, 7), size)
         # scn_cell_map's count of rows outside the volume (a level tensor whose spatial_size / batch disagrees with its
         # coordinates): copied to pinned memory behind the launch, carried on rpn_score, read by RoiSelector.finish after the
         # host wait it makes anyway
-        fh = self._flag_host.get(str(feats.device))
-        if fh is None:
-            fh = self._flag_host[str(feats.device)] = torch.zeros(1, dtype=torch.int32).pin_memory()
-        fh.copy_(flag, non_blocking=True)
-        out[1].cell_flags = [fh]
+        out[1].cell_flags = [self._flags_to_host(flag)]
         return out
+
+    def _flags_to_host(self, flag):
+        fh = self._flag_host.get(str(flag.device))
+        if fh is None:
+            fh = self._flag_host[str(flag.device)] = torch.zeros(1, dtype=torch.int32).pin_memory()
+        fh.copy_(flag, non_blocking=True)
+        return fh
 
     def forward(self, level_tensor):
         if (self.engine or self.ENGINE) == "tiles" and level_tensor.features.is_cuda:
             return self._forward_tiles(level_tensor)
+        if self.head is None:
+            raise L.ScnError("DenseRpn(with_head=False) hands over the channels-last slab of engine 'tiles' on the MI355X "
+                             "(no CPU fallback)")
         if self.keep_volume:
             raise L.ScnError("DenseRpn(keep_volume=True) keeps the channels-last slab of engine 'tiles'; engine 'miopen' has none")
         dense = self.to_dense(level_tensor)                  # [B, C, X', Y', Z'] (bf16 when the slab is bf16-stored)
@@ -280,28 +335,210 @@ def decode_boxes(anchors, deltas, scene_shape=None):
     return boxes
 
 
+class _UpPlan:
+    """What AnchorNetworkUpsample keeps per (scene shape, level sizes, device): a function of those alone."""
+    __slots__ = ("n_all", "n_inside", "dest", "levels", "anchors", "inside_cpu")
+
+
+class _Operation(nn.Module):
+    """Name holder: the reference wraps its heads as ConcatOutputListList(ZipApply(ModuleMap(...))), which spells their
+    parameters `rpn_net_levels.operation.{level}.{group}.weight` / `.bias` (custom_container.py:24-26,87-99)."""
+
+    def __init__(self, level_groups):
+        super().__init__()
+        self.operation = nn.ModuleList(nn.ModuleList(g) for g in level_groups)
+
+
+class AnchorNetworkUpsample(nn.Module):
+    """The reference's up-sampling RPN heads (ndsis/modules/anchor_network.py:127-219): per anchor level one
+    `ConvTranspose3d(C, A_g * 7, kernel = stride = extra_stride_g)` per group g of anchors that share an extra stride, so that a
+    group's anchors sit on the level's grid refined by that stride (combined stride conv_stride / extra_stride, fractional).
+    raw_anchor_levels: per level the groups' anchors [A_g, 3] in voxels; conv_stride_levels: per level the stride of its
+    volume (a number or one per axis); channels_levels: per level C; extra_stride_levels: per level [G, 3] integers.
+    Parameters have the reference's shapes ([C, A_g * 7, s0, s1, s2], [A_g * 7]), names
+    (`rpn_net_levels.operation.{l}.{g}.*`) and initialisation (nn.ConvTranspose3d's, in the reference's construction order).
+
+    A transposed convolution with kernel = stride has no overlap between taps: level l is ONE row GEMM P = X @ Wm + bias_cols
+    on the level's channels-last slab (functional.NetworkInNetworkFunction; Wm [C, Ncol], column col0_g + ((a s1 + b) s2 + c)
+    (A_g 7) + co = W_g[ci, co, a, b, c], packed per call with permute / reshape / cat so that autograd carries the gradients
+    back to the ConvTranspose3d-shaped parameters) and one scatter into the outputs (functional.AnchorUpFunction,
+    scn_anchor_up.hip).
+
+    forward([(slab [B X Y Z, C], size (X, Y, Z), batch)] per level, scene_shape) -> (rpn_bbox [B, N, 2, 3], rpn_score [B, N],
+    anchors [N, 2, 3] = (centre, size)) over the anchors inside the scene (+ allowed_border), in the reference's order: groups
+    in level order then group order, fine cells row-major with z fastest, the anchor index minor (anchor.py:82-113,171-192)."""
+
+    def __init__(self, raw_anchor_levels, conv_stride_levels, channels_levels, allowed_border=0, *, extra_stride_levels):
+        super().__init__()
+        if not (len(raw_anchor_levels) == len(conv_stride_levels) == len(channels_levels) == len(extra_stride_levels)):
+            raise ValueError("AnchorNetworkUpsample: one entry per level in every argument")
+        heads, self._groups = [], []
+        for anchors_l, stride_l, c, extra_l in zip(raw_anchor_levels, conv_stride_levels, channels_levels, extra_stride_levels):
+            extra_l = np.asarray(extra_l, dtype=np.int64).reshape(-1, 3)
+            if len(anchors_l) != len(extra_l) or not 1 <= len(extra_l) <= L.ANCHOR_UP_MAX_GROUPS:
+                raise ValueError(f"AnchorNetworkUpsample: {len(anchors_l)} anchor groups, {len(extra_l)} extra strides "
+                                 f"(1 .. {L.ANCHOR_UP_MAX_GROUPS} groups per level, one stride each)")
+            conv = np.broadcast_to(np.asarray(stride_l), (3,))
+            combined = conv / extra_l                                   # float64, as create_level_upsampler divides
+            groups = []
+            for g, (a, e) in enumerate(zip(anchors_l, extra_l)):
+                a = torch.as_tensor(np.asarray(a, dtype=np.float64), dtype=torch.float32).reshape(-1, 3)
+                e = tuple(int(v) for v in e)
+                if a.shape[0] < 1 or min(e) < 1:
+                    raise ValueError("AnchorNetworkUpsample: every group needs an anchor and extra strides >= 1")
+                groups.append(dict(extra=e, n_anchors=a.shape[0], raw=a,
+                                   stride=torch.as_tensor(combined[g], dtype=torch.float32)))   # AnchorStorage's cast
+            self._groups.append(groups)
+            heads.append([nn.ConvTranspose3d(int(c), gr["n_anchors"] * 7, gr["extra"], gr["extra"]) for gr in groups])
+        self.rpn_net_levels = _Operation(heads)
+        self.conv_strides = [tuple(int(v) for v in np.broadcast_to(np.asarray(s), (3,))) for s in conv_stride_levels]
+        self.channels_levels = tuple(int(c) for c in channels_levels)
+        self.allowed_border = allowed_border
+        self._cache = {}
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_cache"] = {}
+        return d
+
+    def heads(self):
+        """The ConvTranspose3d modules, level-major."""
+        return [h for lv in self.rpn_net_levels.operation for h in lv]
+
+    @property
+    def ncol_levels(self):
+        return tuple(sum(g["extra"][0] * g["extra"][1] * g["extra"][2] * g["n_anchors"] * 7 for g in lv) for lv in self._groups)
+
+    def all_anchors(self, sizes):
+        """Every anchor of levels of spatial `sizes`, in all-anchor order, fp32 [N_all, 2, 3] on the host
+        (AnchorDescriptionMultiLevel._get_pixelwise_anchors, anchor.py:127-146: centres (arange + 0.5) * stride in fp32)."""
+        out = []
+        for groups, size in zip(self._groups, sizes):
+            for g in groups:
+                ranges = [(torch.arange(int(n) * e, dtype=torch.float32) + 0.5) * st
+                          for n, e, st in zip(size, g["extra"], g["stride"])]
+                shifts = torch.cartesian_prod(*ranges).unsqueeze(-2)
+                out.append(torch.stack(torch.broadcast_tensors(shifts, g["raw"]), dim=-2).reshape(-1, 2, 3))
+        return torch.cat(out, 0)
+
+    def plan(self, scene_shape, sizes, device):
+        sizes = tuple(tuple(int(v) for v in s) for s in sizes)
+        key = (tuple(float(v) for v in scene_shape), sizes, str(device))
+        pl = self._cache.get(key)
+        if pl is None:
+            anchors = self.all_anchors(sizes)
+            inside = inside_indicator(anchors, torch.tensor(key[0], dtype=torch.float32), self.allowed_border)
+            dest = torch.where(inside, torch.cumsum(inside, 0) - 1, torch.full((), -1, dtype=torch.int64)).to(torch.int32)
+            pl = _UpPlan()
+            pl.n_all, pl.n_inside = int(anchors.shape[0]), int(inside.sum())
+            pl.inside_cpu = inside
+            pl.anchors = anchors[inside].to(device)
+            pl.dest = dest.to(device)
+            pl.levels, first = [], 0
+            for groups, size, ncol in zip(self._groups, sizes, self.ncol_levels):
+                table, col = L.host_i64(6 * len(groups)), 0
+                for i, g in enumerate(groups):
+                    e, a = g["extra"], g["n_anchors"]
+                    table[6 * i:6 * i + 6] = [e[0], e[1], e[2], a, col, first]
+                    col += e[0] * e[1] * e[2] * a * 7
+                    first += size[0] * size[1] * size[2] * e[0] * e[1] * e[2] * a
+                pl.levels.append((size, ncol, table, len(groups)))
+            self._cache[key] = pl
+        return pl
+
+    def packed(self, level):
+        """(Wm [C, Ncol], bias_cols [Ncol]) of a level from its groups' parameters."""
+        ws, bs = [], []
+        for h in self.rpn_net_levels.operation[level]:
+            taps = h.weight.shape[2] * h.weight.shape[3] * h.weight.shape[4]
+            ws.append(h.weight.permute(0, 2, 3, 4, 1).reshape(h.weight.shape[0], -1))
+            bs.append(h.bias.repeat(taps))
+        return torch.cat(ws, 1), torch.cat(bs, 0)
+
+    def level_sizes(self, scene_shape):
+        return tuple(tuple(int(v) // s for v, s in zip(scene_shape, st)) for st in self.conv_strides)
+
+    def target_calculator(self, scene_shape, device=None):
+        """The reference's `rpn_target_calculator` (anchor.py:148-165) over exactly the inside anchors `forward` returns for a
+        scene of `scene_shape` voxels (every level's grid: scene_shape / its stride), as MultiLevelRpn.target_calculator."""
+        from .loss import RpnTargetCalculator
+        device = device if device is not None else self.heads()[0].weight.device
+        scene = tuple(int(v) for v in scene_shape)
+        return RpnTargetCalculator(self.plan(scene, self.level_sizes(scene), device).anchors)
+
+    def forward(self, level_slabs, scene_shape):
+        from . import functional as F
+        if len(level_slabs) != len(self._groups):
+            raise ValueError(f"AnchorNetworkUpsample: {len(self._groups)} levels, {len(level_slabs)} slabs")
+        if not all(s[0].is_cuda for s in level_slabs):
+            raise L.ScnError("AnchorNetworkUpsample: the level slabs must live on the MI355X (no CPU fallback)")
+        batch = int(level_slabs[0][2])
+        pl = self.plan(scene_shape, [s[1] for s in level_slabs], level_slabs[0][0].device)
+        Ps = []
+        for l, (slab, size, b) in enumerate(level_slabs):
+            if int(b) != batch:
+                raise ValueError("AnchorNetworkUpsample: the levels disagree about the batch size")
+            Wm, bias_cols = self.packed(l)
+            Ps.append(F.NetworkInNetworkFunction.apply(slab, Wm, bias_cols))
+        rpn_bbox, rpn_score = F.AnchorUpFunction.apply(pl, batch, *Ps)
+        return rpn_bbox, rpn_score, pl.anchors
+
+    def load_reference_state_dict(self, state_dict):
+        """Copy a reference checkpoint's head parameters: keys `rpn_net_levels.operation.{l}.{g}.weight` / `.bias`, bare or
+        under `bbox_network.` (then every other key of the checkpoint is somebody else's).  The reference's non-learned
+        entries (`anchor_storage.conv_stride_levels`, `anchor_storage.raw_anchor_levels.*`, `anchor_storage.descriptions.*`)
+        are ignored.  A missing or extra group, or another shape, is a ValueError that names the key; nothing is copied then."""
+        prefix = "bbox_network."
+        if any(k.startswith(prefix) for k in state_dict):
+            state_dict = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+        given = {k: v for k, v in state_dict.items() if not k.startswith("anchor_storage.")}
+        own = dict(self.named_parameters())
+        for k in given:
+            if k not in own:
+                raise ValueError(f"AnchorNetworkUpsample: the checkpoint's `{k}` has no counterpart (levels / groups: "
+                                 f"{[len(g) for g in self._groups]})")
+        for k, p in own.items():
+            if k not in given:
+                raise ValueError(f"AnchorNetworkUpsample: the checkpoint lacks `{k}`")
+            if tuple(given[k].shape) != tuple(p.shape):
+                raise ValueError(f"AnchorNetworkUpsample: `{k}` is {tuple(given[k].shape)} in the checkpoint, {tuple(p.shape)} here")
+        with torch.no_grad():
+            for k, p in own.items():
+                p.copy_(torch.as_tensor(given[k]).to(p.device, p.dtype))
+
+
 class MultiLevelRpn(nn.Module):
     """The reference's RPN shape with several anchor levels (scannet_config/run.py:525-536: `upconvoluted_anchornetwork`,
     one dilation network per anchor level, `anchor_output_channels = [128, 256]`, `num_dilations = 5` :609): one DenseRpn per
     level -- SparseToDense of THAT encoder level, its own dilation stack, a 1x1 head for its own anchors -- the levels'
     outputs concatenated in level order and the anchors that leave the scene dropped (`rpn_bbox_score_splitter`,
-    anchor.py:177-197).  The reference's heads are transposed convolutions that refine the anchor grid
-    (`AnchorNetworkUpsample`, anchor_network.py:127-219): dense torch modules, out of scope; the 1x1 heads
-    here keep every level's anchors on the level's own grid.
-    levels: [(channels, stride, width, anchors [A, 3] in voxels)];  forward(level_tensors) -> (rpn_bbox [B, N, 2, 3],
-    rpn_score [B, N], anchors [N, 2, 3]) over the inside anchors of all levels."""
+    anchor.py:177-197).  extra_stride_levels=None: 1x1 heads, every level's anchors on the level's own grid
+    (`AnchorNetworkConv`).  extra_stride_levels given (per level [G, 3]): the reference's committed heads, transposed
+    convolutions that refine the anchor grid per group of anchors (`AnchorNetworkUpsample` above, as `self.anchor_network`); the
+    DenseRpn levels then carry no head and hand over their stack's slab, and a level's anchors are its groups' [A_g, 3] lists.
+    levels: [(channels, stride, width, anchors [A, 3] in voxels -- or the groups' anchors)];  forward(level_tensors) ->
+    (rpn_bbox [B, N, 2, 3], rpn_score [B, N], anchors [N, 2, 3]) over the inside anchors of all levels."""
 
     def __init__(self, levels, num_dilations=5, autocast_bf16=False, engine=None, allowed_border=0, keep_volume=False,
-                 class_output_index=0):
+                 class_output_index=0, extra_stride_levels=None):
         """keep_volume / class_output_index (off: nothing changes): the level `class_output_index` keeps its stack's output
         volume (DenseRpn(keep_volume=True)), read back as `self.volume`; 0 is the reference's index with segmentation
         (scannet_config/run.py:605-607)."""
         super().__init__()
         self.class_output_index = int(class_output_index)
-        self.levels = nn.ModuleList(DenseRpn(c, stride, width, num_dilations, tuple(map(tuple, a)), autocast_bf16, engine,
-                                             keep_inside=False,
-                                             keep_volume=bool(keep_volume) and i == self.class_output_index % len(levels))
+        up = extra_stride_levels is not None
+        self.levels = nn.ModuleList(DenseRpn(c, stride, width, num_dilations, () if up else tuple(map(tuple, a)), autocast_bf16,
+                                             engine, keep_inside=False,
+                                             keep_volume=bool(keep_volume) and i == self.class_output_index % len(levels),
+                                             **(dict(with_head=False) if up else {}))
                                     for i, (c, stride, width, a) in enumerate(levels))
+        self.anchor_network = None
+        if up:
+            if autocast_bf16:
+                raise ValueError("MultiLevelRpn: the up-sampling heads run on the fp32 slab of engine 'tiles'")
+            self.anchor_network = AnchorNetworkUpsample([a for _, _, _, a in levels], [s for _, s, _, _ in levels],
+                                                        [w for _, _, w, _ in levels], allowed_border,
+                                                        extra_stride_levels=extra_stride_levels)
         self.allowed_border = float(allowed_border)
         self._cache = {}
 
@@ -317,6 +554,10 @@ class MultiLevelRpn(nn.Module):
     def forward(self, level_tensors):
         outs = [rpn(t) for rpn, t in zip(self.levels, level_tensors)]
         scene = tuple(int(v) * self.levels[0].stride for v in level_tensors[0].spatial_size)
+        if self.anchor_network is not None:
+            rpn_bbox, rpn_score, anchors = self.anchor_network([o[:3] for o in outs], scene)
+            rpn_score.cell_flags = [o[3] for o in outs]
+            return rpn_bbox, rpn_score, anchors
         return self.combine(outs, scene)
 
     def _inside(self, level_anchors, scene_shape, device):
@@ -333,6 +574,8 @@ class MultiLevelRpn(nn.Module):
         `forward` returns for a scene of `scene_shape` voxels (every level's grid: scene_shape / its stride)
         (loss.RpnTargetCalculator, scn_rpn_targets)."""
         from .loss import RpnTargetCalculator
+        if self.anchor_network is not None:
+            return self.anchor_network.target_calculator(scene_shape, device)
         device = device if device is not None else self.levels[0].head.weight.device
         scene = tuple(int(v) for v in scene_shape)
         level_anchors = [l.anchors_for(tuple(v // l.stride for v in scene), device) for l in self.levels]

@@ -19,9 +19,12 @@ Workloads (BASELINE.json configs; SURVEY.md §8d synthetic inputs):
   ref-crop-rpn  the reference's own detection step as far as this path reaches: plan 32-48-64-80-96-112 on its training batch
                     (12 crops of 128 x 128 x 64, run.py:364,485-488), SparseToDense of BOTH anchor levels (stride 4: 64 ch,
                     stride 8: 80 ch), a 5 x 128 and a 5 x 256 dilation stack (run.py:525-536,609), 3 + 11 anchors per cell
-                    (scannet_config/network.py:7-45) behind 1x1 heads (NOT AnchorNetworkUpsample's transposed convolutions:
-                    dense, out of scope), inside-the-scene anchors only, top-1024 / NMS 0.5 / 256 kept (run.py:847-853), boxes
-                    clipped to the scene (anchor.py:218-225), sparse ROI crop + mask branch.
+                    (scannet_config/network.py:7-45) behind 1x1 heads -- or, `upsample_heads=True`, behind the reference's
+                    committed heads (run.py:339,532-537: AnchorNetworkUpsample, one transposed convolution per group of
+                    anchors on a grid finer than the level's: 182 272 anchors per crop in 11 groups, 88 536 of them inside,
+                    where the 1x1 heads have 71 680; rpn.AnchorNetworkUpsample, scn_anchor_up.hip) --, inside-the-scene
+                    anchors only, top-1024 / NMS 0.5 / 256 kept (run.py:847-853), boxes clipped to the scene
+                    (anchor.py:218-225), sparse ROI crop + mask branch.
   cfg5  configs[4]  one ~600k-voxel scene, 5-level U-Net to 512 channels
 configs[3] (8 scenes data-parallel) is cfg3 with one scene per rank.
 """
@@ -88,8 +91,10 @@ class SparseStepModel(torch.nn.Module):
     """Backbone (+ mask branch for cfg3) as one module, so that one flat parameter buffer covers the step."""
 
     def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False, with_class=False,
-                 with_segmentation=False):
-        """with_rpn: False | "stand-in" (cfg3-rpn: one anchor level, 2 x 32 stack) | "reference" (ref-crop-rpn: the reference's two
+                 with_segmentation=False, upsample_heads=False):
+        """upsample_heads (with_rpn="reference" only; False: nothing changes): the reference's committed RPN heads,
+        rpn.AnchorNetworkUpsample with its extra strides and anchor groups, in place of the 1x1 heads.
+        with_rpn: False | "stand-in" (cfg3-rpn: one anchor level, 2 x 32 stack) | "reference" (ref-crop-rpn: the reference's two
         anchor levels with 5 x 128 / 5 x 256 stacks, rpn.MultiLevelRpn).
         with_class: the reference's class branch (classhead.ClassBranch) on the coarsest RPN level of the encoder -- the
         reference's `class_output_index=-1` on a main network that ends at its last anchor level (run.py:581-584, 605-608).
@@ -103,7 +108,19 @@ class SparseStepModel(torch.nn.Module):
         self.mask = MaskBranch(channels[0], 7, bf16_blocks=storage) if with_mask else None
         self.rpn = self.roi_selector = None
         self.rpn_levels = None                 # indices of the encoder levels the RPN reads
-        if with_rpn == "reference":
+        if upsample_heads and with_rpn != "reference":
+            raise ValueError("upsample_heads=True needs with_rpn='reference' (the reference's two anchor levels)")
+        if with_rpn == "reference" and upsample_heads:
+            from .rpn import MultiLevelRpn, RoiSelector, REF_EXTRA_STRIDE_LEVELS, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS
+            if storage:
+                raise ValueError("upsample_heads=True runs the RPN in fp32 (dtype f32)")
+            self.rpn_levels = (2, 3)
+            self.rpn = MultiLevelRpn([(channels[2], 4, 128, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS[0]),
+                                      (channels[3], 8, 256, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS[1])], num_dilations=5,
+                                     extra_stride_levels=REF_EXTRA_STRIDE_LEVELS,
+                                     **(dict(keep_volume=True) if with_class == "dense" else {}))
+            self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:847-853: 1024 / 256 / 0.5
+        elif with_rpn == "reference":
             from .rpn import MultiLevelRpn, RoiSelector, REF_ANCHOR_LEVELS_VOXELS
             # run.py:525-549: anchor paths on the two levels behind the in-between downsamplers (64 ch at stride 4, 80 ch at
             # stride 8 in the plan 32-48-64-80-96-112), anchor_output_channels = [128, 256], num_dilations = 5 (run.py:609)
@@ -155,8 +172,14 @@ class SceneStep:
     def __init__(self, workload="cfg2", device=None, dtype="f32", prefetch=True, seed=1, grad_seed=100, n_buckets=4,
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
-                 class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False):
-        """step_group: run the fp32 weight gradients of a step as one grid per kernel variant after the last backward pass
+                 class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
+                 upsample_heads=False):
+        """upsample_heads (`ref-crop-rpn` only; False: nothing changes): the RPN heads are the reference's committed ones
+        (run.py:339 `upconvoluted_anchornetwork = True`): rpn.AnchorNetworkUpsample, per anchor level one transposed
+        convolution per group of anchors that share an extra stride, so targets, draw, top-k and NMS see the reference's anchor
+        set (182 272 anchors per 128 x 128 x 64 crop, 88 536 inside) instead of the 1x1 heads' 71 680; every loss, predict() and
+        evaluate() run on it without further switches.  fp32 only.
+        step_group: run the fp32 weight gradients of a step as one grid per kernel variant after the last backward pass
         (executor.step_weight_gradients; one rank, no gradient buckets).  It keeps every stage's workspaces and unit slabs alive
         until then -- the cfg2 step's working set grows from 1.04 to 2.03 GB -- so False is the way to fit a scene that only fits
         with the per-pass form.
@@ -213,6 +236,11 @@ class SceneStep:
             raise ValueError("class_loss=True needs an RPN in the step (the -rpn workloads)")
         if dense_class and not class_loss:
             raise ValueError("dense_class=True chooses the class branch's arm: it needs class_loss=True")
+        if upsample_heads and workload != "ref-crop-rpn":
+            raise ValueError("upsample_heads=True is the reference's RPN head: only ref-crop-rpn has its two anchor levels")
+        if upsample_heads and dtype != "f32":
+            raise ValueError("upsample_heads=True runs the RPN in fp32 (dtype f32)")
+        self.upsample_heads = bool(upsample_heads)
         if segmentation_loss and not nb:
             raise ValueError("segmentation_loss=True needs a workload with boxes (cfg3, cfg3-rpn, ref-crop-rpn): the labels "
                              "come from the scene's instances")
@@ -290,7 +318,8 @@ class SceneStep:
         self.model = SparseStepModel(self.channels, bool(self.n_boxes), storage, rpn_kind, self.n_boxes,
                                      batchnorm=workload.endswith("-bn"),
                                      with_class="dense" if self.dense_class else self.class_loss,
-                                     with_segmentation=self.segmentation_loss).to(self.device)
+                                     with_segmentation=self.segmentation_loss,
+                                     **(dict(upsample_heads=True) if self.upsample_heads else {})).to(self.device)
         if self.with_rpn:
             self._init_rpn()
         self.rpn_loss = bool(rpn_loss)
@@ -416,6 +445,13 @@ class SceneStep:
         g = torch.Generator().manual_seed(1234)
         rpn = self.model.rpn
         with torch.no_grad():
+            if getattr(rpn, "anchor_network", None) is not None:
+                for h in rpn.anchor_network.heads():                                 # weight [C, A_g * 7, s0, s1, s2]
+                    w = torch.randn(h.weight.shape, generator=g) * 0.02
+                    w[:, 6::7] = torch.randn(w[:, 6::7].shape, generator=g) * 0.5
+                    h.weight.copy_(w.to(h.weight.device))
+                    h.bias.zero_()
+                return
             for h in ([r.head for r in rpn.levels] if hasattr(rpn, "levels") else [rpn.head]):
                 w = torch.randn(h.weight.shape, generator=g) * 0.02              # box deltas: boxes stay near their anchors
                 w[6::7] = torch.randn(w[6::7].shape, generator=g) * 0.5          # channel a*7+6 = the score of anchor a
@@ -772,12 +808,23 @@ class SceneStep:
                    "output, rpn_bbox, rpn_score and the mask logits")
             if hasattr(r, "levels"):
                 eng = r.levels[0].engine or r.levels[0].ENGINE
+                up = getattr(r, "anchor_network", None)
+
+                def head(i, l):
+                    if up is None:
+                        return f"1x1 head ({l.n_anchors} anchors/cell)"
+                    return ("up-sampling heads (" + ", ".join("x".join(map(str, g["extra"])) + f": {g['n_anchors']}"
+                                                              for g in up._groups[i]) + " anchors per fine cell)")
                 s += ("; + the REFERENCE's RPN shape INSIDE the step (run.py:525-536,609,847-853): " + " + ".join(
                     f"SparseToDense of the stride-{l.stride} level ({l.channels} ch) -> dense dilation stack {l.channels}"
-                    + f"-{l.width}" * (len(l.stack) // 2) + f" (3^3) + 1x1 head ({l.n_anchors} anchors/cell)" for l in r.levels)
+                    + f"-{l.width}" * (len(l.stack) // 2) + " (3^3) + " + head(i, l) for i, l in enumerate(r.levels))
                     + f", dense layers on engine '{eng}' "
                     + ("(this library's tile kernels on a fully active grid)" if eng == "tiles" else "(torch / MIOpen conv3d)")
-                    + "; 1x1 heads instead of AnchorNetworkUpsample's transposed convolutions (dense, out of scope) " + sel)
+                    + ("; 1x1 heads (AnchorNetworkConv), every anchor on its level's own grid -- the reference's committed "
+                       "AnchorNetworkUpsample heads: upsample_heads=True " if up is None else
+                       "; the reference's AnchorNetworkUpsample heads (run.py:339,532-537): per level one transposed "
+                       "convolution with kernel = stride per group of anchors, as one row GEMM + one scatter "
+                       "(scn_anchor_up.hip) ") + sel)
             else:
                 eng = r.engine or r.ENGINE
                 s += (f"; + RPN boundary INSIDE the step, a STAND-IN lighter than the reference's (one anchor level, 2 x {r.width} "
