@@ -73,7 +73,9 @@ extern "C" {
  *      additive within 5: + scn_wgrad_step_begin / _hold / _flush / _discard, scn_wgrad_group_counts; switch
  *      SCN_EXEC_GROUP_STEP (152 entry points);
  *      additive within 5: + scn_roialign_fwd / _bwd, scn_dense_maxpool_fwd / _bwd (156 entry points);
- *      additive within 5: + scn_anchor_up_fwd / _bwd (158 entry points) */
+ *      additive within 5: + scn_anchor_up_fwd / _bwd (158 entry points);
+ *      additive within 5: + scn_philox_words_host, scn_philox_fill, scn_sample_pack_drawn, scn_sample_cut_start (162 entry
+ *      points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -1032,6 +1034,50 @@ int scn_sample_pack(const int32_t* rows, int64_t m, const float* colors, const f
                     const float* normal_noise, int normal_noise_per_point, int use_color, int use_ones, int use_normal,
                     float* features, const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance,
                     int64_t n_kept, uint32_t* mask_words, scn_stream_t stream);
+
+/* ---- the sample conversion's random numbers, drawn on the device -- csrc/scn_rng.h, scn_draws.hip, scn_sample.hip ----
+ * Generator: Philox4x32-10 (Random123: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with
+ *   key = (seed lo32, seed hi32), counter = (index, stream, sample counter lo32, sample counter hi32),
+ * so every value is a function of (seed, sample counter, stream, index) alone: no state, no dependence on the launch shape or
+ * the order of calls.  Streams: SCN_RNG_* below.  A uniform of a word w is u(w) = ((w >> 9) + 0.5) * 2^-23 (exact in fp32, inside
+ * (0, 1)); the three normals of a draw (w0 .. w3) are z0 = r0 cospi(2 u(w1)), z1 = r0 sinpi(2 u(w1)), z2 = r1 cospi(2 u(w3)) with
+ * r0 = sqrt(-2 log u(w0)), r1 = sqrt(-2 log u(w2)), in fp32 with the accurate logf / sqrtf / sincospif.  A noise value is
+ * sigma * z rounded once; it is added to the feature with one more rounding.
+ *
+ * scn_philox_words_host: the four words of one draw, computed on the HOST (no GPU is touched).
+ * scn_philox_fill (1 launch, none for n == 0): the draws of indices first_index .. first_index + n - 1 of one stream; mode 0:
+ *   out uint32 [n][4] = the words; mode 1: out fp32 [n][3] = sigma * (z0, z1, z2).  Indices beyond 2^32: SCN_ESIZE.
+ * scn_sample_pack_drawn: scn_sample_pack with the noise drawn in the kernel instead of read -- kept row p of a per-point noise
+ *   is index p of stream SCN_RNG_COLOR / SCN_RNG_NORMAL, a common noise (*_common != 0) is index 0 of SCN_RNG_COLOR_COMMON /
+ *   SCN_RNG_NORMAL_COMMON.  A sigma of 0: no noise, no generator call.  Every output is bit-equal to scn_sample_pack fed the
+ *   tensors scn_philox_fill (mode 1) writes for the same seed, counter and sigma.  Launches and error codes as scn_sample_pack.
+ * scn_sample_cut_start (1 launch of one workgroup): the start positions of the reference's random_cut_out
+ *   (sparse_augmentation.py:50-78) over discrete int32 [n][3] (scn_vox_discretize's voxels before a cut-out); size_host /
+ *   border_host int32 [3] on the HOST (border = the largest empty border per dimension, 0 <= border <= size).  With (w0, w1, ..) the draw of
+ *   (SCN_RNG_CUT, index 0): i = (w0 * 3) >> 32, j = (w1 * 2) >> 32, the dimension order is [0, 1, 2] with element i, then
+ *   element j of the rest, taken out.  For the k-th dimension d of that order: lo / hi / count over the voxels the dimensions
+ *   before left alive; count == 0 ends the loop (later starts stay 0); min_start = lo - border, max_start = hi + 1 - size +
+ *   border; max_start <= min_start: start[d] = min_start and nothing is cut along d; else start[d] = min_start + ((w_k of
+ *   (SCN_RNG_CUT, index 1) * (uint64)(max_start - min_start)) >> 32) and only voxels with 0 <= x[d] - start[d] < size[d] stay
+ *   alive.  out8 (DEVICE int32 [8]) = start[3], order[3], voxels alive after the last processed dimension, dimensions
+ *   processed.  n < 1, a size < 1 or a border outside 0 .. size: SCN_EINVAL.  Starts are formed in 64 bits and
+ *   saturate at the int32 range.  Integers only: reruns give identical values.  Does not wait for the host. */
+#define SCN_RNG_HOST 0           /* distortion matrix, mirror, angle, sub-pixel offset: drawn on the host */
+#define SCN_RNG_CUT 1
+#define SCN_RNG_COLOR 2
+#define SCN_RNG_NORMAL 3
+#define SCN_RNG_COLOR_COMMON 4
+#define SCN_RNG_NORMAL_COMMON 5
+int scn_philox_words_host(uint64_t seed, uint64_t counter, uint32_t stream, uint32_t index, uint32_t* out4);
+int scn_philox_fill(uint64_t seed, uint64_t counter, uint32_t stream, int64_t first_index, int64_t n, int mode, float sigma,
+                    void* out, scn_stream_t stream_handle);
+int scn_sample_pack_drawn(const int32_t* rows, int64_t m, const float* colors, const float* normals, const int64_t* instance_ids,
+                          int n_instances, const float* rotation_host, uint64_t seed, uint64_t counter, float color_sigma,
+                          int color_common, float normal_sigma, int normal_common, int use_color, int use_ones, int use_normal,
+                          float* features, const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance,
+                          int64_t n_kept, uint32_t* mask_words, scn_stream_t stream);
+int scn_sample_cut_start(const int32_t* discrete, int64_t n, const int32_t* size_host, const int32_t* border_host, uint64_t seed,
+                         uint64_t counter, int32_t* out8, scn_stream_t stream);
 
 /* ---- dense RoiAlign and the unclamped dense max pool of the reference's dense class branch (ndsis/modules/
  * roi_select_dense.py:28-141 RoiAlign with clip_boxes=True; nn.MaxPool3d(2)) -- csrc/scn_roialign.hip, fp32 ----

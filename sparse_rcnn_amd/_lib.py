@@ -180,6 +180,11 @@ _SIGS = {
     "scn_dense_maxpool_bwd": (C.c_int, [p, p, i64, C.POINTER(i64), i32, p, p]),
     "scn_anchor_up_fwd": (C.c_int, [p, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, p, i64, i64, p, p, p]),
     "scn_anchor_up_bwd": (C.c_int, [p, p, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, p, i64, i64, p, p]),
+    "scn_philox_words_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "scn_philox_fill": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, i64, i64, i32, f32, p, p]),
+    "scn_sample_pack_drawn": (C.c_int, [p, i64, p, p, p, i32, p, C.c_uint64, C.c_uint64, f32, i32, f32, i32, i32, i32, i32, p, p, p,
+                                        p, i64, p, p]),
+    "scn_sample_cut_start": (C.c_int, [p, i64, p, p, C.c_uint64, C.c_uint64, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -196,6 +201,7 @@ PYRAMID_DESC_LEN = 8 + PYRAMID_MAX_LEVELS * PYRAMID_LEVEL_STRIDE
 COLSUM_BLOCKS = 512
 SAMPLE_MAX_INSTANCES = 1023      # SCN_SAMPLE_MAX_INSTANCES
 ANCHOR_UP_MAX_GROUPS = 16        # SCN_ANCHOR_UP_MAX_GROUPS
+RNG_HOST, RNG_CUT, RNG_COLOR, RNG_NORMAL, RNG_COLOR_COMMON, RNG_NORMAL_COMMON = range(6)     # SCN_RNG_*: the streams
 
 
 class ScnError(RuntimeError):

@@ -12,6 +12,7 @@
 // The selection between the two (ratio of two exact counts > threshold, boxes, labels) is a few hundred values: the host
 // does it from one copy of the stats table (sparse_rcnn_amd/sample.py).
 #include "scn_common.h"
+#include "scn_rng.h"
 
 #include <limits.h>
 
@@ -123,8 +124,25 @@ struct PackArgs {
     const int* slot_of; long long w; unsigned* words;
 };
 
-__global__ __launch_bounds__(256) void k_sample_pack(PackArgs a) {
+// Where the noise comes from is a compile-time variant of ONE kernel body.  kDrawn = false: the tensors above, the kernel
+// scn_sample_pack has always launched (its argument block is PackArgs and nothing else).  kDrawn = true: the noise of kept
+// row p is drawn in place (scn_rng.h: streams 2 / 3 with index p, or the common draw of streams 4 / 5 with index 0) and
+// added as v + sigma * z, each rounded once -- the bits scn_sample_pack gives when fed what scn_philox_fill writes.
+template <bool kDrawn> struct PackArgsT : PackArgs {};
+template <> struct PackArgsT<true> : PackArgs {
+    unsigned long long seed, counter;
+    float csigma, nsigma;                              // 0 = no noise, no generator call
+    int ccommon, ncommon;
+};
+
+template <bool kDrawn>
+__global__ __launch_bounds__(256) void k_sample_pack(PackArgsT<kDrawn> a) {
     const int lane = threadIdx.x & 63;
+    [[maybe_unused]] float ccz[3] = {0.f, 0.f, 0.f}, ncz[3] = {0.f, 0.f, 0.f};
+    if constexpr (kDrawn) {
+        if (a.feats && a.use_color && a.csigma != 0.f && a.ccommon) scn_rng_normal3(scn_rng_draw(a.seed, a.counter, SCN_RNG_COLOR_COMMON, 0), ccz);
+        if (a.feats && a.use_normal && a.nsigma != 0.f && a.ncommon) scn_rng_normal3(scn_rng_draw(a.seed, a.counter, SCN_RNG_NORMAL_COMMON, 0), ncz);
+    }
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p - lane < a.m; p += (long long)gridDim.x * blockDim.x) {
         int slot = -1;
         if (p < a.m) {
@@ -132,20 +150,30 @@ __global__ __launch_bounds__(256) void k_sample_pack(PackArgs a) {
             if (a.feats) {
                 float* f = a.feats + p * a.c;
                 if (a.use_color) {
+                    [[maybe_unused]] float z[3] = {ccz[0], ccz[1], ccz[2]};
+                    if constexpr (kDrawn) {
+                        if (a.csigma != 0.f && !a.ccommon) scn_rng_normal3(scn_rng_draw(a.seed, a.counter, SCN_RNG_COLOR, (uint32_t)p), z);
+                    }
 #pragma unroll
                     for (int d = 0; d < 3; ++d) {
                         const float v = a.colors[3 * r + d];
-                        f[d] = a.cnoise ? __fadd_rn(v, a.cnoise[a.cnoise_pp ? 3 * p + d : d]) : v;
+                        if constexpr (kDrawn) f[d] = a.csigma != 0.f ? scn_rng_add_noise(v, a.csigma, z[d]) : v;
+                        else f[d] = a.cnoise ? __fadd_rn(v, a.cnoise[a.cnoise_pp ? 3 * p + d : d]) : v;
                     }
                     f += 3;
                 }
                 if (a.use_ones) *f++ = 1.f;
                 if (a.use_normal) {
                     const float x = a.normals[3 * r], y = a.normals[3 * r + 1], z = a.normals[3 * r + 2];
+                    [[maybe_unused]] float nz[3] = {ncz[0], ncz[1], ncz[2]};
+                    if constexpr (kDrawn) {
+                        if (a.nsigma != 0.f && !a.ncommon) scn_rng_normal3(scn_rng_draw(a.seed, a.counter, SCN_RNG_NORMAL, (uint32_t)p), nz);
+                    }
 #pragma unroll
                     for (int d = 0; d < 3; ++d) {          // the association of k_vox_project: torch's CPU matmul for K = 3
                         const float v = fmaf(z, a.r[6 + d], fmaf(y, a.r[3 + d], __fmul_rn(x, a.r[d])));
-                        f[d] = a.nnoise ? __fadd_rn(v, a.nnoise[a.nnoise_pp ? 3 * p + d : d]) : v;
+                        if constexpr (kDrawn) f[d] = a.nsigma != 0.f ? scn_rng_add_noise(v, a.nsigma, nz[d]) : v;
+                        else f[d] = a.nnoise ? __fadd_rn(v, a.nnoise[a.nnoise_pp ? 3 * p + d : d]) : v;
                     }
                 }
             }
@@ -191,15 +219,16 @@ extern "C" int scn_sample_stats(const int32_t* discrete, const int32_t* table, c
     return SCN_OK;
 }
 
-extern "C" int scn_sample_pack(const int32_t* rows, int64_t m, const float* colors, const float* normals,
-                               const int64_t* instance_ids, int n_instances, const float* rotation_host,
-                               const float* color_noise, int color_noise_per_point, const float* normal_noise,
-                               int normal_noise_per_point, int use_color, int use_ones, int use_normal, float* features,
-                               const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance, int64_t n_kept,
-                               uint32_t* mask_words, scn_stream_t stream) {
+// The argument checks and the launch of both pack entry points; `a` arrives with its noise source filled in.
+template <bool kDrawn>
+static int sample_pack_run(PackArgsT<kDrawn>& a, const char* who, const int32_t* rows, int64_t m, const float* colors,
+                           const float* normals, const int64_t* instance_ids, int n_instances, const float* rotation_host,
+                           int use_color, int use_ones, int use_normal, float* features, const int64_t* seg_table,
+                           int64_t* seg_labels, const int32_t* slot_of_instance, int64_t n_kept, uint32_t* mask_words,
+                           scn_stream_t stream) {
     SCN_REQUIRE(m >= 0 && m < 2147483647LL && n_kept >= 0 && n_instances >= 0);
     if (n_instances > SCN_SAMPLE_MAX_INSTANCES)
-        return scn::fail(SCN_ESIZE, "scn_sample_pack%s: %lld instances, at most %lld", "", n_instances, SCN_SAMPLE_MAX_INSTANCES);
+        return scn::fail(SCN_ESIZE, "%s: %lld instances, at most %lld", who, n_instances, SCN_SAMPLE_MAX_INSTANCES);
     if (m == 0) return SCN_OK;                         // no kept row: no feature, no label, no mask word
     const int c = (use_color ? 3 : 0) + (use_ones ? 1 : 0) + (use_normal ? 3 : 0);
     SCN_REQUIRE(rows && (c == 0 || features));
@@ -208,13 +237,10 @@ extern "C" int scn_sample_pack(const int32_t* rows, int64_t m, const float* colo
     SCN_REQUIRE((seg_labels == nullptr) == (seg_table == nullptr));
     SCN_REQUIRE(n_kept == 0 || (slot_of_instance && mask_words));
     SCN_REQUIRE((!seg_labels && n_kept == 0) || instance_ids);
-    PackArgs a;
     a.rows = rows; a.m = m; a.colors = colors; a.normals = normals;
     a.ids = (seg_labels || n_kept) ? (const long long*)instance_ids : nullptr;
     a.slots = n_instances + 1;
     for (int k = 0; k < 9; ++k) a.r[k] = use_normal ? rotation_host[k] : 0.f;
-    a.cnoise = use_color ? color_noise : nullptr; a.cnoise_pp = color_noise_per_point ? 1 : 0;
-    a.nnoise = use_normal ? normal_noise : nullptr; a.nnoise_pp = normal_noise_per_point ? 1 : 0;
     a.use_color = use_color ? 1 : 0; a.use_ones = use_ones ? 1 : 0; a.use_normal = use_normal ? 1 : 0; a.c = c;
     a.feats = c ? features : nullptr;
     a.seg_table = (const long long*)seg_table; a.seg = (long long*)seg_labels;
@@ -222,7 +248,38 @@ extern "C" int scn_sample_pack(const int32_t* rows, int64_t m, const float* colo
     a.w = (m + 31) / 32; a.words = mask_words;
     if (n_kept) SCN_HIP(hipMemsetAsync(mask_words, 0, (size_t)n_kept * (size_t)a.w * sizeof(uint32_t), S(stream)));
     if (!a.feats && !a.ids) return SCN_OK;
-    hipLaunchKernelGGL(k_sample_pack, dim3(scn::ew_grid(m, 256)), dim3(256), 0, S(stream), a);
+    hipLaunchKernelGGL(k_sample_pack<kDrawn>, dim3(scn::ew_grid(m, 256)), dim3(256), 0, S(stream), a);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
+}
+
+extern "C" int scn_sample_pack(const int32_t* rows, int64_t m, const float* colors, const float* normals,
+                               const int64_t* instance_ids, int n_instances, const float* rotation_host,
+                               const float* color_noise, int color_noise_per_point, const float* normal_noise,
+                               int normal_noise_per_point, int use_color, int use_ones, int use_normal, float* features,
+                               const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance, int64_t n_kept,
+                               uint32_t* mask_words, scn_stream_t stream) {
+    PackArgsT<false> a;
+    a.cnoise = use_color ? color_noise : nullptr; a.cnoise_pp = color_noise_per_point ? 1 : 0;
+    a.nnoise = use_normal ? normal_noise : nullptr; a.nnoise_pp = normal_noise_per_point ? 1 : 0;
+    return sample_pack_run<false>(a, "scn_sample_pack", rows, m, colors, normals, instance_ids, n_instances, rotation_host,
+                                  use_color, use_ones, use_normal, features, seg_table, seg_labels, slot_of_instance, n_kept,
+                                  mask_words, stream);
+}
+
+extern "C" int scn_sample_pack_drawn(const int32_t* rows, int64_t m, const float* colors, const float* normals,
+                                     const int64_t* instance_ids, int n_instances, const float* rotation_host, uint64_t seed,
+                                     uint64_t counter, float color_sigma, int color_common, float normal_sigma,
+                                     int normal_common, int use_color, int use_ones, int use_normal, float* features,
+                                     const int64_t* seg_table, int64_t* seg_labels, const int32_t* slot_of_instance,
+                                     int64_t n_kept, uint32_t* mask_words, scn_stream_t stream) {
+    SCN_REQUIRE(color_sigma == color_sigma && normal_sigma == normal_sigma);      // a NaN sigma is no amount of noise
+    PackArgsT<true> a;
+    a.cnoise = nullptr; a.cnoise_pp = 0; a.nnoise = nullptr; a.nnoise_pp = 0;
+    a.seed = seed; a.counter = counter;
+    a.csigma = use_color ? color_sigma : 0.f; a.nsigma = use_normal ? normal_sigma : 0.f;
+    a.ccommon = color_common ? 1 : 0; a.ncommon = normal_common ? 1 : 0;
+    return sample_pack_run<true>(a, "scn_sample_pack_drawn", rows, m, colors, normals, instance_ids, n_instances,
+                                 rotation_host, use_color, use_ones, use_normal, features, seg_table, seg_labels,
+                                 slot_of_instance, n_kept, mask_words, stream);
 }

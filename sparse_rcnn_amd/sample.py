@@ -9,21 +9,31 @@ Every random number of the reference is an input (`Draws`).  `draw_augmentation`
 with torch's CPU generator, by the reference's calls in the reference's order, so one ``torch.manual_seed`` gives the
 reference's values; `convert_sample(..., draws=None)` calls them itself at the points where the reference draws.
 
+`PhiloxDraws` is the other source: a conversion whose every random number is a function of (seed, sample counter) -- the counter-
+based generator of csrc/scn_rng.h (Philox4x32-10).  The nine host values come from `philox_normals` / `philox_words` here; the
+random cut-out's start is ONE launch (scn_sample_cut_start) and one 32-byte read; the per-point noise is drawn inside the pack
+kernel (scn_sample_pack_drawn) and never exists as a tensor unless `augmentation['color_shift'].tensor()` asks for it.  It does
+not reproduce ``torch.manual_seed``'s values: the reference's fixtures pin the host-generator path, and the tests pin this path
+to that one.
+
 Host waits of one `convert_sample`: the kept-row count (augment_coords' own) and ONE copy of the (I + 1) x 8 instance table,
-queued before that count is waited for.  The random cut-out adds the three small reads of `random_cut_start`.
+queued before that count is waited for.  The random cut-out adds the three small reads of `random_cut_start` -- with a
+`PhiloxDraws` one read of 32 bytes, and no noise is copied to the device.
 DEVIATION: ``augmentation['remaining_points']`` stays on the device (the reference copies N bools to the host per sample).
 """
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
 from .loss import PackedMasks
 from .voxelize import _augment_coords, _f32xn, _i32x3
 
-__all__ = ["Draws", "draw_augmentation", "random_cut_start", "convert_sample", "collate", "join_packed_masks"]
+__all__ = ["Draws", "PhiloxDraws", "draw_augmentation", "random_cut_start", "convert_sample", "collate", "join_packed_masks",
+           "philox_words", "philox_normals"]
 
 
 class Draws:
@@ -40,17 +50,21 @@ class Draws:
         self.normal_noise = None if normal_noise is None else torch.as_tensor(normal_noise, dtype=torch.float32)
 
 
-def _distortion_matrix(dtype, coord_noise_sigma, theta, mirror):
+def _distortion_matrix(dtype, coord_noise_sigma, theta, mirror, normals=None, mirror_bit=None, uniform=None, pick=None):
     """get_coord_distortion_matrix (sparse_augmentation.py:9-38): randn(3,3), then randint(0,2) if mirror is None, then rand()
-    if theta is None (multinomial if theta is a list)."""
-    m = torch.eye(3, dtype=dtype) + torch.randn((3, 3), dtype=dtype) * coord_noise_sigma
-    m[0, 0] *= (torch.randint(0, 2, ()) * 2 - 1) if mirror is None else (-1 if mirror else 1)
+    if theta is None (multinomial if theta is a list).  Each draw can be handed in instead (`PhiloxDraws`): `normals` fp32
+    [3,3], `mirror_bit` 0 / 1, `uniform` in (0, 1), `pick(n)` -> an index below n; a None is drawn from torch's generator."""
+    m = torch.eye(3, dtype=dtype) + (torch.randn((3, 3), dtype=dtype) if normals is None else normals) * coord_noise_sigma
+    if mirror is None:
+        m[0, 0] *= (torch.randint(0, 2, ()) if mirror_bit is None else mirror_bit) * 2 - 1
+    else:
+        m[0, 0] *= -1 if mirror else 1
     if theta is None:
-        angle = torch.rand((), dtype=dtype) * 2 * math.pi
+        angle = (torch.rand((), dtype=dtype) if uniform is None else torch.tensor(uniform, dtype=dtype)) * 2 * math.pi
     else:
         angle = torch.tensor(theta, dtype=dtype)
         if angle.numel() > 1:
-            angle = angle[torch.ones_like(angle).multinomial(1)[0]]
+            angle = angle[torch.ones_like(angle).multinomial(1)[0] if pick is None else pick(angle.numel())]
     c, s = torch.cos(angle), torch.sin(angle)
     return m @ torch.tensor([[c, s, 0.], [-s, c, 0.], [0., 0., 1.]])
 
@@ -128,6 +142,99 @@ def random_cut_start(discrete_coords, size, max_border):
     return start
 
 
+# ---- the counter-based generator (csrc/scn_rng.h), restated for the host's handful of values ----
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox_words(seed, counter, stream, index):
+    """Philox4x32-10 with key = (seed lo32, seed hi32) and counter = (index, stream, counter lo32, counter hi32): the draw
+    scn_rng.h's scn_rng_draw makes.  seed / counter: Python integers below 2^64; stream / index: integers or integer arrays
+    (broadcast).  -> numpy uint32 [..., 4]."""
+    seed, counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+    index, stream = np.broadcast_arrays(np.asarray(index, dtype=np.uint64), np.asarray(stream, dtype=np.uint64))
+    c = [index & _MASK32, stream & _MASK32, np.full(index.shape, counter & 0xFFFFFFFF, np.uint64),
+         np.full(index.shape, counter >> 32, np.uint64)]
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]        # 32 x 32 -> 64: no overflow in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & _MASK32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & _MASK32]
+        k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def _philox_uniform(words):
+    """u(w) = ((w >> 9) + 0.5) * 2^-23 in float64 (the same value as the fp32 form: it is exact in both)."""
+    return ((words >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+
+
+def philox_normals(seed, counter, stream, index):
+    """The three normals of each draw -- z0 = r0 cos(2 pi u1), z1 = r0 sin(2 pi u1), z2 = r1 cos(2 pi u3), r0 = sqrt(-2 ln u0),
+    r1 = sqrt(-2 ln u2) -- computed in float64 and cast: numpy fp32 [..., 3].  For the host's few values; the device's fp32
+    evaluation of the same words (scn_philox_fill) agrees to a few ulp, not to the bit."""
+    u = _philox_uniform(philox_words(seed, counter, stream, index))
+    r0, r1 = np.sqrt(-2 * np.log(u[..., 0])), np.sqrt(-2 * np.log(u[..., 2]))
+    z = np.stack([r0 * np.cos(2 * np.pi * u[..., 1]), r0 * np.sin(2 * np.pi * u[..., 1]), r1 * np.cos(2 * np.pi * u[..., 3])], -1)
+    return z.astype(np.float32)
+
+
+class _LazyNoise:
+    """`augmentation['color_shift']` / `['normals_shift']` of a `PhiloxDraws` conversion: the noise the pack kernel added, as a
+    recipe.  `.tensor()` materialises it on the device (scn_philox_fill): fp32 [3] (common) or [M, 3]."""
+
+    def __init__(self, draws, which, m, sigma, common, device):
+        self.draws, self.which, self.m, self.sigma, self.common, self.device = draws, which, m, sigma, common, device
+
+    def tensor(self):
+        return self.draws.noise_tensor(self.which, self.m, self.sigma, self.common, device=self.device)
+
+
+class PhiloxDraws(Draws):
+    """The draws of one conversion as a function of (seed, counter): one seed per run, counter = the global index of the sample
+    (INTEGRATION.md), so no two conversions share a value whatever rank or step makes them.
+
+    Host part, stream 0, through `_distortion_matrix`'s arithmetic: the normals of indices 0 .. 2 are the rows of the 3 x 3 that
+    coord_noise_sigma scales; of index 3, the low bit of word 0 is the mirror (1 = mirrored) and word 1 the angle (u * 2 pi) or
+    the pick from a list of angles ((w * len) >> 32); the uniforms of words 0 .. 2 of index 4 are the sub-pixel offset.  Fixed
+    theta / mirror / sub_pixel_offset pass through, as in `draw_augmentation`.  `start_positions` may be set by hand (a given
+    start); left None, `convert_sample` fills it from scn_sample_cut_start, together with `cut_order` / `cut_alive` /
+    `cut_dims`.  The noise is never stored here: `convert_sample` draws it inside the pack kernel."""
+
+    def __init__(self, seed, counter, *, coord_noise_sigma=0, theta=None, mirror=None, sub_pixel_offset=None):
+        self.seed, self.counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+        z = torch.from_numpy(philox_normals(self.seed, self.counter, L.RNG_HOST, np.arange(3)))
+        w = philox_words(self.seed, self.counter, L.RNG_HOST, np.arange(3, 5))
+        ortho = _distortion_matrix(torch.float32, coord_noise_sigma, theta, mirror, normals=z, mirror_bit=int(w[0, 0] & 1),
+                                   uniform=float(_philox_uniform(w[0, 1])), pick=lambda n: (int(w[0, 1]) * n) >> 32)
+        if sub_pixel_offset is None:
+            sub_pixel_offset = torch.from_numpy(_philox_uniform(w[1, :3]).astype(np.float32))
+        super().__init__(ortho, sub_pixel_offset)
+        self.cut_order = self.cut_alive = self.cut_dims = None
+
+    def cut_start(self, discrete, size, border):
+        """random_cut_out's start positions for the device voxels `discrete` int32 [N, 3]: one launch, one 32-byte read.
+        Fills start_positions (int64 [3], host), cut_order, cut_alive and cut_dims (scn_sample_cut_start's out8)."""
+        out8 = torch.empty(8, dtype=torch.int32, device=discrete.device)
+        L.check(L.lib().scn_sample_cut_start(L.ptr(discrete), discrete.shape[0], _i32x3(size), _i32x3(border), self.seed,
+                                             self.counter, L.ptr(out8), L.stream()))
+        host = out8.cpu()                                        # the one read of the random cut-out
+        self.start_positions = host[:3].to(torch.int64)
+        self.cut_order, self.cut_alive, self.cut_dims = host[3:6].tolist(), int(host[6]), int(host[7])
+        return self.start_positions
+
+    def noise_tensor(self, which, m, sigma, common, device=None):
+        """The noise `convert_sample` adds for `which` = 'color' | 'normal', materialised on the device by scn_philox_fill:
+        fp32 [3] (common) or [m, 3] (kept-row order) = sigma * z, bit for bit what the pack kernel adds."""
+        stream = {("color", False): L.RNG_COLOR, ("normal", False): L.RNG_NORMAL, ("color", True): L.RNG_COLOR_COMMON,
+                  ("normal", True): L.RNG_NORMAL_COMMON}[(which, bool(common))]
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        n = 1 if common else int(m)
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        L.check(L.lib().scn_philox_fill(self.seed, self.counter, stream, 0, n, 1, float(sigma), L.ptr(out), L.stream()))
+        return out[0] if common else out
+
+
 def _ceil_div(a, b):
     return -(-a // b)
 
@@ -171,7 +278,10 @@ def convert_sample(sample, *, spatial_size, instance_cutoff_threshold, color_noi
     a copy and a wait).
 
     draws: a `Draws` (every None in it that is needed is drawn in place), or None: `draw_augmentation` from coord_noise_sigma /
-    theta / mirror / sub_pixel_offset here.  With a `Draws`, those four keywords are not read.
+    theta / mirror / sub_pixel_offset here.  With a `Draws`, those four keywords are not read.  A `PhiloxDraws`: nothing is
+    drawn on the host -- the random cut-out's start comes from scn_sample_cut_start (one launch, one small read; written back
+    to `draws.start_positions`), the noise is drawn inside scn_sample_pack_drawn, and `augmentation['color_shift']` /
+    `['normals_shift']` are objects whose `.tensor()` materialises what was added (without noise: the zero-dim zero, as ever).
     Cut-out: spatial_size and shift -> fixed; spatial_size alone -> random (`draws.start_positions`, else `random_cut_start`
     with max_empty_border_size_divisor); spatial_size None -> none.  (Without a cut-out the reference's spatial size is the
     LARGEST voxel coordinate + 2 shift: with shift None or 0 the points on the far faces lie outside [0, size), and a network fed
@@ -203,6 +313,7 @@ def convert_sample(sample, *, spatial_size, instance_cutoff_threshold, color_noi
         draws = draw_augmentation(coord_noise_sigma=coord_noise_sigma, theta=theta, mirror=mirror,
                                   sub_pixel_offset=sub_pixel_offset, use_color=False, use_normal=False)
     rot_and_scale = draws.almost_orthonormal * scale
+    philox = isinstance(draws, PhiloxDraws)
 
     start_positions = None
     if spatial_size is not None and shift is None:
@@ -213,6 +324,8 @@ def convert_sample(sample, *, spatial_size, instance_cutoff_threshold, color_noi
             border = [0, 0, 0] if max_empty_border_size_divisor is None else [s // max_empty_border_size_divisor for s in size3]
 
             def start_positions(discrete):
+                if philox:
+                    return draws.cut_start(discrete, size3, border)
                 draws.start_positions = random_cut_start(discrete, size3, border)
                 return draws.start_positions
 
@@ -239,18 +352,19 @@ def convert_sample(sample, *, spatial_size, instance_cutoff_threshold, color_noi
     seg_raw = labels_raw if segmentation_label_mapper is None else torch.as_tensor(segmentation_label_mapper).cpu()[labels_raw]
     seg_table = torch.nn.functional.pad(seg_raw.to(torch.int64), (0, 1), value=background_label)
 
-    # the noise of the kept rows: drawn now if it was not given (the reference draws it here, colour first)
-    if use_color and color_noise_sigma and draws.color_noise is None:
-        draws.color_noise = _feature_noise(color_noise_sigma, common_color_noise, m)
-    if use_normal and normal_noise_sigma and draws.normal_noise is None:
-        draws.normal_noise = _feature_noise(normal_noise_sigma, common_normal_noise, m)
-    cn = draws.color_noise if (use_color and color_noise_sigma) else None
-    nn_ = draws.normal_noise if (use_normal and normal_noise_sigma) else None
-    for name, t in (("color_noise", cn), ("normal_noise", nn_)):
-        if t is not None and tuple(t.shape) not in ((3,), (m, 3)):
-            raise ValueError(f"{name}: [3] or [{m}, 3] (one row per kept point) required, got {tuple(t.shape)}")
-    cn_dev = None if cn is None else cn.to(dev).contiguous()
-    nn_dev = None if nn_ is None else nn_.to(dev).contiguous()
+    if not philox:
+        # the noise of the kept rows: drawn now if it was not given (the reference draws it here, colour first)
+        if use_color and color_noise_sigma and draws.color_noise is None:
+            draws.color_noise = _feature_noise(color_noise_sigma, common_color_noise, m)
+        if use_normal and normal_noise_sigma and draws.normal_noise is None:
+            draws.normal_noise = _feature_noise(normal_noise_sigma, common_normal_noise, m)
+        cn = draws.color_noise if (use_color and color_noise_sigma) else None
+        nn_ = draws.normal_noise if (use_normal and normal_noise_sigma) else None
+        for name, t in (("color_noise", cn), ("normal_noise", nn_)):
+            if t is not None and tuple(t.shape) not in ((3,), (m, 3)):
+                raise ValueError(f"{name}: [3] or [{m}, 3] (one row per kept point) required, got {tuple(t.shape)}")
+        cn_dev = None if cn is None else cn.to(dev).contiguous()
+        nn_dev = None if nn_ is None else nn_.to(dev).contiguous()
 
     c = (3 if use_color else 0) + (1 if use_ones else 0) + (3 if use_normal else 0)
     features = torch.empty((m, c), dtype=torch.float32, device=dev)
@@ -258,11 +372,22 @@ def convert_sample(sample, *, spatial_size, instance_cutoff_threshold, color_noi
     w = (m + 31) // 32
     words = torch.empty(max(g * w, 1), dtype=torch.int32, device=dev)
     slot_dev, seg_table_dev = slot_of.to(dev), seg_table.to(dev)
-    L.check(lib.scn_sample_pack(
-        L.ptr(rows), m, L.ptr(colors), L.ptr(normals), L.ptr(instance_ids), n_inst,
-        _f32xn(draws.almost_orthonormal, 9), L.ptr(cn_dev), int(cn is not None and cn.dim() == 2), L.ptr(nn_dev),
-        int(nn_ is not None and nn_.dim() == 2), int(bool(use_color)), int(bool(use_ones)), int(bool(use_normal)),
-        L.ptr(features) if c else 0, L.ptr(seg_table_dev), L.ptr(seg), L.ptr(slot_dev), g, L.ptr(words), L.stream()))
+    if philox:                                               # the noise is drawn inside the kernel: no randn, no copy
+        csig = float(color_noise_sigma) if (use_color and color_noise_sigma) else 0.0
+        nsig = float(normal_noise_sigma) if (use_normal and normal_noise_sigma) else 0.0
+        cn = _LazyNoise(draws, "color", m, csig, bool(common_color_noise), dev) if csig else None
+        nn_ = _LazyNoise(draws, "normal", m, nsig, bool(common_normal_noise), dev) if nsig else None
+        L.check(lib.scn_sample_pack_drawn(
+            L.ptr(rows), m, L.ptr(colors), L.ptr(normals), L.ptr(instance_ids), n_inst, _f32xn(draws.almost_orthonormal, 9),
+            draws.seed, draws.counter, csig, int(bool(common_color_noise)), nsig, int(bool(common_normal_noise)),
+            int(bool(use_color)), int(bool(use_ones)), int(bool(use_normal)), L.ptr(features) if c else 0,
+            L.ptr(seg_table_dev), L.ptr(seg), L.ptr(slot_dev), g, L.ptr(words), L.stream()))
+    else:
+        L.check(lib.scn_sample_pack(
+            L.ptr(rows), m, L.ptr(colors), L.ptr(normals), L.ptr(instance_ids), n_inst,
+            _f32xn(draws.almost_orthonormal, 9), L.ptr(cn_dev), int(cn is not None and cn.dim() == 2), L.ptr(nn_dev),
+            int(nn_ is not None and nn_.dim() == 2), int(bool(use_color)), int(bool(use_ones)), int(bool(use_normal)),
+            L.ptr(features) if c else 0, L.ptr(seg_table_dev), L.ptr(seg), L.ptr(slot_dev), g, L.ptr(words), L.stream()))
     gt_mask = PackedMasks(words, [g], [m])
     if dense_masks:
         gt_mask = gt_mask.unpack(0)

@@ -12,7 +12,14 @@ for (a) and (b), as a training run that keeps its scenes in HBM has them; the dr
 timed window ends in a device synchronise; each variant is warmed up, then the variants alternate for `--repeats` rounds and the
 median and the range over the rounds are printed.  Launches are counted with torch's profiler in a separate, untimed call.
 
-    python tools/sample_bench.py [--repeats 15] [--out profiles/sample_convert.txt]
+`--draws` says where the random numbers of (a) come from.  `given` (default): made on the host beforehand and handed in, the
+measurement above.  `host`: `convert_sample(draws=None)` -- the matrix, the random cut-out's start (random_cut_start: three small
+reads) and the per-point noise (torch.randn on the CPU, copied from pageable memory) are drawn inside the timed call, which is
+what a training loop on the host generator pays.  `device`: `PhiloxDraws` -- the start from scn_sample_cut_start, the noise
+inside scn_sample_pack_drawn.  `host` and `device` time (a) alone; every round draws afresh (round r: torch.manual_seed(r) /
+sample counters from r * samples), so the kept-row counts differ a little from round to round and between the two.
+
+    python tools/sample_bench.py [--repeats 15] [--draws given|host|device] [--out profiles/sample_convert.txt]
 """
 import argparse
 import os
@@ -26,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sample_restate as R                                                      # noqa: E402
-from test_gpu_sample import _device_convert, _training_kw                       # noqa: E402
+from test_gpu_sample import _device_convert, _training_kw, _training_mappers                      # noqa: E402
 
 
 def timed(fn, sync):
@@ -61,10 +68,46 @@ def count_launches(fn):
         return f"profiler failed: {type(e).__name__}"
 
 
+def drawn_cases(args, cases, say):
+    """(a) with its draws made inside the timed call: on the host (draws=None) or on the device (PhiloxDraws)."""
+    from sparse_rcnn_amd.sample import PhiloxDraws, collate, convert_sample
+    kept = []
+
+    def run(items, r):
+        if args.draws == "host":
+            torch.manual_seed(r)
+        outs = []
+        for i, (_, d, k) in enumerate(items):
+            draws = PhiloxDraws(1234, r * len(items) + i, coord_noise_sigma=0.1) if args.draws == "device" else None
+            outs.append(convert_sample(
+                d, spatial_size=k["spatial_size"], shift=k["shift"], instance_cutoff_threshold=0.8, color_noise_sigma=0.1,
+                common_color_noise=False, normal_noise_sigma=0, common_normal_noise=False, use_color=True, use_ones=True,
+                use_normal=True, additional_bbox_pixel=0, background_label=-100, scale=k["scale"],
+                instance_label_mapper=k["instance_label_mapper"], segmentation_label_mapper=k["segmentation_label_mapper"],
+                coord_noise_sigma=0.1, draws=draws))
+        kept.append(sum(int(o[1].shape[0]) for o in outs))
+        return collate(outs) if len(outs) > 1 else outs
+
+    for title, items in cases.items():
+        n = sum(s[0].shape[0] for s, _, _ in items)
+        for r in range(3):
+            run(items, 1000 + r)
+        torch.cuda.synchronize()
+        del kept[:]
+        t = [timed(lambda: run(items, r), True) for r in range(args.repeats)]
+        say(f"== {title}: {len(items)} sample(s), {n} stored points, kept per round {min(kept)} .. {max(kept)}, 40 instances each ==")
+        say(f"  (a) device path, draws = {args.draws:6s}                median {statistics.median(t):8.3f} ms   min {min(t):8.3f}   "
+            f"max {max(t):8.3f}   per sample {statistics.median(t) / len(items):8.3f} ms   ({len(t)} rounds)")
+        say(f"  device activities of one call (kernels, memsets, memcpys): {count_launches(lambda: run(items, 0))}")
+    say("host waits per sample, by construction: the kept-row count and the shift/extent copy of augment_coords + ONE copy of the "
+        "(I + 1) x 8 instance table; the random cut-out: + 3 reads in random_cut_start (host) or + 1 read of 32 bytes (device)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--points", type=int, default=200_000)
+    ap.add_argument("--draws", choices=("given", "host", "device"), default="given")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -83,6 +126,18 @@ def main():
     crops_raw = [make_raw_sample(args.points, 40, seed=2 + i) for i in range(3)]
     on_dev = lambda s: tuple(t.to(dev) for t in s[:4]) + (s[4],)               # noqa: E731
     cases = {}
+    if args.draws != "given":                                                   # no draws to prepare: the shapes and the mappers
+        inst, seg = _training_mappers()
+        light = lambda size, shift: dict(spatial_size=size, shift=shift, scale=1 / 0.02, instance_label_mapper=inst,   # noqa: E731
+                                         segmentation_label_mapper=seg)
+        cases["one scene, fixed cut-out 320x320x160"] = [(scene, on_dev(scene), light((320, 320, 160), 0))]
+        cases["12 random crops 128x128x64, collated"] = [(crops_raw[i % 3], on_dev(crops_raw[i % 3]), light((128, 128, 64), None))
+                                                         for i in range(12)]
+        drawn_cases(args, cases, say)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     kw = _training_kw(scene, seed=5, spatial_size=(320, 320, 160), shift=0)
     cases["one scene, fixed cut-out 320x320x160"] = [(scene, on_dev(scene), kw)]
     crops = []
