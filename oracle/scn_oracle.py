@@ -325,6 +325,19 @@ def pool_fwd(X, child, average):
     return Y
 
 
+def pool_bwd(X, Y, dY, parent, average, n_off):
+    """Backward of `pool_fwd` as the upstream kernels compute it, NOT as autograd differentiates `pool_fwd`:
+    max: dX[f] = dY[parent[f]] where X[f] == Y[parent[f]] as values, else 0 -- EVERY child that equals the cell's output
+    receives the full dY ([UPSTREAM-SCN] MaxPooling backward as recalled: `if (input == output) d_input += d_output` per
+    rule), where autograd through `torch.maximum` halves the gradient between equal inputs; after a ReLU an all-zero cell
+    hands dY to every child;  avg: dX[f] = dY[parent[f]] / n_off.
+    The two agree wherever no cell holds a tie (tests/test_stream_restate_cpu.py records the difference at a tie)."""
+    g = dY[_t(parent)]
+    if average:
+        return g / float(n_off)
+    return torch.where(X == Y[_t(parent)], g, torch.zeros_like(g))
+
+
 def split_batch(X, coords, batch_size):
     """custom_operations.py:24-39: per sample b the rows whose batch column equals b, in row order (a [B, N] bool mask
     `arange(B)[:, None] == coords[:, -1]` and one boolean index per sample)."""

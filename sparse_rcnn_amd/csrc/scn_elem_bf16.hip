@@ -1,8 +1,9 @@
 // bf16-STORAGE forms of the HBM-bound feature kernels (BASELINE configs 3-5): OutputLayer gather / segment sum, the ROI
 // feature gather (the same row gather), Max/AveragePooling, SparseToDense, AddTable, and the storage casts.  Slabs are
 // uint16 bf16 bit patterns; values are widened exactly, the arithmetic is the fp32 kernels' (scn_elem.hip), and every
-// result is rounded to bf16 ONCE (round-to-nearest-even, the rounding of torch's .to(torch.bfloat16)).  Half the bytes of
-// the fp32 forms: these kernels are pure streaming / row-gather passes, bound by HBM.
+// result is rounded to bf16 ONCE (round-to-nearest-even, the rounding of torch's .to(torch.bfloat16)); comparisons are of
+// the widened VALUES too (-0 == +0), never of bit patterns.  Half the bytes of the fp32 forms: these kernels are pure
+// streaming / row-gather passes, bound by HBM.
 #include "scn_common.h"
 
 using scn::S;
@@ -113,9 +114,10 @@ __global__ void k_pool_bwd_b(const us* __restrict__ X, const us* __restrict__ Y,
          i += (long long)gridDim.x * blockDim.x) {
         const long long f = i / c;
         const long long o = (long long)parent[f] * c + (int)(i - f * c);
-        // max: a stored maximum IS one of the stored inputs (a maximum is not rounded), so the bit patterns compare
+        // max: a stored maximum IS one of the stored inputs (a maximum is not rounded), so the comparison is exact -- but it
+        // is one of VALUES, as in k_pool_bwd: a -0 child equals a +0 output (bit patterns 0x8000 / 0x0000 do not)
         const int n_off = (avg >> 8) ? (avg >> 8) : 8;
-        dX[i] = (avg & 1) ? bn(bw(dY[o]) * (1.0f / (float)n_off)) : (X[i] == Y[o] ? dY[o] : (us)0);
+        dX[i] = (avg & 1) ? bn(bw(dY[o]) * (1.0f / (float)n_off)) : (bw(X[i]) == bw(Y[o]) ? dY[o] : (us)0);
     }
 }
 

@@ -757,8 +757,12 @@ def test_streaming_fp32_tile_kernel_agrees_with_the_k_split_kernel(gpu, c, targe
 
 
 def test_bf16_elementwise_forms_match_torch(gpu):
-    """scn_cast_* / scn_add_bf16 / scn_gather_rows_bf16 / scn_segment_sum_bf16 / pooling / SparseToDense in bf16 storage against
-    torch on the same bits (casts and gathers bit-exact; sums within one bf16 rounding of the fp64 sum)."""
+    """scn_cast_* / scn_add_bf16 / scn_gather_rows_bf16 / scn_segment_sum_bf16 against torch on the same bits, on 256-byte
+    aligned torch allocations of `randn` values at one size (5000 x 24 = 120 000 elements: every grid-stride loop runs once;
+    c = 24 takes the gather's 16-byte body; the 777 x 7 cast runs the VECTOR body's scalar tail, on an aligned pointer).
+    Casts, add and gather bit-exact; the segment sum is the fp64 sum rounded to fp32, then to bf16.
+    The scalar bodies behind misaligned pointers, the loops' second trip, the casts at rounding ties / overflow / NaN, and
+    bf16 pooling and SparseToDense are in tests/test_gpu_streaming.py."""
     from sparse_rcnn_amd import _lib as L
     lib = L.lib()
     g = torch.Generator().manual_seed(0)
