@@ -75,7 +75,8 @@ extern "C" {
  *      additive within 5: + scn_roialign_fwd / _bwd, scn_dense_maxpool_fwd / _bwd (156 entry points);
  *      additive within 5: + scn_anchor_up_fwd / _bwd (158 entry points);
  *      additive within 5: + scn_philox_words_host, scn_philox_fill, scn_sample_pack_drawn, scn_sample_cut_start (162 entry
- *      points) */
+ *      points);
+ *      additive within 5: + scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16 (166 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -1080,7 +1081,8 @@ int scn_sample_cut_start(const int32_t* discrete, int64_t n, const int32_t* size
                          uint64_t counter, int32_t* out8, scn_stream_t stream);
 
 /* ---- dense RoiAlign and the unclamped dense max pool of the reference's dense class branch (ndsis/modules/
- * roi_select_dense.py:28-141 RoiAlign with clip_boxes=True; nn.MaxPool3d(2)) -- csrc/scn_roialign.hip, fp32 ----
+ * roi_select_dense.py:28-141 RoiAlign with clip_boxes=True; nn.MaxPool3d(2)) -- csrc/scn_roialign.hip, fp32 (the bf16
+ * forms follow) ----
  * F fp32 [batch X Y Z][c], channels-last, row ((b X + x) Y + y) Z + z; size_host = (X, Y, Z) and extract_host = (ex, ey, ez),
  * each >= 2, int64 [3] on the HOST.  boxes fp32 [n_boxes][2][3] = (start, stop) in cells, already transformed and clipped to
  * [0, size - 1]; sample_of_box int32 [n_boxes], ascending, in 0 .. batch - 1.  Out fp32 [n_boxes ex ey ez][c], row
@@ -1108,6 +1110,31 @@ int scn_dense_maxpool_fwd(const float* X, int64_t n_boxes, const int64_t* extent
                           scn_stream_t stream);
 int scn_dense_maxpool_bwd(const float* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host, int c,
                           float* dX, scn_stream_t stream);
+
+/* ---- the same four calls on bf16-STORED slabs (the dense class branch under bf16 storage) -- csrc/scn_roialign.hip ----
+ * Arguments, layouts, range checks, launch counts and the n_boxes == 0 paths are those of the fp32 forms above; F, Out, dOut,
+ * dF, X, Y, dY, dX hold bf16 bit patterns (uint16_t).  boxes stay fp32, sample_of_box int32, and `table` is the same buffer,
+ * filled by the same kernels: the sample cells and weights are bit-identical to the fp32 call's, and a table written by
+ * either forward serves either backward.
+ * Arithmetic: every element is widened exactly when it is read; the products and sums are the fp32 kernels', in the same
+ * order (corner order and (wx * wy) * wz forward; the nested ordered gather over boxes, i, j, k backward; no atomics); the
+ * result is rounded to bf16 ONCE, at the store, to nearest even.  So each call's output equals the fp32 call's output on the
+ * widened inputs, rounded once, bit for bit.  scn_roialign_bwd_bf16 writes every cell of dF, +0 where no sample reads it
+ * (n_boxes == 0: one memset); reruns give identical bits.
+ * scn_dense_maxpool_fwd_bf16: the maximum of 8 bf16 children is one of them -- exact; the first child wins a tie, a NaN child
+ * wins, argmax is a uint8 per element.  scn_dense_maxpool_bwd_bf16: dY at that child, +0 at the other seven.
+ * Lanes are 16 bytes = 8 channels: c % 8 == 0 and 16-byte aligned feature pointers are REQUIRED (the storage rule of the Python
+ * side: a slab is bf16-stored only when its width is a multiple of 8); anything else returns SCN_EINVAL with a message before
+ * anything is launched.  Neither call waits for the host. */
+int scn_roialign_fwd_bf16(const uint16_t* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                          const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host, void* table, uint16_t* Out,
+                          scn_stream_t stream);
+int scn_roialign_bwd_bf16(const uint16_t* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch,
+                          const int64_t* size_host, int c, const int64_t* extract_host, uint16_t* dF, scn_stream_t stream);
+int scn_dense_maxpool_fwd_bf16(const uint16_t* X, int64_t n_boxes, const int64_t* extent_host, int c, uint16_t* Y,
+                               uint8_t* argmax, scn_stream_t stream);
+int scn_dense_maxpool_bwd_bf16(const uint16_t* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host, int c,
+                               uint16_t* dX, scn_stream_t stream);
 
 /* ---- the permutation half of the reference's up-sampling RPN heads (ndsis/modules/anchor_network.py:127-219
  * AnchorNetworkUpsample; anchor.py:167-192 rpn_permuter + rpn_bbox_score_splitter) -- csrc/scn_anchor_up.hip, fp32 ----

@@ -215,7 +215,12 @@ class DenseClassBranch(nn.Module):
     """forward(volume_slab [B X Y Z, feature_channels], size (X, Y, Z), batch, boxes) -> (class_scores [R, num_classes] fp32,
     (bbox_tensor [R, 2, 3] in cells, boxes per sample, size)): the middle entry is what ClassLossSelector / ClassPredictor read.
     boxes: list (one per sample) of fp32 [n, 2, 3] (start, stop) boxes in scene units; `stride` scene units per cell.
-    The branch computes in fp32, as ClassBranch does.
+    storage=torch.float32 (default): the branch computes in fp32, as ClassBranch does -- a bf16 volume is widened on entry.
+    storage=torch.bfloat16: the branch's slabs are bf16-STORED -- a bf16 volume is used as it is (an fp32 one is cast once: exact
+    when the RPN stack stored bf16), the input convolution, RoiAlign (scn_roialign_fwd_bf16), the max pool and the strided levels
+    run on bf16 slabs under `set_feature_storage(torch.bfloat16)` with fp32 accumulation, SparseGlobalPool widens the final rows,
+    and the linear layers and the scores are fp32.  Parameters, their gradients and the checkpoint maps do not change.  Every
+    width (feature_channels, input_channels, output_channels) must then be a multiple of 8, the bf16 lane.
 
     The box count changes every training step and the index structures of a fully active grid depend on its batch, so R is
     rounded up to a multiple of BOX_BUCKET and ONE Metadata is kept per bucket: the padding boxes' rows enter the first strided
@@ -224,8 +229,15 @@ class DenseClassBranch(nn.Module):
     they change no real box's result."""
 
     def __init__(self, feature_channels, stride, input_channels=32, output_channels=(64, 128), linear_channels=(64,),
-                 num_classes=18, num_units=1, cut_shape=(16, 16, 16)):
+                 num_classes=18, num_units=1, cut_shape=(16, 16, 16), storage=torch.float32):
         super().__init__()
+        if storage not in (torch.float32, torch.bfloat16):
+            raise ValueError("DenseClassBranch: storage is torch.float32 or torch.bfloat16")
+        widths = (feature_channels, input_channels) + tuple(output_channels)
+        if storage is torch.bfloat16 and any(int(w) % 8 for w in widths):
+            raise ValueError(f"DenseClassBranch(storage=torch.bfloat16): every width must be a multiple of 8 (16-byte lanes of "
+                             f"bf16 rows), got feature / input / output channels {widths}")
+        self.storage = storage
         self.stride, self.num_units = stride, int(num_units)
         self.cut_shape = tuple(int(c) for c in cut_shape)
         down = 2 ** (1 + len(output_channels))
@@ -271,16 +283,16 @@ class DenseClassBranch(nn.Module):
         from . import functional as F
         from .tensor import SparseConvNetTensor
         size = tuple(int(v) for v in size)
-        prev = M.set_feature_storage(torch.float32)
+        prev = M.set_feature_storage(self.storage)
         try:
-            if volume_slab.dtype != torch.float32:
-                volume_slab = volume_slab.float()
+            if volume_slab.dtype != self.storage:
+                volume_slab = volume_slab.to(self.storage)
             md = metadata if metadata is not None else self._metadata(size, batch, volume_slab.device)
             augmented = self.input_conv_layer(SparseConvNetTensor(volume_slab, md, torch.as_tensor(size, dtype=torch.long)))
             box_slab, selection = self.roi_getter.forward_slab(augmented.features, size, batch, boxes)
             r = selection[0].shape[0]
             if r == 0:
-                return volume_slab.new_zeros((0, self.num_classes)), selection
+                return volume_slab.new_zeros((0, self.num_classes), dtype=torch.float32), selection
             rb = self.bucket(r)
             half = tuple(c // 2 for c in self.cut_shape)
             pooled = F.DenseMaxPoolFunction.apply(box_slab, r, self.cut_shape, rb)

@@ -1,10 +1,14 @@
 // Dense RoiAlign (ndsis/modules/roi_select_dense.py:28-141 `RoiAlign` / `RoiAlignInner`, trilinear, clip_boxes=True) and the
 // unclamped dense 2^3/2 max pool (torch.nn.MaxPool3d(2)) behind it, on channels-last slabs (include/scn_mi355x.h:
-// scn_roialign_fwd, scn_roialign_bwd, scn_dense_maxpool_fwd, scn_dense_maxpool_bwd).  fp32 only.
+// scn_roialign_fwd, scn_roialign_bwd, scn_dense_maxpool_fwd, scn_dense_maxpool_bwd), fp32 slabs or bf16-STORED slabs (the
+// _bf16 forms): one set of kernels, templated on the element type.  A bf16 lane is 16 bytes = 8 channels; its elements are
+// widened exactly when they are read, every product and sum is the fp32 kernel's in the same order, and the result is rounded
+// to bf16 once, at the store (round to nearest even) -- a _bf16 call gives the fp32 call's output on the widened inputs,
+// rounded once, bit for bit.  The tables are the same buffer, filled by the same two kernels.
 //
 // Layout.  F [B X Y Z, C], row ((b X + x) Y + y) Z + z -- the slab of a fully active grid, what rpn.DenseRpn keeps.
 // Out [R ex ey ez, C], row ((r ex + i) ey + j) ez + k -- the slab of the fully active grid (ex, ey, ez) with batch R.  Lanes
-// run along C (4 channels per lane when C is a multiple of 4), so every corner read and every output write is one
+// run along C (4 fp32 channels per lane when C is a multiple of 4, 8 bf16 channels), so every corner read and every output write is one
 // contiguous row segment (C = 32: 128 B, eight lanes of 16 B).
 //
 // Coordinate table.  The sample positions depend on (box, axis, sample) only: k_roialign_table computes the R (ex + ey + ez)
@@ -98,27 +102,59 @@ __global__ void k_roialign_cells(int64_t n_boxes, Geo g, Tables tb) {
     }
 }
 
-template <int V> struct Vec;
-template <> struct Vec<1> {
+template <typename T, int V> struct Vec;         // one lane's V channels of a row of T, held as fp32
+template <> struct Vec<float, 1> {
     float v;
     __device__ static Vec load(const float* p) { return {*p}; }
     __device__ void store(float* p) const { *p = v; }
     __device__ static Vec zero() { return {0.f}; }
     __device__ void fma(float a, const Vec& x) { v += a * x.v; }
 };
-template <> struct Vec<4> {
+template <> struct Vec<float, 4> {
     float4 v;
     __device__ static Vec load(const float* p) { return {*reinterpret_cast<const float4*>(p)}; }
     __device__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
     __device__ static Vec zero() { return {make_float4(0.f, 0.f, 0.f, 0.f)}; }
     __device__ void fma(float a, const Vec& x) { v.x += a * x.v.x; v.y += a * x.v.y; v.z += a * x.v.z; v.w += a * x.v.w; }
 };
+// 8 bf16 bit patterns in one 16-byte lane: widened exactly by load, rounded to nearest even by store (the only rounding)
+__device__ __forceinline__ unsigned f32_to_bf16(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
+template <> struct Vec<uint16_t, 8> {
+    float v[8];
+    __device__ static Vec load(const uint16_t* p) {
+        const uint4 u = *reinterpret_cast<const uint4*>(p);
+        const unsigned w[4] = {u.x, u.y, u.z, u.w};
+        Vec r;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            r.v[2 * l] = __uint_as_float(w[l] << 16);
+            r.v[2 * l + 1] = __uint_as_float(w[l] & 0xffff0000u);
+        }
+        return r;
+    }
+    __device__ void store(uint16_t* p) const {
+        unsigned w[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) w[l] = f32_to_bf16(v[2 * l]) | (f32_to_bf16(v[2 * l + 1]) << 16);
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    __device__ static Vec zero() {
+        Vec r;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) r.v[l] = 0.f;
+        return r;
+    }
+    __device__ void fma(float a, const Vec& x) {
+#pragma unroll
+        for (int l = 0; l < 8; ++l) v[l] += a * x.v[l];
+    }
+};
 
 // one workgroup per (box, x sample): the x cells and weights are uniform; its ey * ez rows x C / V lanes in 32-bit arithmetic
-template <int V>
+template <typename T, int V>
 __global__ void __launch_bounds__(256)
-k_roialign_fwd(const float* __restrict__ F, Tables tb, const int32_t* __restrict__ sample_of_box, int cv, Geo g,
-               float* __restrict__ Out) {
+k_roialign_fwd(const T* __restrict__ F, Tables tb, const int32_t* __restrict__ sample_of_box, int cv, Geo g,
+               T* __restrict__ Out) {
     const int c = cv * V;
     const int i = (int)(blockIdx.x % (unsigned)g.ex);
     const int64_t r = blockIdx.x / (unsigned)g.ex;
@@ -132,7 +168,7 @@ k_roialign_fwd(const float* __restrict__ F, Tables tb, const int32_t* __restrict
         wxs[1] = tb.w[base + i]; wxs[0] = 1.f - wxs[1];
     }
     const unsigned items = (unsigned)g.ey * g.ez * cv;
-    float* out_plane = Out + (r * g.ex + i) * (int64_t)g.ey * g.ez * c;
+    T* out_plane = Out + (r * g.ex + i) * (int64_t)g.ey * g.ez * c;
     for (unsigned t = threadIdx.x; t < items; t += blockDim.x) {
         const unsigned row = t / (unsigned)cv, q = t - row * cv;
         const unsigned j = row / (unsigned)g.ez, k = row - j * g.ez;
@@ -144,7 +180,7 @@ k_roialign_fwd(const float* __restrict__ F, Tables tb, const int32_t* __restrict
             wys[1] = tb.w[ty]; wys[0] = 1.f - wys[1];
             wzs[1] = tb.w[tz]; wzs[0] = 1.f - wzs[1];
         }
-        Vec<V> acc = Vec<V>::zero();
+        Vec<T, V> acc = Vec<T, V>::zero();
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -157,7 +193,7 @@ k_roialign_fwd(const float* __restrict__ F, Tables tb, const int32_t* __restrict
                         wt = (wxs[a] * wys[bb]) * wzs[cc];
                     }
                     const int64_t cell = (((int64_t)b * g.X + xs[a]) * g.Y + ys[bb]) * g.Z + zs[cc];
-                    acc.fma(wt, Vec<V>::load(F + cell * c + q * V));
+                    acc.fma(wt, Vec<T, V>::load(F + cell * c + q * V));
                 }
         acc.store(out_plane + (int64_t)row * c + q * V);
     }
@@ -180,10 +216,10 @@ __device__ __forceinline__ float axis_weight(int l, int h, float wv, int cell) {
 constexpr int BWD_THREADS = 128;      // = the boxes whose x / y ranges one pass holds in LDS
 
 // grid (batch * X * Y, ceil(Z * cv / 128)): workgroup = one (sample, x, y) column, thread = one (z, channel group) of it
-template <int V>
+template <typename T, int V>
 __global__ void __launch_bounds__(BWD_THREADS)
-k_roialign_bwd(const float* __restrict__ dOut, Tables tb, const int32_t* __restrict__ sample_of_box, int64_t n_boxes, int cv, Geo g,
-               float* __restrict__ dF) {
+k_roialign_bwd(const T* __restrict__ dOut, Tables tb, const int32_t* __restrict__ sample_of_box, int64_t n_boxes, int cv, Geo g,
+               T* __restrict__ dF) {
     __shared__ int s_x0[BWD_THREADS], s_nx[BWD_THREADS], s_y0[BWD_THREADS], s_ny[BWD_THREADS];
     __shared__ int64_t s_range[2];
     const int c = cv * V;
@@ -197,7 +233,7 @@ k_roialign_bwd(const float* __restrict__ dOut, Tables tb, const int32_t* __restr
     if (threadIdx.x < 2) s_range[threadIdx.x] = lower_bound_i32(sample_of_box, n_boxes, b + (int)threadIdx.x);
     __syncthreads();
     const int64_t r0 = s_range[0], r1 = s_range[1];
-    Vec<V> total = Vec<V>::zero();
+    Vec<T, V> total = Vec<T, V>::zero();
     for (int64_t c0 = r0; c0 < r1; c0 += BWD_THREADS) {
         const int n_here = (int)(r1 - c0 < BWD_THREADS ? r1 - c0 : BWD_THREADS);
         __syncthreads();                                    // (the previous pass has been read)
@@ -219,16 +255,16 @@ k_roialign_bwd(const float* __restrict__ dOut, Tables tb, const int32_t* __restr
             const int32_t *lx = tb.lo + r * g.E, *hx = tb.hi + r * g.E;
             const int32_t *ly = lx + g.ex, *hy = hx + g.ex, *lz = ly + g.ey, *hz = hy + g.ey;
             const float *wx = tb.w + r * g.E, *wy = wx + g.ex, *wz = wy + g.ey;
-            Vec<V> si = Vec<V>::zero();
+            Vec<T, V> si = Vec<T, V>::zero();
             for (int i = x0; i < x0 + nx; ++i) {
                 const float ax = axis_weight(lx[i], hx[i], wx[i], x);
-                Vec<V> sj = Vec<V>::zero();
+                Vec<T, V> sj = Vec<T, V>::zero();
                 for (int j = y0; j < y0 + ny; ++j) {
                     const float ay = axis_weight(ly[j], hy[j], wy[j], y);
-                    Vec<V> sk = Vec<V>::zero();
-                    const float* row = dOut + ((((int64_t)r * g.ex + i) * g.ey + j) * g.ez) * c + q * V;
+                    Vec<T, V> sk = Vec<T, V>::zero();
+                    const T* row = dOut + ((((int64_t)r * g.ex + i) * g.ey + j) * g.ez) * c + q * V;
                     for (int k = k0; k < k0 + nk; ++k)
-                        sk.fma(axis_weight(lz[k], hz[k], wz[k], z), Vec<V>::load(row + (int64_t)k * c));
+                        sk.fma(axis_weight(lz[k], hz[k], wz[k], z), Vec<T, V>::load(row + (int64_t)k * c));
                     sj.fma(ay, sk);
                 }
                 si.fma(ax, sj);
@@ -240,9 +276,9 @@ k_roialign_bwd(const float* __restrict__ dOut, Tables tb, const int32_t* __restr
 }
 
 // one workgroup per (box, output x): its oy * oz rows x C / V lanes
-template <int V>
+template <typename T, int V>
 __global__ void __launch_bounds__(256)
-k_dense_maxpool_fwd(const float* __restrict__ X, int cv, int ox, int oy, int oz, float* __restrict__ Y,
+k_dense_maxpool_fwd(const T* __restrict__ X, int cv, int ox, int oy, int oz, T* __restrict__ Y,
                     uint8_t* __restrict__ arg) {
     const int c = cv * V;
     const unsigned i = blockIdx.x % (unsigned)ox;
@@ -251,32 +287,31 @@ k_dense_maxpool_fwd(const float* __restrict__ X, int cv, int ox, int oy, int oz,
     for (unsigned t = threadIdx.x; t < items; t += blockDim.x) {
         const unsigned row_in = t / (unsigned)cv, q = t - row_in * cv;
         const unsigned j = row_in / (unsigned)oz, k = row_in - j * oz;
-        float m[V];
+        Vec<T, V> best;                                    // (the maximum is one of the inputs: storing it rounds nothing)
+        float* m = reinterpret_cast<float*>(&best);
         uint8_t am[V];
 #pragma unroll
         for (int ch = 0; ch < 8; ++ch) {
             const int dx = ch >> 2, dy = (ch >> 1) & 1, dz = ch & 1;
             const int64_t in_row = ((r * (2 * ox) + 2 * i + dx) * (2 * oy) + 2 * j + dy) * (2 * oz) + 2 * k + dz;
-            const Vec<V> v = Vec<V>::load(X + in_row * c + q * V);
+            const Vec<T, V> v = Vec<T, V>::load(X + in_row * c + q * V);
             const float* vf = reinterpret_cast<const float*>(&v);
 #pragma unroll
             for (int l = 0; l < V; ++l)
                 if (ch == 0 || vf[l] > m[l] || vf[l] != vf[l]) { m[l] = vf[l]; am[l] = (uint8_t)ch; }
         }
         const int64_t o = (((r * ox + i) * oy + j) * oz + k) * c + q * V;
+        best.store(Y + o);
 #pragma unroll
-        for (int l = 0; l < V; ++l) {
-            Y[o + l] = m[l];
-            arg[o + l] = am[l];
-        }
+        for (int l = 0; l < V; ++l) arg[o + l] = am[l];
     }
 }
 
 // one workgroup per (box, input x): its 2 oy * 2 oz rows x C / V lanes
-template <int V>
+template <typename T, int V>
 __global__ void __launch_bounds__(256)
-k_dense_maxpool_bwd(const float* __restrict__ dY, const uint8_t* __restrict__ arg, int cv, int ox, int oy, int oz,
-                    float* __restrict__ dX) {
+k_dense_maxpool_bwd(const T* __restrict__ dY, const uint8_t* __restrict__ arg, int cv, int ox, int oy, int oz,
+                    T* __restrict__ dX) {
     const int c = cv * V;
     const unsigned x = blockIdx.x % (unsigned)(2 * ox);
     const int64_t r = blockIdx.x / (unsigned)(2 * ox);
@@ -287,8 +322,11 @@ k_dense_maxpool_bwd(const float* __restrict__ dY, const uint8_t* __restrict__ ar
         const int mine = (int)(((x & 1) << 2) | ((y & 1) << 1) | (z & 1));
         const int64_t o = (((r * ox + (x >> 1)) * oy + (y >> 1)) * oz + (z >> 1)) * c + q * V;
         const int64_t in = (((r * (2 * ox) + x) * (2 * oy) + y) * (2 * oz) + z) * c + q * V;
+        Vec<T, V> g = Vec<T, V>::load(dY + o);
+        float* gf = reinterpret_cast<float*>(&g);
 #pragma unroll
-        for (int l = 0; l < V; ++l) dX[in + l] = arg[o + l] == mine ? dY[o + l] : 0.f;
+        for (int l = 0; l < V; ++l) gf[l] = arg[o + l] == mine ? gf[l] : 0.f;
+        g.store(dX + in);
     }
 }
 
@@ -311,6 +349,20 @@ bool wide(int c, const void* a, const void* b) {
     return c % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0;
 }
 
+// bf16 rows have the 16-byte form only (8 channels per lane): the storage rule of modules.py -- a slab is bf16-stored only
+// when its width is a multiple of 8
+bool lanes_bf16(int c, const void* a, const void* b) {
+    return c % 8 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0;
+}
+#define SCN_REQUIRE_BF16_LANES(c, a, b)                                                                                     \
+    do {                                                                                                                    \
+        if (!lanes_bf16(c, a, b)) {                                                                                         \
+            snprintf(scn::g_err, sizeof(scn::g_err), "%s: bf16 rows need c %% 8 == 0 (got %d) and 16-byte aligned feature " \
+                     "pointers", __func__, (int)(c));                                                                       \
+            return SCN_EINVAL;                                                                                              \
+        }                                                                                                                   \
+    } while (0)
+
 int pool_geo(const int64_t* extent_host, int64_t n_boxes, int c, int* o) {
     SCN_REQUIRE(extent_host && n_boxes >= 0 && c >= 1);
     for (int d = 0; d < 3; ++d) {
@@ -318,6 +370,62 @@ int pool_geo(const int64_t* extent_host, int64_t n_boxes, int c, int* o) {
         o[d] = (int)(extent_host[d] / 2);
     }
     SCN_REQUIRE(n_boxes * extent_host[0] < (1ll << 31));                                          // one workgroup per (box, x)
+    return SCN_OK;
+}
+
+// The launches behind the entry points: rows of T in lanes of W elements when `wd` (16 bytes), else of N (fp32: 4 and 1, the
+// scalar form; bf16: 8 and 8 -- the entry point has refused every other row)
+template <typename T, int W, int N>
+int roialign_fwd(const T* F, const Geo& g, int c, bool wd, const float* boxes, const int32_t* sample_of_box, int64_t n_boxes,
+                 void* table, T* Out, scn_stream_t stream) {
+    const Tables tb = tables(table, n_boxes, g);
+    hipLaunchKernelGGL(k_roialign_table, dim3(scn::ew_grid(n_boxes * g.E, 256)), dim3(256), 0, scn::S(stream), boxes, n_boxes, g, tb);
+    SCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_roialign_cells, dim3(scn::ew_grid(n_boxes * g.S, 256)), dim3(256), 0, scn::S(stream), n_boxes, g, tb);
+    SCN_LAUNCH_CHECK();
+    const dim3 grid((unsigned)(n_boxes * g.ex));
+    if (wd)
+        hipLaunchKernelGGL((k_roialign_fwd<T, W>), grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c / W, g, Out);
+    else
+        hipLaunchKernelGGL((k_roialign_fwd<T, N>), grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c / N, g, Out);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+template <typename T, int W, int N>
+int roialign_bwd(const T* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch, const Geo& g, int c,
+                 bool wd, T* dF, scn_stream_t stream) {
+    const Tables tb = tables(const_cast<void*>(table), n_boxes, g);
+    const int cv = wd ? c / W : c / N;
+    SCN_REQUIRE(scn::cdiv((int64_t)g.Z * cv, BWD_THREADS) <= 65535);
+    const dim3 grid((unsigned)(batch * g.X * g.Y), (unsigned)scn::cdiv((int64_t)g.Z * cv, BWD_THREADS));
+    if (wd)
+        hipLaunchKernelGGL((k_roialign_bwd<T, W>), grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, tb, sample_of_box, n_boxes, cv, g, dF);
+    else
+        hipLaunchKernelGGL((k_roialign_bwd<T, N>), grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, tb, sample_of_box, n_boxes, cv, g, dF);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+template <typename T, int W, int N>
+int maxpool_fwd(const T* X, int64_t n_boxes, const int* o, int c, bool wd, T* Y, uint8_t* argmax, scn_stream_t stream) {
+    const dim3 grid((unsigned)(n_boxes * o[0]));
+    if (wd)
+        hipLaunchKernelGGL((k_dense_maxpool_fwd<T, W>), grid, dim3(256), 0, scn::S(stream), X, c / W, o[0], o[1], o[2], Y, argmax);
+    else
+        hipLaunchKernelGGL((k_dense_maxpool_fwd<T, N>), grid, dim3(256), 0, scn::S(stream), X, c / N, o[0], o[1], o[2], Y, argmax);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+template <typename T, int W, int N>
+int maxpool_bwd(const T* dY, const uint8_t* argmax, int64_t n_boxes, const int* o, int c, bool wd, T* dX, scn_stream_t stream) {
+    const dim3 grid((unsigned)(n_boxes * 2 * o[0]));
+    if (wd)
+        hipLaunchKernelGGL((k_dense_maxpool_bwd<T, W>), grid, dim3(256), 0, scn::S(stream), dY, argmax, c / W, o[0], o[1], o[2], dX);
+    else
+        hipLaunchKernelGGL((k_dense_maxpool_bwd<T, N>), grid, dim3(256), 0, scn::S(stream), dY, argmax, c / N, o[0], o[1], o[2], dX);
+    SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
 
@@ -331,18 +439,19 @@ extern "C" int scn_roialign_fwd(const float* F, int batch, const int64_t* size_h
     if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
     if (n_boxes == 0) return SCN_OK;
     SCN_REQUIRE(F && boxes && sample_of_box && table && Out);
-    const Tables tb = tables(table, n_boxes, g);
-    hipLaunchKernelGGL(k_roialign_table, dim3(scn::ew_grid(n_boxes * g.E, 256)), dim3(256), 0, scn::S(stream), boxes, n_boxes, g, tb);
-    SCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_roialign_cells, dim3(scn::ew_grid(n_boxes * g.S, 256)), dim3(256), 0, scn::S(stream), n_boxes, g, tb);
-    SCN_LAUNCH_CHECK();
-    const dim3 grid((unsigned)(n_boxes * g.ex));
-    if (wide(c, F, Out))
-        hipLaunchKernelGGL(k_roialign_fwd<4>, grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c / 4, g, Out);
-    else
-        hipLaunchKernelGGL(k_roialign_fwd<1>, grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c, g, Out);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    return roialign_fwd<float, 4, 1>(F, g, c, wide(c, F, Out), boxes, sample_of_box, n_boxes, table, Out, stream);
+}
+
+extern "C" int scn_roialign_fwd_bf16(const uint16_t* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                                     const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host, void* table,
+                                     uint16_t* Out, scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && c >= 1);
+    SCN_REQUIRE_BF16_LANES(c, F, Out);
+    Geo g;
+    if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(F && boxes && sample_of_box && table && Out);
+    return roialign_fwd<uint16_t, 8, 8>(F, g, c, true, boxes, sample_of_box, n_boxes, table, Out, stream);
 }
 
 extern "C" int scn_roialign_bwd(const float* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch,
@@ -357,17 +466,23 @@ extern "C" int scn_roialign_bwd(const float* dOut, const void* table, const int3
         return SCN_OK;
     }
     SCN_REQUIRE(dOut && table && sample_of_box);
-    const Tables tb = tables(const_cast<void*>(table), n_boxes, g);
-    const bool wd = wide(c, dOut, dF);
-    const int cv = wd ? c / 4 : c;
-    SCN_REQUIRE(scn::cdiv((int64_t)g.Z * cv, BWD_THREADS) <= 65535);
-    const dim3 grid((unsigned)(batch * g.X * g.Y), (unsigned)scn::cdiv((int64_t)g.Z * cv, BWD_THREADS));
-    if (wd)
-        hipLaunchKernelGGL(k_roialign_bwd<4>, grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, tb, sample_of_box, n_boxes, cv, g, dF);
-    else
-        hipLaunchKernelGGL(k_roialign_bwd<1>, grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, tb, sample_of_box, n_boxes, cv, g, dF);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    return roialign_bwd<float, 4, 1>(dOut, table, sample_of_box, n_boxes, batch, g, c, wide(c, dOut, dF), dF, stream);
+}
+
+extern "C" int scn_roialign_bwd_bf16(const uint16_t* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes,
+                                     int batch, const int64_t* size_host, int c, const int64_t* extract_host, uint16_t* dF,
+                                     scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && c >= 1 && dF);
+    SCN_REQUIRE_BF16_LANES(c, dOut, dF);
+    Geo g;
+    if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
+    const int64_t cells = (int64_t)batch * g.X * g.Y * g.Z;
+    if (n_boxes == 0) {
+        SCN_HIP(hipMemsetAsync(dF, 0, (size_t)cells * c * sizeof(uint16_t), scn::S(stream)));      // (+0 in bf16 too)
+        return SCN_OK;
+    }
+    SCN_REQUIRE(dOut && table && sample_of_box);
+    return roialign_bwd<uint16_t, 8, 8>(dOut, table, sample_of_box, n_boxes, batch, g, c, true, dF, stream);
 }
 
 extern "C" int scn_dense_maxpool_fwd(const float* X, int64_t n_boxes, const int64_t* extent_host, int c, float* Y,
@@ -376,13 +491,17 @@ extern "C" int scn_dense_maxpool_fwd(const float* X, int64_t n_boxes, const int6
     if (int rc = pool_geo(extent_host, n_boxes, c, o)) return rc;
     if (n_boxes == 0) return SCN_OK;
     SCN_REQUIRE(X && Y && argmax);
-    const dim3 grid((unsigned)(n_boxes * o[0]));
-    if (wide(c, X, Y))
-        hipLaunchKernelGGL(k_dense_maxpool_fwd<4>, grid, dim3(256), 0, scn::S(stream), X, c / 4, o[0], o[1], o[2], Y, argmax);
-    else
-        hipLaunchKernelGGL(k_dense_maxpool_fwd<1>, grid, dim3(256), 0, scn::S(stream), X, c, o[0], o[1], o[2], Y, argmax);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    return maxpool_fwd<float, 4, 1>(X, n_boxes, o, c, wide(c, X, Y), Y, argmax, stream);
+}
+
+extern "C" int scn_dense_maxpool_fwd_bf16(const uint16_t* X, int64_t n_boxes, const int64_t* extent_host, int c, uint16_t* Y,
+                                          uint8_t* argmax, scn_stream_t stream) {
+    int o[3];
+    if (int rc = pool_geo(extent_host, n_boxes, c, o)) return rc;
+    SCN_REQUIRE_BF16_LANES(c, X, Y);
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(X && Y && argmax);
+    return maxpool_fwd<uint16_t, 8, 8>(X, n_boxes, o, c, true, Y, argmax, stream);
 }
 
 extern "C" int scn_dense_maxpool_bwd(const float* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host, int c,
@@ -391,11 +510,15 @@ extern "C" int scn_dense_maxpool_bwd(const float* dY, const uint8_t* argmax, int
     if (int rc = pool_geo(extent_host, n_boxes, c, o)) return rc;
     if (n_boxes == 0) return SCN_OK;
     SCN_REQUIRE(dY && argmax && dX);
-    const dim3 grid((unsigned)(n_boxes * 2 * o[0]));
-    if (wide(c, dY, dX))
-        hipLaunchKernelGGL(k_dense_maxpool_bwd<4>, grid, dim3(256), 0, scn::S(stream), dY, argmax, c / 4, o[0], o[1], o[2], dX);
-    else
-        hipLaunchKernelGGL(k_dense_maxpool_bwd<1>, grid, dim3(256), 0, scn::S(stream), dY, argmax, c, o[0], o[1], o[2], dX);
-    SCN_LAUNCH_CHECK();
-    return SCN_OK;
+    return maxpool_bwd<float, 4, 1>(dY, argmax, n_boxes, o, c, wide(c, dY, dX), dX, stream);
+}
+
+extern "C" int scn_dense_maxpool_bwd_bf16(const uint16_t* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host,
+                                          int c, uint16_t* dX, scn_stream_t stream) {
+    int o[3];
+    if (int rc = pool_geo(extent_host, n_boxes, c, o)) return rc;
+    SCN_REQUIRE_BF16_LANES(c, dY, dX);
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(dY && argmax && dX);
+    return maxpool_bwd<uint16_t, 8, 8>(dY, argmax, n_boxes, o, c, true, dX, stream);
 }

@@ -1232,14 +1232,26 @@ def _host3(v):
     return h
 
 
+def _slab16(features, what):
+    """The slab of the two dense operators: fp32, or bf16 STORAGE -- 16-byte lanes of 8 channels, so a bf16 slab's width is a
+    multiple of 8 (modules.py stores no other width in bf16)."""
+    X = _feat(features)
+    if _is_bf16(X) and X.shape[1] % 8:
+        raise ValueError(f"{what}: a bf16-stored slab needs a width that is a multiple of 8, got {X.shape[1]}")
+    return X
+
+
 class RoiAlignFunction(torch.autograd.Function):
     """forward(F [B X Y Z, C] channels-last slab, boxes fp32 [R, 2, 3] transformed and clipped to the volume (cells),
     sample_of_box int32 [R] ascending, batch, size (X, Y, Z), extract (ex, ey, ez)) -> [R ex ey ez, C], the slab of the fully
-    active grid `extract` with batch R.  The backward is the library's ordered gather (no atomics): dF covers every cell."""
+    active grid `extract` with batch R.  The backward is the library's ordered gather (no atomics): dF covers every cell.
+    A bf16-stored slab (C a multiple of 8) gives a bf16 slab and a bf16 dF: the fp32 arithmetic on exactly widened values,
+    rounded once at the store; boxes and the table are the same."""
 
     @staticmethod
     def forward(ctx, features, boxes, sample_of_box, batch, size, extract):
-        X = _f32(features)
+        X = _slab16(features, "RoiAlign")
+        hb = _is_bf16(X)
         size, extract = tuple(int(s) for s in size), tuple(int(s) for s in extract)
         batch, r, c = int(batch), int(boxes.shape[0]), X.shape[1]
         if X.shape[0] != batch * size[0] * size[1] * size[2]:
@@ -1247,33 +1259,37 @@ class RoiAlignFunction(torch.autograd.Function):
         if tuple(boxes.shape) != (r, 2, 3) or sample_of_box.shape[0] != r or sample_of_box.dtype != torch.int32:
             raise ValueError("RoiAlign: boxes fp32 [R, 2, 3] and sample_of_box int32 [R] required")
         boxes = _f32(boxes)
-        out = _new((r * extract[0] * extract[1] * extract[2], c), X)
+        out = _new((r * extract[0] * extract[1] * extract[2], c), X, X.dtype)
         table = torch.empty(max(r, 1) * (3 * sum(extract) + 2 * sum(size)), dtype=torch.int32, device=X.device)
-        L.check(L.lib().scn_roialign_fwd(L.ptr(X), batch, _host3(size), c, L.ptr(boxes), L.ptr(sample_of_box), r,
-                                         _host3(extract), L.ptr(table), L.ptr(out), L.stream()))
+        fwd = L.lib().scn_roialign_fwd_bf16 if hb else L.lib().scn_roialign_fwd
+        L.check(fwd(L.ptr(X), batch, _host3(size), c, L.ptr(boxes), L.ptr(sample_of_box), r, _host3(extract), L.ptr(table),
+                    L.ptr(out), L.stream()))
         ctx.save_for_backward(table, sample_of_box)
-        ctx.cfg = (batch, size, extract, r, c)
+        ctx.cfg = (batch, size, extract, r, c, hb)
         return out
 
     @staticmethod
     def backward(ctx, dOut):
         table, sample_of_box = ctx.saved_tensors
-        batch, size, extract, r, c = ctx.cfg
-        dOut = _f32(dOut)
-        dF = _new((batch * size[0] * size[1] * size[2], c), dOut)
-        L.check(L.lib().scn_roialign_bwd(L.ptr(dOut), L.ptr(table), L.ptr(sample_of_box), r, batch, _host3(size), c,
-                                         _host3(extract), L.ptr(dF), L.stream()))
+        batch, size, extract, r, c, hb = ctx.cfg
+        dOut = dOut.to(torch.bfloat16).contiguous() if hb else _f32(dOut)
+        dF = _new((batch * size[0] * size[1] * size[2], c), dOut, dOut.dtype)
+        bwd = L.lib().scn_roialign_bwd_bf16 if hb else L.lib().scn_roialign_bwd
+        L.check(bwd(L.ptr(dOut), L.ptr(table), L.ptr(sample_of_box), r, batch, _host3(size), c, _host3(extract), L.ptr(dF),
+                    L.stream()))
         return dF, None, None, None, None, None
 
 
 class DenseMaxPoolFunction(torch.autograd.Function):
     """forward(X [R ex ey ez, C], n_boxes R, extent (ex, ey, ez) even, pad_boxes=0) -> [max(R, pad_boxes) ex/2 ey/2 ez/2, C]:
     the plain maximum of the 8 children (no clamp at 0, the first child on a tie: nn.MaxPool3d(2)); the rows of the boxes
-    R .. pad_boxes - 1 are zero and take no gradient (the class branch's box-count bucket)."""
+    R .. pad_boxes - 1 are zero and take no gradient (the class branch's box-count bucket).  fp32, or a bf16-stored slab (C a
+    multiple of 8) in and out: the maximum of bf16 values is one of them, so nothing is rounded."""
 
     @staticmethod
     def forward(ctx, features, n_boxes, extent, pad_boxes=0):
-        X = _f32(features)
+        X = _slab16(features, "DenseMaxPool")
+        hb = _is_bf16(X)
         extent = tuple(int(s) for s in extent)
         r, c = int(n_boxes), X.shape[1]
         if any(e % 2 or e < 2 for e in extent):
@@ -1282,22 +1298,24 @@ class DenseMaxPoolFunction(torch.autograd.Function):
             raise ValueError(f"DenseMaxPool: {X.shape[0]} rows are not {r} boxes of {extent}")
         per = (extent[0] // 2) * (extent[1] // 2) * (extent[2] // 2)
         rows = max(r, int(pad_boxes)) * per
-        Y = _new((rows, c), X)
+        Y = _new((rows, c), X, X.dtype)
         arg = torch.empty((r * per, c), dtype=torch.uint8, device=X.device)
-        L.check(L.lib().scn_dense_maxpool_fwd(L.ptr(X), r, _host3(extent), c, L.ptr(Y), L.ptr(arg), L.stream()))
+        fwd = L.lib().scn_dense_maxpool_fwd_bf16 if hb else L.lib().scn_dense_maxpool_fwd
+        L.check(fwd(L.ptr(X), r, _host3(extent), c, L.ptr(Y), L.ptr(arg), L.stream()))
         if rows > r * per:
             Y[r * per:].zero_()
         ctx.save_for_backward(arg)
-        ctx.cfg = (r, extent, c, per)
+        ctx.cfg = (r, extent, c, per, hb)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         (arg,) = ctx.saved_tensors
-        r, extent, c, per = ctx.cfg
-        dY = _f32(dY)
-        dX = _new((r * per * 8, c), dY)
-        L.check(L.lib().scn_dense_maxpool_bwd(L.ptr(dY), L.ptr(arg), r, _host3(extent), c, L.ptr(dX), L.stream()))
+        r, extent, c, per, hb = ctx.cfg
+        dY = dY.to(torch.bfloat16).contiguous() if hb else _f32(dY)
+        dX = _new((r * per * 8, c), dY, dY.dtype)
+        bwd = L.lib().scn_dense_maxpool_bwd_bf16 if hb else L.lib().scn_dense_maxpool_bwd
+        L.check(bwd(L.ptr(dY), L.ptr(arg), r, _host3(extent), c, L.ptr(dX), L.stream()))
         return dX, None, None, None
 
 

@@ -559,7 +559,8 @@ class RoiAlign(torch.nn.Module):
     reference's signature and return value: forward(featuremap [B, C, X, Y, Z], bbox_batch) -> (box_features
     [R, C, ex, ey, ez], (bbox_tensor, counts, scene_shape)).  A `torch.channels_last_3d` featuremap is used in place (its
     memory IS the slab [B X Y Z, C]); any other layout is copied once.  box_features is the permuted view of the
-    [R, ex, ey, ez, C] buffer the kernel wrote.
+    [R, ex, ey, ez, C] buffer the kernel wrote.  A bf16 featuremap (C a multiple of 8, else ValueError) gives bf16 box_features
+    -- the fp32 arithmetic on exactly widened values, rounded once; bbox_tensor, the counts and the shape do not depend on it.
 
     Only what the reference constructs is built (model.py:523-525: clip_boxes=True, no padding): with clip_boxes=False an
     unclipped negative coordinate WRAPS in the reference's advanced indexing (index -1 reads the last cell) -- behaviour nobody

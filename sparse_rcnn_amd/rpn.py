@@ -153,7 +153,9 @@ class DenseRpn(nn.Module):
         stack's output slab, (fp32 slab [B X Y Z, width], size, batch, pinned cell flags); engine "tiles" only.
         keep_volume (off: nothing changes): keep the stack's output volume -- after its last ReLU, before the head -- of the
         last forward as `self.volume` = (fp32 slab [B X Y Z, width], size, batch, its fully active Metadata): what the
-        reference's dense class branch reads (`class_output_anchor`, model.py:435-437).  Engine "tiles" only.
+        reference's dense class branch reads (`class_output_anchor`, model.py:435-437).  Engine "tiles" only.  The same
+        volume in the stack's stored dtype is `self.volume_stored`: the same tuple with a bf16 slab under autocast_bf16 --
+        widening it gives `volume` bit for bit -- and `volume` itself in fp32: what a bf16-stored class branch reads.
         keep_inside: return only the anchors that lie inside the scene (+ allowed_border), as the reference's
         `rpn_bbox_score_splitter` does (anchor.py:103-113,177-197; `allowed_border=0`, scannet_config/run.py:841) -- deltas,
         scores and anchors compacted in anchor order.  The reference's own shape is width 128 / 256 and num_dilations 5
@@ -162,6 +164,7 @@ class DenseRpn(nn.Module):
         self.engine = engine
         self.keep_inside, self.allowed_border = bool(keep_inside), float(allowed_border)
         self.keep_volume, self.volume = bool(keep_volume), None
+        self._stored = None                   # keep_volume: the stack's stored dtype, then `volume_stored`'s tuple once asked for
         self.channels, self.stride, self.width = int(channels), int(stride), int(width)
         self.to_dense = M.SparseToDense(3, self.channels)
         layers, cin = [], self.channels
@@ -181,8 +184,21 @@ class DenseRpn(nn.Module):
     def __getstate__(self):
         d = self.__dict__.copy()                 # (the fully active Metadata objects: device index structures, rebuilt on use)
         d["_dense_md"], d["_anchor_cache"], d["_flag_host"] = {}, {}, {}
-        d["volume"] = None
+        d["volume"] = d["_stored"] = None
         return d
+
+    @property
+    def volume_stored(self):
+        """`volume` with the slab in the dtype the stack stored it in (see __init__).  The stack's last ReLU is a stand-alone one
+        and runs on the widened slab (`_forward_tiles`; the library has no bf16 stand-alone ReLU), so the stored form is
+        `volume` narrowed back on first use: exact, every value of it is a bf16 value, and ReLU commutes with the exact
+        widening.  A forward that never asks launches nothing for it."""
+        if self._stored is None or self.volume is None:
+            return None
+        if not isinstance(self._stored, tuple):
+            x, size, B, dmd = self.volume
+            self._stored = (x if x.dtype == self._stored else x.to(self._stored), size, B, dmd)
+        return self._stored
 
     def anchors_for(self, shape, device):
         key = (tuple(shape), str(device))
@@ -269,11 +285,13 @@ class DenseRpn(nn.Module):
             x = M._conv_input(x, layer.in_channels, layer.out_channels, True)
             x = F.SubmanifoldConvolutionFunction.apply(x, W, layer.bias, dmd, ssz, 3, relu_in, None)
             relu_in = False
+        stored = x.dtype
         x = x.float()
         if relu_in:
             x = F.ReLUFunction.apply(x)
         if self.keep_volume:
             self.volume = (x, size, B, dmd)
+            self._stored = stored
         if self.head is None:
             return x, size, B, self._flags_to_host(flag)
         Wh = self.head.weight.reshape(self.head.out_channels, self.head.in_channels).t()
@@ -550,6 +568,10 @@ class MultiLevelRpn(nn.Module):
     @property
     def volume(self):
         return self.levels[self.class_output_index].volume
+
+    @property
+    def volume_stored(self):
+        return self.levels[self.class_output_index].volume_stored
 
     def forward(self, level_tensors):
         outs = [rpn(t) for rpn, t in zip(self.levels, level_tensors)]

@@ -91,8 +91,10 @@ class SparseStepModel(torch.nn.Module):
     """Backbone (+ mask branch for cfg3) as one module, so that one flat parameter buffer covers the step."""
 
     def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False, with_class=False,
-                 with_segmentation=False, upsample_heads=False):
-        """upsample_heads (with_rpn="reference" only; False: nothing changes): the reference's committed RPN heads,
+                 with_segmentation=False, upsample_heads=False, class_storage=None):
+        """class_storage (with_class="dense" on bf16 storage only; None: nothing changes): "bf16" builds the dense class branch
+        with storage=torch.bfloat16 and hands it the RPN's volume in its stored dtype (`rpn.volume_stored`).
+        upsample_heads (with_rpn="reference" only; False: nothing changes): the reference's committed RPN heads,
         rpn.AnchorNetworkUpsample with its extra strides and anchor groups, in place of the 1x1 heads.
         with_rpn: False | "stand-in" (cfg3-rpn: one anchor level, 2 x 32 stack) | "reference" (ref-crop-rpn: the reference's two
         anchor levels with 5 x 128 / 5 x 256 stacks, rpn.MultiLevelRpn).
@@ -108,6 +110,12 @@ class SparseStepModel(torch.nn.Module):
         self.mask = MaskBranch(channels[0], 7, bf16_blocks=storage) if with_mask else None
         self.rpn = self.roi_selector = None
         self.rpn_levels = None                 # indices of the encoder levels the RPN reads
+        if class_storage not in (None, "bf16"):
+            raise ValueError("class_storage: None | 'bf16'")
+        if class_storage and (with_class != "dense" or storage != "all"):
+            raise ValueError("class_storage='bf16' stores the DENSE class branch's slabs in bf16: it needs the dense arm "
+                             "(dense_class=True) on bf16 storage (dtype='bf16')")
+        self.class_storage = class_storage
         if upsample_heads and with_rpn != "reference":
             raise ValueError("upsample_heads=True needs with_rpn='reference' (the reference's two anchor levels)")
         if with_rpn == "reference" and upsample_heads:
@@ -144,7 +152,8 @@ class SparseStepModel(torch.nn.Module):
             if with_class == "dense":
                 src = self.rpn.levels[self.rpn.class_output_index] if hasattr(self.rpn, "levels") else self.rpn
                 self.class_level = self.rpn_levels[self.rpn.class_output_index if hasattr(self.rpn, "levels") else 0]
-                self.class_branch = DenseClassBranch(src.width, src.stride)
+                self.class_branch = DenseClassBranch(src.width, src.stride,
+                                                     **(dict(storage=torch.bfloat16) if class_storage else {}))
             else:
                 self.class_level = self.rpn_levels[-1]
                 self.class_branch = ClassBranch(channels[self.class_level], 2 ** self.class_level)
@@ -163,7 +172,7 @@ class SparseStepModel(torch.nn.Module):
         if isinstance(self.class_branch, DenseClassBranch):
             if self.rpn.volume is None:
                 raise L.ScnError("the dense class branch reads the RPN's kept volume: run_rpn first")
-            slab, size, batch, md = self.rpn.volume
+            slab, size, batch, md = self.rpn.volume_stored if self.class_storage else self.rpn.volume
             return self.class_branch(slab, size, batch, boxes, metadata=md)
         return self.class_branch(interims[self.class_level], boxes)
 
@@ -173,8 +182,12 @@ class SceneStep:
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
-                 upsample_heads=False):
-        """upsample_heads (`ref-crop-rpn` only; False: nothing changes): the RPN heads are the reference's committed ones
+                 upsample_heads=False, class_storage=None):
+        """class_storage (with dense_class=True and dtype="bf16"; None: nothing changes): "bf16" keeps the dense class branch's
+        slabs bf16-stored (classhead.DenseClassBranch(storage=torch.bfloat16): input convolution, RoiAlign, max pool and strided
+        levels on bf16 slabs with fp32 accumulation; linear layers and scores fp32) and hands it the RPN stack's volume as the
+        stack stored it, instead of widening the volume to an fp32 branch.
+        upsample_heads (`ref-crop-rpn` only; False: nothing changes): the RPN heads are the reference's committed ones
         (run.py:339 `upconvoluted_anchornetwork = True`): rpn.AnchorNetworkUpsample, per anchor level one transposed
         convolution per group of anchors that share an extra stride, so targets, draw, top-k and NMS see the reference's anchor
         set (182 272 anchors per 128 x 128 x 64 crop, 88 536 inside) instead of the 1x1 heads' 71 680; every loss, predict() and
@@ -236,6 +249,11 @@ class SceneStep:
             raise ValueError("class_loss=True needs an RPN in the step (the -rpn workloads)")
         if dense_class and not class_loss:
             raise ValueError("dense_class=True chooses the class branch's arm: it needs class_loss=True")
+        if class_storage not in (None, "bf16"):
+            raise ValueError("class_storage: None | 'bf16'")
+        if class_storage and not (dense_class and dtype == "bf16"):
+            raise ValueError("class_storage='bf16' needs dense_class=True and dtype='bf16'")
+        self.class_storage = class_storage
         if upsample_heads and workload != "ref-crop-rpn":
             raise ValueError("upsample_heads=True is the reference's RPN head: only ref-crop-rpn has its two anchor levels")
         if upsample_heads and dtype != "f32":
@@ -319,7 +337,8 @@ class SceneStep:
                                      batchnorm=workload.endswith("-bn"),
                                      with_class="dense" if self.dense_class else self.class_loss,
                                      with_segmentation=self.segmentation_loss,
-                                     **(dict(upsample_heads=True) if self.upsample_heads else {})).to(self.device)
+                                     **(dict(upsample_heads=True) if self.upsample_heads else {}),
+                                     **(dict(class_storage=class_storage) if class_storage else {})).to(self.device)
         if self.with_rpn:
             self._init_rpn()
         self.rpn_loss = bool(rpn_loss)
@@ -853,7 +872,10 @@ class SceneStep:
             cb = self.model.class_branch
             s += (("; the DENSE class branch (1^3 conv + 1 unit @32 on the stride-" + str(cb.stride) + " volume of the RPN's dilation "
                    "stack, RoiAlign to " + "x".join(map(str, cb.cut_shape)) + " (scn_roialign.hip), max pool 2 without clamp, "
-                   "2^3/2 conv + unit @64 and @128 on fully active box grids, mean pool, Linear 128-64-18) trains the stack too, "
+                   "2^3/2 conv + unit @64 and @128 on fully active box grids, mean pool, Linear 128-64-18" +
+                   (", its slabs bf16-STORED from the stack's stored volume to the mean pool (class_storage bf16: "
+                    "scn_roialign_fwd_bf16 / scn_dense_maxpool_fwd_bf16, fp32 accumulation, fp32 linear layers)"
+                    if self.class_storage else "") + ") trains the stack too, "
                    "on the reference's class loss: ") if self.dense_class else
                   ("; the class branch (SubM1 + 1 unit @32 on the stride-" + str(cb.stride) + " level, sparse "
                    "ROI cut, 2^3/2 conv + unit @64 and @128, mean pool, Linear 128-64-18) trains on the reference's class loss: "))

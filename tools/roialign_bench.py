@@ -4,7 +4,12 @@ volume 32 x 32 x 16 x 128 at stride 4, R = 32 drawn proposals + 8 ground-truth b
 the restatement run as torch operators on the same device tensors (tests/roialign_restate.py: advanced indexing + weighted sum,
 max_pool3d, conv3d, linear -- what the reference's dense arm executes).  Medians of alternating rounds, inputs resident.
 
-    python tools/roialign_bench.py [--out profiles/roialign.txt]
+--dtype bf16: the bf16-STORED forms (scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16,
+DenseClassBranch(storage=torch.bfloat16)) at the same shape on bf16-valued inputs, with the fp32 forms re-measured on the
+widened inputs in the alternating rounds of the same run (a comparison across runs would compare sessions); the torch
+restatement is not timed again.
+
+    python tools/roialign_bench.py [--dtype f32|bf16] [--out profiles/roialign.txt]
 """
 import argparse
 import os
@@ -41,11 +46,127 @@ def boxes_per_crop(rng, n, scene):
     return torch.from_numpy(np.stack([start, start + edge], 1))
 
 
+def _rate(nbytes, ms):
+    return (f"{nbytes / 1e6:.1f} MB in {ms:.4f} ms = {nbytes / ms / 1e9:.2f} TB/s = {100 * nbytes / ms / 1e-3 / HBM_ACHIEVABLE:.0f} % of "
+            f"the 6.3 TB/s a streaming kernel reaches")
+
+
+def bf16_against_f32(rounds):
+    """-> the record's lines: every bf16 form next to its fp32 twin, alternating rounds of one run."""
+    from sparse_rcnn_amd import roi
+    from sparse_rcnn_amd.classhead import DenseClassBranch
+    from sparse_rcnn_amd.functional import DenseMaxPoolFunction, RoiAlignFunction
+    dev, bf = torch.device("cuda"), torch.bfloat16
+    batch, size, stride, cut, c_vol, c = 12, (32, 32, 16), 4, (16, 16, 16), 128, 32
+    rng = np.random.default_rng(0)
+    bbox_batch = [boxes_per_crop(rng, 40, (128, 128, 64)).to(dev) for _ in range(batch)]
+    bbox, counts, assoc = roi.transform_boxes_interpolation(bbox_batch, size, True, stride)
+    r = bbox.shape[0]
+    sample = assoc.to(dev, torch.int32)
+    cells = batch * size[0] * size[1] * size[2]
+    g = torch.Generator().manual_seed(0)
+    lines = [f"shape: {batch} crops, volume {size[0]}x{size[1]}x{size[2]} cells at stride {stride}, R = {r} boxes (40 per crop, "
+             f"edges 8-96 voxels), cut 16^3, {c} channels; intermediate [R*4096, {c}]: fp32 {r * 4096 * c * 4 / 1e6:.1f} MB, bf16 "
+             f"{r * 4096 * c * 2 / 1e6:.1f} MB; inputs are bf16 values, the fp32 forms read them widened; medians of {rounds} "
+             f"alternating rounds (f32, bf16, f32, ...), 20 launches per round"]
+    med = lambda v: statistics.median(v)
+    fmt = lambda v: " ".join(f"{x:.4f}" for x in v)
+
+    # ---- the four kernels alone ----
+    F16 = torch.randn((cells, c), generator=g).to(dev).to(bf)
+    d16 = torch.randn((r * 4096, c), generator=g).to(dev).to(bf)
+    ops = {}
+    for name, F, dout in (("f32", F16.float(), d16.float()), ("bf16", F16, d16)):
+        a = F.clone().requires_grad_()
+        out = RoiAlignFunction.apply(a, bbox, sample, batch, size, cut)
+        b = out.detach().clone().requires_grad_()
+        pooled = DenseMaxPoolFunction.apply(b, r, cut)
+        dpool = dout[:pooled.shape[0]].contiguous()
+
+        def fwd(a=a):
+            return RoiAlignFunction.apply(a, bbox, sample, batch, size, cut)
+
+        def bwd(a=a, out=out, dout=dout):
+            a.grad = None
+            torch.autograd.backward([out], [dout], retain_graph=True)
+
+        def pool_fwd(b=b):
+            return DenseMaxPoolFunction.apply(b, r, cut)
+
+        def pool_bwd(b=b, pooled=pooled, dpool=dpool):
+            b.grad = None
+            torch.autograd.backward([pooled], [dpool], retain_graph=True)
+
+        es = F.element_size()
+        ops[name] = dict(fwd=fwd, bwd=bwd, pool_fwd=pool_fwd, pool_bwd=pool_bwd, out=out, pooled=pooled,
+                         bytes=dict(fwd=(out.numel() + F.numel()) * es, bwd=(dout.numel() + F.numel()) * es,
+                                    pool_fwd=(out.numel() + pooled.numel()) * es + pooled.numel(),
+                                    pool_bwd=(out.numel() + pooled.numel()) * es + pooled.numel()))
+    same = torch.equal(ops["bf16"]["out"], ops["f32"]["out"].to(bf)) and torch.equal(ops["bf16"]["pooled"].float(), ops["f32"]["pooled"].to(bf).float())
+    lines.append(f"bf16 forward == fp32 forward on the widened inputs, rounded once, and its max pool: {'equal bits' if same else 'DIFFERENT'}")
+    t = {(k, n): [] for k in ("fwd", "bwd", "pool_fwd", "pool_bwd") for n in ("f32", "bf16")}
+    for _ in range(rounds):
+        for k in ("fwd", "bwd", "pool_fwd", "pool_bwd"):
+            for n in ("f32", "bf16"):
+                t[(k, n)].append(timed(ops[n][k], 20))
+    what = {"fwd": "scn_roialign_fwd (output written once + volume read once)", "bwd": "scn_roialign_bwd (dOut read once + dF written once)",
+            "pool_fwd": "scn_dense_maxpool_fwd (input read, output + argmax written)",
+            "pool_bwd": "scn_dense_maxpool_bwd (dY + argmax read, dX written)"}
+    for k in ("fwd", "bwd", "pool_fwd", "pool_bwd"):
+        for n in ("f32", "bf16"):
+            lines.append(f"{what[k]} {n}: {_rate(ops[n]['bytes'][k], med(t[(k, n)]))} (rounds {fmt(t[(k, n)])})")
+        lines.append(f"  bf16 / f32 time: {med(t[(k, 'bf16')]) / med(t[(k, 'f32')]):.2f}")
+    del ops
+
+    # ---- the dense branch end to end ----
+    torch.manual_seed(0)
+    b32 = DenseClassBranch(c_vol, stride).to(dev)
+    b16 = DenseClassBranch(c_vol, stride, storage=bf).to(dev)
+    b16.load_state_dict(b32.state_dict())
+    v16 = torch.randn((cells, c_vol), generator=g).to(dev).to(bf)
+    gs = torch.randn((r, 18), generator=g).to(dev)
+
+    def run(branch, vol):
+        def f():
+            vol.grad = None
+            for p in branch.parameters():
+                p.grad = None
+            scores, _ = branch(vol, size, batch, bbox_batch)
+            torch.autograd.backward([scores], [gs])
+            return scores
+        return f
+
+    legs = {"fp32 branch, fp32 volume": run(b32, v16.float().requires_grad_()),
+            "fp32 branch, bf16 volume widened on entry (the island of a bf16 step)": run(b32, v16.clone().requires_grad_()),
+            "bf16-stored branch, bf16 volume": run(b16, v16.clone().requires_grad_())}
+    s = {k: f().detach() for k, f in legs.items()}
+    keys = list(legs)
+    lines.append(f"dense branch, scores bf16-stored vs fp32: max diff {float((s[keys[2]] - s[keys[0]]).abs().max()):.2e} "
+                 f"(scale {float(s[keys[0]].abs().max()):.3g})")
+    tb = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, f in legs.items():
+            tb[k].append(timed(f, 5, 2))
+    for k in keys:
+        lines.append(f"dense branch fwd + bwd (R = {r}, bucket {b32.bucket(r)}), {k}: median {med(tb[k]):.3f} ms (rounds "
+                     f"{' '.join(f'{x:.3f}' for x in tb[k])})")
+    lines.append(f"  bf16-stored / fp32 island: {med(tb[keys[2]]) / med(tb[keys[1]]):.2f}")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
     args = ap.parse_args()
+    if args.dtype == "bf16":
+        text = "\n".join(bf16_against_f32(args.rounds))
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     import roialign_restate as R
     from sparse_rcnn_amd import roi
     from sparse_rcnn_amd.classhead import DenseClassBranch, slab_to_conv3d_weight
