@@ -76,7 +76,8 @@ extern "C" {
  *      additive within 5: + scn_anchor_up_fwd / _bwd (158 entry points);
  *      additive within 5: + scn_philox_words_host, scn_philox_fill, scn_sample_pack_drawn, scn_sample_cut_start (162 entry
  *      points);
- *      additive within 5: + scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16 (166 entry points) */
+ *      additive within 5: + scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16 (166 entry points);
+ *      additive within 5: + scn_relu_fwd_bf16 / _bwd_bf16 (168 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -664,6 +665,11 @@ int scn_pad_params_many(int n, const float* const* in_host, float* const* out_ho
 int scn_cast_f32_to_bf16(const float* X, int64_t count, uint16_t* Y, scn_stream_t stream);
 int scn_cast_bf16_to_f32(const uint16_t* X, int64_t count, float* Y, scn_stream_t stream);
 int scn_add_bf16(const uint16_t* A, const uint16_t* B, int64_t count, uint16_t* Y, scn_stream_t stream);
+/* scn.ReLU on a bf16-stored slab (module_factory.py:581-611: the dilation stack's last ReLU).  Y[i] is the bf16 whose widening is
+ * scn_relu_fwd's result on the widened X[i] (exact: the result is X[i] or a zero); dX[i] = dY[i] bit for bit where the widened
+ * X[i] > 0, else +0 -- scn_relu_bwd's test.  count == 0: SCN_OK, no pointer is read. */
+int scn_relu_fwd_bf16(const uint16_t* X, int64_t count, uint16_t* Y, scn_stream_t stream);
+int scn_relu_bwd_bf16(const uint16_t* X, const uint16_t* dY, int64_t count, uint16_t* dX, scn_stream_t stream);
 int scn_gather_rows_bf16(const uint16_t* X, const int32_t* rows, int64_t m, int c, uint16_t* Y, scn_stream_t stream);
 int scn_segment_sum_bf16(const uint16_t* dY, const int32_t* item_row, int64_t n_items, int64_t n_rows, int c, uint16_t* dX,
                          double* acc64, scn_stream_t stream);

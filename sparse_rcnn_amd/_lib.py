@@ -131,6 +131,8 @@ _SIGS = {
     "scn_cast_f32_to_bf16": (C.c_int, [p, i64, p, p]),
     "scn_cast_bf16_to_f32": (C.c_int, [p, i64, p, p]),
     "scn_add_bf16": (C.c_int, [p, p, i64, p, p]),
+    "scn_relu_fwd_bf16": (C.c_int, [p, i64, p, p]),
+    "scn_relu_bwd_bf16": (C.c_int, [p, p, i64, p, p]),
     "scn_gather_rows_bf16": (C.c_int, [p, p, i64, i32, p, p]),
     "scn_segment_sum_bf16": (C.c_int, [p, p, i64, i64, i32, p, p, p]),
     "scn_pool_fwd_bf16": (C.c_int, [p, p, i64, i32, i32, p, p]),

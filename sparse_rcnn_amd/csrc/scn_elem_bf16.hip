@@ -54,6 +54,52 @@ __global__ void k_add_b(const us* __restrict__ a, const us* __restrict__ b, long
         y[i] = bn(bw(a[i]) + bw(b[i]));
 }
 
+// ---- stand-alone ReLU on a stored slab ------------------------------------------------------------------------------
+// The twins of k_ew<0> / k_ew<1> (scn_elem.hip) with the same expressions on the widened value: fwd fmaxf(u, 0.f), whose
+// result is u or a zero -- a bf16 value, so taking its upper 16 bits is exact; bwd copies dY's bits where u > 0.f, else +0.
+// 16-byte lanes of 8 elements when every pointer is 16-byte aligned (vec), a scalar tail; a scalar body otherwise.
+__device__ __forceinline__ us relu_b(us h) { return (us)(__float_as_uint(fmaxf(bw(h), 0.f)) >> 16); }
+__device__ __forceinline__ unsigned relu2_b(unsigned v) {                   // two elements of one 32-bit word
+    return (unsigned)relu_b((us)(v & 0xffffu)) | ((unsigned)relu_b((us)(v >> 16)) << 16);
+}
+__device__ __forceinline__ unsigned mask2_b(unsigned x, unsigned g) {
+    return (bw((us)(x & 0xffffu)) > 0.f ? (g & 0xffffu) : 0u) | (bw((us)(x >> 16)) > 0.f ? (g & 0xffff0000u) : 0u);
+}
+
+template <bool BWD>   // fwd: y = relu(a);  bwd: a = x, b = dy, y = dx
+__global__ void k_relu_b(const us* __restrict__ a, const us* __restrict__ b, long long count, us* __restrict__ y, int vec) {
+    const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    long long done = 0;
+    if (vec) {
+        const long long n8 = count >> 3;
+        for (long long i = tid; i < n8; i += stride) {
+            const uint4 u = ((const uint4*)a)[i];
+            uint4 r;
+            if (BWD) {
+                const uint4 g = ((const uint4*)b)[i];
+                r = make_uint4(mask2_b(u.x, g.x), mask2_b(u.y, g.y), mask2_b(u.z, g.z), mask2_b(u.w, g.w));
+            } else {
+                r = make_uint4(relu2_b(u.x), relu2_b(u.y), relu2_b(u.z), relu2_b(u.w));
+            }
+            ((uint4*)y)[i] = r;
+        }
+        done = n8 << 3;
+    }
+    for (long long i = done + tid; i < count; i += stride) y[i] = BWD ? (bw(a[i]) > 0.f ? b[i] : (us)0) : relu_b(a[i]);
+}
+
+template <bool BWD>
+static int relu_b_launch(const uint16_t* a, const uint16_t* b, int64_t count, uint16_t* y, scn_stream_t stream) {
+    SCN_REQUIRE(count >= 0);
+    if (count == 0) return SCN_OK;
+    SCN_REQUIRE(a && y && (!BWD || b));
+    const int vec = (((uintptr_t)a | (uintptr_t)y | (uintptr_t)b) & 15) == 0;
+    hipLaunchKernelGGL(k_relu_b<BWD>, dim3(scn::ew_grid(cdiv(count, 8), 256)), dim3(256), 0, S(stream), (const us*)a,
+                       (const us*)b, (long long)count, (us*)y, vec);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
 // ---- row gather (OutputLayer, ROI feature gather): a byte copy of 2c-byte rows ------------------------------------
 __global__ void k_gather_rows_b(const us* __restrict__ X, const int* __restrict__ rows, long long m, int c,
                                 us* __restrict__ Y, int vec) {
@@ -168,6 +214,14 @@ extern "C" int scn_add_bf16(const uint16_t* A, const uint16_t* B, int64_t count,
                        (long long)count, (us*)Y);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
+}
+
+extern "C" int scn_relu_fwd_bf16(const uint16_t* X, int64_t count, uint16_t* Y, scn_stream_t stream) {
+    return relu_b_launch<false>(X, nullptr, count, Y, stream);
+}
+
+extern "C" int scn_relu_bwd_bf16(const uint16_t* X, const uint16_t* dY, int64_t count, uint16_t* dX, scn_stream_t stream) {
+    return relu_b_launch<true>(X, dY, count, dX, stream);
 }
 
 extern "C" int scn_gather_rows_bf16(const uint16_t* X, const int32_t* rows, int64_t m, int c, uint16_t* Y,

@@ -968,18 +968,25 @@ class JoinedNetworkInNetworkFunction(torch.autograd.Function):
 class ReLUFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features):
-        X = _f32(features)
+        """fp32, or a bf16-STORED slab (scn_relu_fwd_bf16 / _bwd_bf16: result and gradient stay bf16, and widening either gives
+        the fp32 function's result on the widened input bit for bit)."""
+        X = _feat(features)
         _rec_relu(X)
         Y = torch.empty_like(X)
-        L.check(L.lib().scn_relu_fwd(L.ptr(X), X.numel(), L.ptr(Y), L.stream()))
+        fwd = L.lib().scn_relu_fwd_bf16 if _is_bf16(X) else L.lib().scn_relu_fwd
+        L.check(fwd(L.ptr(X), X.numel(), L.ptr(Y), L.stream()))
         ctx.save_for_backward(X)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         (X,) = ctx.saved_tensors
-        dY = _f32(dY)
         dX = torch.empty_like(X)
+        if _is_bf16(X):
+            dY = dY.to(torch.bfloat16).contiguous()
+            L.check(L.lib().scn_relu_bwd_bf16(L.ptr(X), L.ptr(dY), X.numel(), L.ptr(dX), L.stream()))
+            return dX
+        dY = _f32(dY)
         L.check(L.lib().scn_relu_bwd(L.ptr(X), L.ptr(dY), X.numel(), L.ptr(dX), L.stream()))
         return dX
 

@@ -34,7 +34,7 @@ def _out(input, features, spatial_size=None):
 # 513-578) knows nothing about storage types; `scn.set_feature_storage(torch.bfloat16)` switches every tree built on this
 # package to bf16-STORED feature slabs (BASELINE configs 3-5; parameters, their gradients and all accumulation stay fp32):
 # a conv-type layer whose output width is a multiple of 8 stores its result in the storage type, and a layer the bf16 entry
-# points do not serve (input width no multiple of 8 on the tile kernels, batch norm, a stand-alone ReLU) widens its input.
+# points do not serve (input width no multiple of 8 on the tile kernels, batch norm) and the scn.ReLU module widen their input.
 # With the default (torch.float32) nothing changes.
 # ----------------------------------------------------------------------------------------------------------------------
 FEATURE_STORAGE = torch.float32
@@ -395,8 +395,9 @@ class Identity(Module):
 
 
 def _wide(x):
-    """Layers without a bf16 entry point (stand-alone ReLU, AddTable outside a residual unit, batch norm) widen bf16-stored
-    rows; the next conv-type layer stores its result in the tree's storage type again."""
+    """Layers that run on widened rows (AddTable outside a residual unit, batch norm, and the scn.ReLU module: the library's
+    bf16 stand-alone ReLU, functional.ReLUFunction on a bf16 slab, serves the RPN stack's tail, rpn.DenseRpn) widen
+    bf16-stored rows; the next conv-type layer stores its result in the tree's storage type again."""
     return x.float() if x.dtype == torch.bfloat16 else x
 
 

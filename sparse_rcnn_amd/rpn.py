@@ -150,7 +150,9 @@ class DenseRpn(nn.Module):
     def __init__(self, channels, stride=8, width=32, num_dilations=2, anchors=DEFAULT_ANCHORS, autocast_bf16=False, engine=None,
                  keep_inside=True, allowed_border=0, keep_volume=False, with_head=True):
         """with_head=False (MultiLevelRpn with up-sampling heads): no 1x1 head is constructed and `forward` hands over the
-        stack's output slab, (fp32 slab [B X Y Z, width], size, batch, pinned cell flags); engine "tiles" only.
+        stack's output slab, (fp32 slab [B X Y Z, width], size, batch, pinned cell flags); engine "tiles" only.  On a
+        bf16-stored level tensor the stack stays bf16-stored through its last ReLU (functional.ReLUFunction on the bf16 slab) and the slab
+        handed over is that result widened: the heads' row GEMM, P, the scatter and rpn_bbox / rpn_score are fp32.
         keep_volume (off: nothing changes): keep the stack's output volume -- after its last ReLU, before the head -- of the
         last forward as `self.volume` = (fp32 slab [B X Y Z, width], size, batch, its fully active Metadata): what the
         reference's dense class branch reads (`class_output_anchor`, model.py:435-437).  Engine "tiles" only.  The same
@@ -189,10 +191,11 @@ class DenseRpn(nn.Module):
 
     @property
     def volume_stored(self):
-        """`volume` with the slab in the dtype the stack stored it in (see __init__).  The stack's last ReLU is a stand-alone one
-        and runs on the widened slab (`_forward_tiles`; the library has no bf16 stand-alone ReLU), so the stored form is
-        `volume` narrowed back on first use: exact, every value of it is a bf16 value, and ReLU commutes with the exact
-        widening.  A forward that never asks launches nothing for it."""
+        """`volume` with the slab in the dtype the stack stored it in (see __init__).  Behind a 1x1 head the stack's last,
+        stand-alone ReLU runs on the widened slab (`_forward_tiles`), so the stored form is `volume` narrowed back on first
+        use: exact, every value of it is a bf16 value, and ReLU commutes with the exact widening; a forward that never asks
+        launches nothing for it.  With up-sampling heads (with_head=False) that ReLU runs on the bf16 slab itself
+        (scn_relu_fwd_bf16) and the stored form is its output tensor: no cast, connected to autograd."""
         if self._stored is None or self.volume is None:
             return None
         if not isinstance(self._stored, tuple):
@@ -286,6 +289,15 @@ class DenseRpn(nn.Module):
             x = F.SubmanifoldConvolutionFunction.apply(x, W, layer.bias, dmd, ssz, 3, relu_in, None)
             relu_in = False
         stored = x.dtype
+        if self.head is None and relu_in and stored == torch.bfloat16:
+            # up-sampling heads behind a bf16-stored stack: the pending ReLU runs on the stored slab (scn_relu_fwd_bf16), and its
+            # result r IS the stored volume; the heads' fp32 slab is r widened -- relu(widen(x)) bit for bit
+            r = F.ReLUFunction.apply(x)
+            x = r.float()
+            if self.keep_volume:
+                self.volume = (x, size, B, dmd)
+                self._stored = (r, size, B, dmd)
+            return x, size, B, self._flags_to_host(flag)
         x = x.float()
         if relu_in:
             x = F.ReLUFunction.apply(x)
@@ -552,8 +564,6 @@ class MultiLevelRpn(nn.Module):
                                     for i, (c, stride, width, a) in enumerate(levels))
         self.anchor_network = None
         if up:
-            if autocast_bf16:
-                raise ValueError("MultiLevelRpn: the up-sampling heads run on the fp32 slab of engine 'tiles'")
             self.anchor_network = AnchorNetworkUpsample([a for _, _, _, a in levels], [s for _, s, _, _ in levels],
                                                         [w for _, _, w, _ in levels], allowed_border,
                                                         extra_stride_levels=extra_stride_levels)

@@ -95,7 +95,8 @@ class SparseStepModel(torch.nn.Module):
         """class_storage (with_class="dense" on bf16 storage only; None: nothing changes): "bf16" builds the dense class branch
         with storage=torch.bfloat16 and hands it the RPN's volume in its stored dtype (`rpn.volume_stored`).
         upsample_heads (with_rpn="reference" only; False: nothing changes): the reference's committed RPN heads,
-        rpn.AnchorNetworkUpsample with its extra strides and anchor groups, in place of the 1x1 heads.
+        rpn.AnchorNetworkUpsample with its extra strides and anchor groups, in place of the 1x1 heads.  On bf16-stored
+        level tensors the stacks' last ReLU runs on the bf16 slab and the heads read its result widened (fp32 row GEMM, P and scatter).
         with_rpn: False | "stand-in" (cfg3-rpn: one anchor level, 2 x 32 stack) | "reference" (ref-crop-rpn: the reference's two
         anchor levels with 5 x 128 / 5 x 256 stacks, rpn.MultiLevelRpn).
         with_class: the reference's class branch (classhead.ClassBranch) on the coarsest RPN level of the encoder -- the
@@ -120,12 +121,11 @@ class SparseStepModel(torch.nn.Module):
             raise ValueError("upsample_heads=True needs with_rpn='reference' (the reference's two anchor levels)")
         if with_rpn == "reference" and upsample_heads:
             from .rpn import MultiLevelRpn, RoiSelector, REF_EXTRA_STRIDE_LEVELS, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS
-            if storage:
-                raise ValueError("upsample_heads=True runs the RPN in fp32 (dtype f32)")
             self.rpn_levels = (2, 3)
             self.rpn = MultiLevelRpn([(channels[2], 4, 128, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS[0]),
                                       (channels[3], 8, 256, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS[1])], num_dilations=5,
                                      extra_stride_levels=REF_EXTRA_STRIDE_LEVELS,
+                                     **(dict(autocast_bf16=True) if storage else {}),
                                      **(dict(keep_volume=True) if with_class == "dense" else {}))
             self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:847-853: 1024 / 256 / 0.5
         elif with_rpn == "reference":
@@ -191,7 +191,9 @@ class SceneStep:
         (run.py:339 `upconvoluted_anchornetwork = True`): rpn.AnchorNetworkUpsample, per anchor level one transposed
         convolution per group of anchors that share an extra stride, so targets, draw, top-k and NMS see the reference's anchor
         set (182 272 anchors per 128 x 128 x 64 crop, 88 536 inside) instead of the 1x1 heads' 71 680; every loss, predict() and
-        evaluate() run on it without further switches.  fp32 only.
+        evaluate() run on it without further switches.  Any dtype: where the RPN's level tensors are bf16-stored (dtype "bf16")
+        the dilation stacks stay bf16-stored through their last ReLU (scn_relu_fwd_bf16); the heads' row GEMM, P, the scatter
+        and rpn_bbox / rpn_score are fp32, as behind the 1x1 heads.
         step_group: run the fp32 weight gradients of a step as one grid per kernel variant after the last backward pass
         (executor.step_weight_gradients; one rank, no gradient buckets).  It keeps every stage's workspaces and unit slabs alive
         until then -- the cfg2 step's working set grows from 1.04 to 2.03 GB -- so False is the way to fit a scene that only fits
@@ -256,8 +258,6 @@ class SceneStep:
         self.class_storage = class_storage
         if upsample_heads and workload != "ref-crop-rpn":
             raise ValueError("upsample_heads=True is the reference's RPN head: only ref-crop-rpn has its two anchor levels")
-        if upsample_heads and dtype != "f32":
-            raise ValueError("upsample_heads=True runs the RPN in fp32 (dtype f32)")
         self.upsample_heads = bool(upsample_heads)
         if segmentation_loss and not nb:
             raise ValueError("segmentation_loss=True needs a workload with boxes (cfg3, cfg3-rpn, ref-crop-rpn): the labels "
@@ -843,7 +843,10 @@ class SceneStep:
                        "AnchorNetworkUpsample heads: upsample_heads=True " if up is None else
                        "; the reference's AnchorNetworkUpsample heads (run.py:339,532-537): per level one transposed "
                        "convolution with kernel = stride per group of anchors, as one row GEMM + one scatter "
-                       "(scn_anchor_up.hip) ") + sel)
+                       "(scn_anchor_up.hip)"
+                       + (", behind a bf16-STORED stack whose last ReLU runs on the bf16 slab (scn_relu_fwd_bf16 / _bwd_bf16); "
+                          "the heads' row GEMM, P, the scatter and rpn_bbox / rpn_score are fp32 "
+                          if self.dtype == "bf16" else " ")) + sel)
             else:
                 eng = r.engine or r.ENGINE
                 s += (f"; + RPN boundary INSIDE the step, a STAND-IN lighter than the reference's (one anchor level, 2 x {r.width} "
