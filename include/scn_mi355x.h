@@ -77,7 +77,8 @@ extern "C" {
  *      additive within 5: + scn_philox_words_host, scn_philox_fill, scn_sample_pack_drawn, scn_sample_cut_start (162 entry
  *      points);
  *      additive within 5: + scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16 (166 entry points);
- *      additive within 5: + scn_relu_fwd_bf16 / _bwd_bf16 (168 entry points) */
+ *      additive within 5: + scn_relu_fwd_bf16 / _bwd_bf16 (168 entry points);
+ *      additive within 5: + scn_wgrad_plan_describe (169 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -477,6 +478,20 @@ int scn_wgrad_bias_rules2(const float* X0, const float* dY0, const float* X1, co
  * convolutions of two stacked residual units (module_factory.py:513-530 `num_units=2`) in one launch.
  * dW = [n_prob][n_off][cin][cout], db = [n_prob][cout] or NULL with db_offsets == 0. */
 int64_t scn_wgrad_scratch_bytes_n(int cin, int cout, const int64_t* prefix_host, int n_off, int n_prob);
+/* Which path a weight-gradient call takes (host only: launches nothing, allocates nothing; tests and tools).  The launcher
+ * and the scratch sizes above take every decision from the function that fills this report.
+ *   n_prob 1: the single-problem entry points; 2 ... 4: the _rules2 / _rules_n forms.  bf16_storage: the _bf16 forms.
+ *   operand_ptr_bits: the low 4 bits of the OR of every operand pointer (X, dY of all problems); out_ptr_bits: of dW | scratch.
+ *   out[0]  kernel: 0 k_wgrad_direct (fp32 MFMA), 1 k_wgrad_tb (bf16 MFMA)
+ *   out[1], out[2]  16-channel tiles of a wave along Cin / Cout (TA, TB)
+ *   out[3] QUAD  out[4] EDGE  out[5] EDGE with vector row pieces  out[6] bf16 rows on the fp32-MFMA kernel (HB)
+ *   out[7]  rules per unit  out[8] units  out[9], out[10] workgroup blocks along Cin / Cout
+ *   out[11], out[12]  unit sum: channels per thread (4 or 1), threads per element
+ *   out[13]  scratch bytes the call writes without db, out[14] with db (both <= the scn_wgrad_scratch_bytes* of the call)
+ *   out[15]  1: no rules at all -- dW and db are cleared by memsets, no kernel runs
+ * SCN_EINVAL for arguments the launcher rejects (operand pointers not aligned to their element type among them). */
+int scn_wgrad_plan_describe(int cin, int cout, const int64_t* prefix_host, int n_off, int n_prob, int bf16_storage,
+                            int operand_ptr_bits, int out_ptr_bits, int64_t out[16]);
 int scn_wgrad_bias_rules_n(const float* const* Xs, const float* const* dYs, int n_prob, int cin, int cout,
                           const int32_t* in_rows, const int32_t* out_rows, const int64_t* prefix_host, int n_off,
                           float* dW, float* db, uint32_t db_offsets, void* scratch, int flags, scn_stream_t stream);

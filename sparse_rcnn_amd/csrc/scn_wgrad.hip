@@ -647,22 +647,6 @@ int make_dplan(int cin, int cout, const int64_t* prefix_host, int n_off, DPlan& 
 }
 }  // namespace
 
-extern "C" int64_t scn_wgrad_scratch_bytes(int cin, int cout, const int64_t* prefix_host, int n_off) {
-    if (!prefix_host || n_off < 1 || n_off > 32 || cin < 1 || cout < 1) return -1;
-    // the largest of the plans a call may use: fp32 rows (v = 0), bf16-stored rows on the fp32-MFMA kernel (v = 1: other
-    // block shapes than v = 0 where 48-wide blocks apply), bf16-MFMA kernel (v = 2)
-    int64_t best = -1;
-    for (int v = 0; v < 3; ++v) {
-        if (v == 2 && !tb_usable(cin, cout)) continue;
-        DPlan pl;
-        if (make_dplan(cin, cout, prefix_host, n_off, pl, v == 2, v == 1) != SCN_OK) return -1;
-        const int64_t b = (int64_t)pl.unit_start[n_off] *
-                              ((int64_t)pl.nbi * pl.nbj * pl.cbi * pl.cbj + (int64_t)pl.nbj * pl.cbj) * (int64_t)sizeof(float) + 512;
-        if (b > best) best = b;
-    }
-    return best;
-}
-
 // n_prob problems on one rule list: n_prob x n_off virtual offsets, problem p's rules behind those of problem p - 1 in the
 // virtual rule space; dW = [n_prob][n_off][cin][cout], db = [n_prob][cout].
 static int multi_problem_plan(int cin, int cout, const int64_t* prefix_host, int n_off, int n_prob, DPlan& pl,
@@ -676,6 +660,88 @@ static int multi_problem_plan(int cin, int cout, const int64_t* prefix_host, int
     pl.n_real = n_off;
     pl.p_rules = P;
     return rc;
+}
+
+// Everything the host decides about one call -- the ONE place it is decided: wgrad_impl launches what this says, the scratch
+// sizes are the largest of what it says for the operand kinds a caller may pass, scn_wgrad_plan_describe reports it.
+//   ptr_bits: low 4 bits of the OR of every operand pointer (X, dY of all problems); out_bits: of dW | scratch.
+struct WdPath {
+    DPlan pl;
+    bool mfma16;                        // k_wgrad_tb (bf16 MFMA); else k_wgrad_direct
+    int ta, tb;                         // k_wgrad_direct: 16-channel tiles of a wave block; k_wgrad_tb: tiles per wave
+    bool quad, edge, evec, hb;          // k_wgrad_direct<.., QUAD, EDGE, .., HB>, vector row pieces of an EDGE launch
+    int V, G;                           // unit sum: channels per thread, threads per element group
+    int cout_pad;
+    int64_t slab_floats, db_floats;     // scratch: the unit blocks, then (calls with db) the units' column sums
+};
+
+static int plan_path(int cin, int cout, const int64_t* prefix_host, int n_off_real, int n_prob, bool hb, unsigned ptr_bits,
+                     unsigned out_bits, WdPath& w) {
+    const int n_off = n_prob * n_off_real;                                   // (virtual) offsets of the launch
+    w.mfma16 = hb && tb_usable(cin, cout) && ((ptr_bits & 15) == 0);
+    const int rc = n_prob > 1 ? multi_problem_plan(cin, cout, prefix_host, n_off_real, n_prob, w.pl, w.mfma16, hb)
+                              : make_dplan(cin, cout, prefix_host, n_off, w.pl, w.mfma16, hb);
+    if (rc != SCN_OK) return rc;
+    const DPlan& pl = w.pl;
+    const Shape sh = pick_shape(cin, cout, hb);
+    // vector row pieces need aligned rows and whole blocks; anything else takes the element-wise (EDGE) instantiation
+    const bool edge = (cin % (16 * sh.ta) != 0) || (cout % (16 * sh.tb) != 0) ||
+                      ((ptr_bits & (sh.ta == 3 ? 3 : 15)) != 0);
+    // EDGE blocks whose fragments are whole (vector loads stay possible, see k_wgrad_direct)
+    const bool evec = edge && !hb && cin % sh.ta == 0 && cout % sh.tb == 0 && (ptr_bits & 15) == 0 &&
+                      (cin * 4) % 16 == 0 && (cout * 4) % 16 == 0 && !scn::sw(scn::SW_WD_NO_EVEC).set;
+    if (w.mfma16) {
+        w.ta = tb_tiles(cin); w.tb = tb_tiles(cout);
+        w.quad = w.edge = w.evec = w.hb = false;
+    } else {
+        w.ta = sh.ta; w.tb = sh.tb; w.quad = sh.quad; w.hb = hb;
+        w.edge = edge && sh.ta != 3;             // (48-wide blocks: one instantiation, whole fragments by construction)
+        w.evec = evec && sh.ta != 3;
+    }
+    // sum of the units: V output channels per thread, G threads per element group so that ~>= 128k threads run
+    w.V = (cout % 4 == 0 && (out_bits & 15) == 0) ? 4 : 1;
+    const int64_t groups = (int64_t)n_off * cin * (cout / w.V);
+    w.G = 1;
+    while (w.G < 16 && groups * w.G < 128 * 1024) w.G *= 2;
+    w.cout_pad = pl.nbj * pl.cbj;
+    w.slab_floats = (int64_t)pl.unit_start[n_off] * pl.nbi * pl.nbj * pl.cbi * pl.cbj;
+    w.db_floats = (int64_t)pl.unit_start[n_off] * w.cout_pad;
+    return SCN_OK;
+}
+
+// Scratch of a call: the largest of the plans it may run under -- fp32 rows (v = 0), bf16-stored rows on the fp32-MFMA kernel
+// (v = 1: misaligned rows, or channel counts the bf16-MFMA kernel does not take; other block shapes than v = 0 where 48-wide
+// blocks apply), bf16-MFMA kernel (v = 2) -- with bias partial sums, whatever the alignment of dW and scratch.
+static int64_t scratch_bytes_impl(int cin, int cout, const int64_t* prefix_host, int n_off, int n_prob) {
+    int64_t best = -1;
+    for (int v = 0; v < 3; ++v) {
+        WdPath w;
+        if (plan_path(cin, cout, prefix_host, n_off, n_prob, v != 0, v == 1 ? 2u : 0u, 0u, w) != SCN_OK) return -1;
+        const int64_t b = (w.slab_floats + w.db_floats) * (int64_t)sizeof(float) + 512;
+        if (b > best) best = b;
+    }
+    return best;
+}
+
+extern "C" int64_t scn_wgrad_scratch_bytes(int cin, int cout, const int64_t* prefix_host, int n_off) {
+    if (!prefix_host || n_off < 1 || n_off > 32 || cin < 1 || cout < 1) return -1;
+    return scratch_bytes_impl(cin, cout, prefix_host, n_off, 1);
+}
+
+extern "C" int scn_wgrad_plan_describe(int cin, int cout, const int64_t* prefix_host, int n_off, int n_prob, int bf16_storage,
+                                       int operand_ptr_bits, int out_ptr_bits, int64_t out[16]) {
+    SCN_REQUIRE(prefix_host && out && n_off >= 1 && n_off <= 32 && cin >= 1 && cout >= 1);
+    SCN_REQUIRE(n_prob >= 1 && n_prob <= WD_MAX_PROB);
+    SCN_REQUIRE((operand_ptr_bits & (bf16_storage ? 1 : 3)) == 0 && (out_ptr_bits & 3) == 0);
+    WdPath w;
+    SCN_REQUIRE(plan_path(cin, cout, prefix_host, n_off, n_prob, bf16_storage != 0, (unsigned)operand_ptr_bits & 15u,
+                          (unsigned)out_ptr_bits & 15u, w) == SCN_OK);
+    const int64_t units = w.pl.unit_start[n_prob * n_off];
+    const int64_t v[16] = {w.mfma16 ? 1 : 0, w.ta, w.tb, w.quad, w.edge, w.evec, w.hb, w.pl.per, units, w.pl.nbi, w.pl.nbj,
+                           w.V, w.G, w.slab_floats * (int64_t)sizeof(float),
+                           (w.slab_floats + w.db_floats) * (int64_t)sizeof(float), units == 0 ? 1 : 0};
+    memcpy(out, v, sizeof(v));
+    return SCN_OK;
 }
 
 // One k_wgrad_direct launch, as wgrad_impl plans it: what the standalone launch passes, and what a grouped launch needs.
@@ -1004,10 +1070,11 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
     }
     SCN_REQUIRE(!multi || (Xs[0] == (const void*)X && dYs[0] == (const void*)dY));
     const int n_off = n_prob * n_off_real;                                   // (virtual) offsets of the launch
-    const bool mfma16 = hb && tb_usable(cin, cout) && ((all_ptrs & 15) == 0);
-    DPlan pl;
-    if (multi) SCN_REQUIRE(multi_problem_plan(cin, cout, prefix_host, n_off_real, n_prob, pl, mfma16, hb) == SCN_OK);
-    else SCN_REQUIRE(make_dplan(cin, cout, prefix_host, n_off, pl, mfma16, hb) == SCN_OK);
+    WdPath path;                                 // every decision of this call: plan_path
+    SCN_REQUIRE(plan_path(cin, cout, prefix_host, n_off_real, n_prob, hb, (unsigned)(all_ptrs & 15),
+                          (unsigned)(((uintptr_t)dW | (uintptr_t)scratch) & 15), path) == SCN_OK);
+    const DPlan& pl = path.pl;
+    const bool mfma16 = path.mfma16;
     SCN_REQUIRE(prefix_host[n_off_real] == prefix_host[0] || (X && dY));
     SCN_REQUIRE((all_ptrs & (hb ? 1 : 3)) == 0);
     if (pl.unit_start[n_off] == 0) {
@@ -1015,23 +1082,16 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
         if (db) SCN_HIP(hipMemsetAsync(db, 0, sizeof(float) * (size_t)n_prob * cout, S(stream)));
         return SCN_OK;
     }
-    const Shape sh = pick_shape(cin, cout, hb);
-    // vector row pieces need aligned rows and whole blocks; anything else takes the element-wise (EDGE) instantiation
-    const bool edge = (cin % (16 * sh.ta) != 0) || (cout % (16 * sh.tb) != 0) ||
-                      ((all_ptrs & (sh.ta == 3 ? 3 : 15)) != 0);
     const bool ident = in_rows == nullptr;
-    const int cout_pad = pl.nbj * pl.cbj;
-    float* db_slabs = db ? (float*)scratch + (int64_t)pl.unit_start[n_off] * pl.nbi * pl.nbj * pl.cbi * pl.cbj : nullptr;
+    const int cout_pad = path.cout_pad;
+    float* db_slabs = db ? (float*)scratch + path.slab_floats : nullptr;
     dim3 grid((unsigned)pl.unit_start[n_off], 1, (unsigned)(pl.nbi * pl.nbj));
     // bit 1: EDGE blocks whose fragments are whole (vector loads stay possible, see k_wgrad_direct)
-    const bool evec = edge && !hb && cin % sh.ta == 0 && cout % sh.tb == 0 && (all_ptrs & 15) == 0 &&
-                      (cin * 4) % 16 == 0 && (cout * 4) % 16 == 0 && !scn::sw(scn::SW_WD_NO_EVEC).set;
-    const int relu_in = ((flags & SCN_F_RELU_IN) ? 1 : 0) | (evec ? 2 : 0);
-    // sum of the units: V output channels per thread, G threads per element group so that ~>= 128k threads run
-    const int V = (cout % 4 == 0 && (((uintptr_t)dW | (uintptr_t)scratch) & 15) == 0) ? 4 : 1;
+    const int relu_in = ((flags & SCN_F_RELU_IN) ? 1 : 0) | (path.evec ? 2 : 0);
+    const int V = path.V;
     const bool deferred = g_defer.on && V == 4;  // the caller batches the sums of several launches (own scratch per launch)
     if (mfma16) {
-        const int ta = tb_tiles(cin), tb = tb_tiles(cout);
+        const int ta = path.ta, tb = path.tb;
 #define LAUNCH_WT(TA_, TB_, I_)                                                                                  \
     hipLaunchKernelGGL((k_wgrad_tb<TA_, TB_, I_>), grid, dim3(256), 4 * 32 * 256, S(stream), (const unsigned short*)X, cin, \
                        (const unsigned short*)dY, cout, in_rows, out_rows, pl, (float*)scratch, relu_in, db_slabs, db_mask, \
@@ -1053,8 +1113,7 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
     } else {
         WdLaunch r;
         r.pl = pl;
-        r.ta = sh.ta; r.tb = sh.tb; r.quad = sh.quad; r.edge = edge; r.ident = ident; r.hb = hb;
-        if (sh.ta == 3) r.edge = false;          // (48-wide blocks: one instantiation, whole fragments by construction)
+        r.ta = path.ta; r.tb = path.tb; r.quad = path.quad; r.edge = path.edge; r.ident = ident; r.hb = path.hb;
         r.X = X; r.dY = dY; r.cin = cin; r.cout = cout; r.relu_in = relu_in; r.cout_pad = cout_pad; r.n_prob = n_prob;
         r.in_rows = in_rows; r.out_rows = out_rows; r.slabs = (float*)scratch; r.db_slabs = db_slabs; r.db_mask = db_mask;
         r.more = more;
@@ -1065,8 +1124,7 @@ static int wgrad_impl(const float* X, int cin, const float* dY, int cout, const 
         }
     }
     const int64_t groups = (int64_t)n_off * cin * (cout / V);
-    int G = 1;
-    while (G < 16 && groups * G < 128 * 1024) G *= 2;
+    const int G = path.G;
     SumArgs sa;
     sa.slabs = (const float*)scratch; sa.dW = dW; sa.db_slabs = db_slabs; sa.db = db;
     memcpy(sa.unit_start, pl.unit_start, sizeof(sa.unit_start));
@@ -1195,16 +1253,7 @@ extern "C" int scn_wgrad_bias_rules(const float* X, int cin, const float* dY, in
 // for n_prob times the work (tools/wgrad_batch_bound.py: two problems take 0.82-0.85 of two calls).
 extern "C" int64_t scn_wgrad_scratch_bytes_n(int cin, int cout, const int64_t* prefix_host, int n_off, int n_prob) {
     if (!prefix_host || n_off < 1 || n_off > 32 || cin < 1 || cout < 1 || n_prob < 2 || n_prob > WD_MAX_PROB) return -1;
-    int64_t best = -1;
-    for (int v = 0; v < 3; ++v) {                    // fp32 rows; bf16-stored rows on the fp32-MFMA kernel; bf16-MFMA plan
-        if (v == 2 && !tb_usable(cin, cout)) continue;
-        DPlan pl;
-        if (multi_problem_plan(cin, cout, prefix_host, n_off, n_prob, pl, v == 2, v == 1) != SCN_OK) return -1;
-        const int64_t b = (int64_t)pl.unit_start[n_prob * n_off] *
-                              ((int64_t)pl.nbi * pl.nbj * pl.cbi * pl.cbj + (int64_t)pl.nbj * pl.cbj) * (int64_t)sizeof(float) + 512;
-        if (b > best) best = b;
-    }
-    return best;
+    return scratch_bytes_impl(cin, cout, prefix_host, n_off, n_prob);
 }
 
 extern "C" int64_t scn_wgrad_scratch_bytes2(int cin, int cout, const int64_t* prefix_host, int n_off) {

@@ -876,7 +876,8 @@ def test_wgrad_48_wide_blocks_match_the_padded_blocks(gpu, c):
     """k_wgrad_direct<3,3> (round 3): the reference's 48- and 96-channel layers are whole multiples of a 48-wide wave block
     (three-dword row pieces) instead of padded 64- / 128-wide ones (1.78x the MFMAs).  Same rules, same per-rule products;
     the unit plan differs, so the fp32 unit sums associate differently: <= 2e-6 of the scale against the padded blocks
-    (SCN_WD_NO_T3=1), single and paired problems, weight and bias gradients, the identity list (NetworkInNetwork)."""
+    (SCN_WD_NO_T3=1), single and paired problems, weight and bias gradients, the identity list (NetworkInNetwork).
+    Absolute anchor of both block shapes (exact and against float64): tests/test_gpu_wgrad_paths.py."""
     import os
     import sparse_rcnn_amd as scn
     from sparse_rcnn_amd import functional as F, _lib as L

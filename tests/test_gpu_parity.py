@@ -2146,7 +2146,8 @@ def test_tile_major_weight_gradient_agrees_with_the_rule_major_kernel(gpu):
     """scn_wgrad_tiles32 (round 6, experiment (c): one row gather per rule, dY tiles through LDS, offsets dealt to waves;
     profiles/r6_wgrad_one_gather.txt) computes the weight gradient of a 32 -> 32 SubM 3^3 layer (module_factory.py:396-414) from
     the forward kernel's tile tables: equal to an fp64 evaluation of the rules within 2e-6 of the scale, as the product kernel
-    (scn_wgrad_rules) is; deterministic; with and without the fused input ReLU; a level whose last tile is ragged."""
+    (scn_wgrad_rules) is; deterministic; with and without the fused input ReLU; a level whose last tile is ragged.
+    Absolute anchor of both kernels (exact and against float64): tests/test_gpu_wgrad_paths.py."""
     from sparse_rcnn_amd import _lib as L
     lib = L.lib()
     scn, coords, feats, fg, x, scene, size = _input(gpu, seed=31, cin=4, grid=(40, 36, 20), n=9003, batch=2, dup=200)
