@@ -78,7 +78,8 @@ extern "C" {
  *      points);
  *      additive within 5: + scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16 (166 entry points);
  *      additive within 5: + scn_relu_fwd_bf16 / _bwd_bf16 (168 entry points);
- *      additive within 5: + scn_wgrad_plan_describe (169 entry points) */
+ *      additive within 5: + scn_wgrad_plan_describe (169 entry points);
+ *      additive within 5: + scn_roialign_pool_fwd / _bwd, their _bf16 forms, scn_box_flatten_fwd / _bwd (175 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -1156,6 +1157,42 @@ int scn_dense_maxpool_fwd_bf16(const uint16_t* X, int64_t n_boxes, const int64_t
                                uint8_t* argmax, scn_stream_t stream);
 int scn_dense_maxpool_bwd_bf16(const uint16_t* dY, const uint8_t* argmax, int64_t n_boxes, const int64_t* extent_host, int c,
                                uint16_t* dX, scn_stream_t stream);
+
+/* ---- RoiAlign and the 2^3 max pool in ONE pass (the reference's class head without an input convolution cuts 8^3 boxes out of
+ * the RPN stack's volume at its full width: the un-pooled samples are never written) -- csrc/scn_roialign.hip ----
+ * Arguments, layouts, range checks and `table` (the same buffer, filled by the same two kernels) are those of scn_roialign_fwd /
+ * _bwd, except: Y [n_boxes ex/2 ey/2 ez/2][c] takes the place of Out, dY that of dOut, and argmax uint8, one byte per element of
+ * Y, is written by the forward and read by the backward.  Every extent must be even (and >= 2): else SCN_EINVAL before any
+ * launch.  The _bf16 forms take bf16 bit patterns and refuse c % 8 != 0 as the calls above do.
+ * scn_roialign_pool_fwd (3 launches, none for n_boxes == 0) = scn_roialign_fwd then scn_dense_maxpool_fwd, BIT FOR BIT, Y and
+ * argmax: each of the 8 children is the RoiAlign sample (the same corner order, (wx * wy) * wz weights; one device function
+ * serves both kernels), in the bf16 form rounded to bf16 once before the comparison; the first child wins a tie, a NaN child
+ * wins.
+ * scn_roialign_pool_bwd (1 launch; n_boxes == 0: one memset) = scn_dense_maxpool_bwd then scn_roialign_bwd, equal as numbers
+ * (a -0 of the pair may be a +0 here): scn_roialign_bwd's ordered gather with dOut[r, i, j, k] = dY[r, i/2, j/2, k/2] where
+ * argmax names child (i & 1, j & 1, k & 1) and 0 elsewhere; terms that are zero by that rule are skipped.  No atomics, reruns
+ * give identical bits, every cell of dF is written.  No call waits for the host. */
+int scn_roialign_pool_fwd(const float* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                          const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host, void* table, float* Y,
+                          uint8_t* argmax, scn_stream_t stream);
+int scn_roialign_pool_bwd(const float* dY, const uint8_t* argmax, const void* table, const int32_t* sample_of_box,
+                          int64_t n_boxes, int batch, const int64_t* size_host, int c, const int64_t* extract_host, float* dF,
+                          scn_stream_t stream);
+int scn_roialign_pool_fwd_bf16(const uint16_t* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                               const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host, void* table,
+                               uint16_t* Y, uint8_t* argmax, scn_stream_t stream);
+int scn_roialign_pool_bwd_bf16(const uint16_t* dY, const uint8_t* argmax, const void* table, const int32_t* sample_of_box,
+                               int64_t n_boxes, int batch, const int64_t* size_host, int c, const int64_t* extract_host,
+                               uint16_t* dF, scn_stream_t stream);
+
+/* ---- the reference's Reshaper (`x.view(R, -1)` of [R, C, x, y, z]) on box grids, with the ReLU behind it -- fp32 ----
+ * X fp32 [n_boxes v][c] (v sites per box, row r v + s) <-> Y fp32 [n_boxes][c v], channel-major: Y[r][ch v + s] =
+ * relu ? max(X[r v + s][ch], 0) : X[r v + s][ch]; a NaN stays a NaN.  scn_box_flatten_bwd writes EVERY element of dX:
+ * dY[r][ch v + s] where !relu or X > 0, else 0 (X may be NULL when !relu).  1 launch each, none for n_boxes == 0; v c < 2^31.
+ * Neither call waits for the host. */
+int scn_box_flatten_fwd(const float* X, int64_t n_boxes, int64_t v, int c, int relu, float* Y, scn_stream_t stream);
+int scn_box_flatten_bwd(const float* X, const float* dY, int64_t n_boxes, int64_t v, int c, int relu, float* dX,
+                        scn_stream_t stream);
 
 /* ---- the permutation half of the reference's up-sampling RPN heads (ndsis/modules/anchor_network.py:127-219
  * AnchorNetworkUpsample; anchor.py:167-192 rpn_permuter + rpn_bbox_score_splitter) -- csrc/scn_anchor_up.hip, fp32 ----

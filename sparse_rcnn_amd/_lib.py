@@ -185,6 +185,12 @@ _SIGS = {
     "scn_roialign_bwd_bf16": (C.c_int, [p, p, p, i64, i32, C.POINTER(i64), i32, C.POINTER(i64), p, p]),
     "scn_dense_maxpool_fwd_bf16": (C.c_int, [p, i64, C.POINTER(i64), i32, p, p, p]),
     "scn_dense_maxpool_bwd_bf16": (C.c_int, [p, p, i64, C.POINTER(i64), i32, p, p]),
+    "scn_roialign_pool_fwd": (C.c_int, [p, i32, C.POINTER(i64), i32, p, p, i64, C.POINTER(i64), p, p, p, p]),
+    "scn_roialign_pool_bwd": (C.c_int, [p, p, p, p, i64, i32, C.POINTER(i64), i32, C.POINTER(i64), p, p]),
+    "scn_roialign_pool_fwd_bf16": (C.c_int, [p, i32, C.POINTER(i64), i32, p, p, i64, C.POINTER(i64), p, p, p, p]),
+    "scn_roialign_pool_bwd_bf16": (C.c_int, [p, p, p, p, i64, i32, C.POINTER(i64), i32, C.POINTER(i64), p, p]),
+    "scn_box_flatten_fwd": (C.c_int, [p, i64, i64, i32, i32, p, p]),
+    "scn_box_flatten_bwd": (C.c_int, [p, p, i64, i64, i32, i32, p, p]),
     "scn_anchor_up_fwd": (C.c_int, [p, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, p, i64, i64, p, p, p]),
     "scn_anchor_up_bwd": (C.c_int, [p, p, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, p, i64, i64, p, p]),
     "scn_philox_words_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),

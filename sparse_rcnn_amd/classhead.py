@@ -226,11 +226,15 @@ class DenseClassBranch(nn.Module):
     rounded up to a multiple of BOX_BUCKET and ONE Metadata is kept per bucket: the padding boxes' rows enter the first strided
     convolution as zeros (functional.DenseMaxPoolFunction writes them), their pooled rows are dropped before the linear
     layers, so their output gradient is zero and they add nothing to any weight gradient; boxes never share a site, so
-    they change no real box's result."""
+    they change no real box's result.
+
+    fused_pool=True (opt-in; the default path is unchanged): RoiAlign and the max pool run as ONE pass
+    (functional.RoiAlignPoolFunction, in either storage) -- the same scores bit for bit, the [R 16^3, C] samples never written."""
 
     def __init__(self, feature_channels, stride, input_channels=32, output_channels=(64, 128), linear_channels=(64,),
-                 num_classes=18, num_units=1, cut_shape=(16, 16, 16), storage=torch.float32):
+                 num_classes=18, num_units=1, cut_shape=(16, 16, 16), storage=torch.float32, fused_pool=False):
         super().__init__()
+        self.fused_pool = bool(fused_pool)
         if storage not in (torch.float32, torch.bfloat16):
             raise ValueError("DenseClassBranch: storage is torch.float32 or torch.bfloat16")
         widths = (feature_channels, input_channels) + tuple(output_channels)
@@ -289,13 +293,22 @@ class DenseClassBranch(nn.Module):
                 volume_slab = volume_slab.to(self.storage)
             md = metadata if metadata is not None else self._metadata(size, batch, volume_slab.device)
             augmented = self.input_conv_layer(SparseConvNetTensor(volume_slab, md, torch.as_tensor(size, dtype=torch.long)))
-            box_slab, selection = self.roi_getter.forward_slab(augmented.features, size, batch, boxes)
+            if self.fused_pool:
+                bbox_tensor, counts, assoc = roi.transform_boxes_interpolation(boxes, size, True, self.stride)
+                selection = (bbox_tensor, counts, size)
+            else:
+                box_slab, selection = self.roi_getter.forward_slab(augmented.features, size, batch, boxes)
             r = selection[0].shape[0]
             if r == 0:
                 return volume_slab.new_zeros((0, self.num_classes), dtype=torch.float32), selection
             rb = self.bucket(r)
             half = tuple(c // 2 for c in self.cut_shape)
-            pooled = F.DenseMaxPoolFunction.apply(box_slab, r, self.cut_shape, rb)
+            if self.fused_pool:
+                sample = assoc.to(device=volume_slab.device, dtype=torch.int32)
+                pooled = F.RoiAlignPoolFunction.apply(augmented.features, selection[0], sample, int(batch), size,
+                                                      self.cut_shape, rb)
+            else:
+                pooled = F.DenseMaxPoolFunction.apply(box_slab, r, self.cut_shape, rb)
             box_md = self._metadata(half, rb, volume_slab.device)
             x = SparseConvNetTensor(pooled, box_md, torch.as_tensor(half, dtype=torch.long))
             vectors = self.vectorice_layer(self.output_conv_layer(x))[:r]
@@ -317,6 +330,135 @@ class DenseClassBranch(nn.Module):
         if prefix is None:
             tail = "input_conv_layer.0.0.0.weight"
             cands = [k[:-len(tail)] for k in state_dict if k.endswith(tail)]
+            prefix = next((c for c in cands if c + "linear_layer.1.weight" in state_dict), cands[0] if cands else "")
+        converted = {k: (conv3d_to_slab_weight(v) if k.startswith(prefix) and v.dim() == 5 else v) for k, v in state_dict.items()}
+        return _load_mapped(self.named_oracle_params(), self.reference_key_map(), converted, prefix,
+                            ("input_conv_layer.", "output_conv_layer.", "linear_layer."), strict)
+
+
+def reshape_reference_key_map(n_same=1, n_linear=2, relu_after_pooling=True):
+    """state_dict key of the reference's RESHAPING ClassNetwork -> this package's parameter name
+    (`ReshapeClassBranch.named_oracle_params`).  Index 0 of `output_conv_layer` is the parameterless max pool, so the bare
+    nn.Conv3d of same-level l sits at l + 1; the input network is an Identity; linear_layer starts with a ReLU only when
+    relu_after_pooling (Linear i at 2 i + 1, else at 2 i).  Checked against the key lists of reference
+    networks built on the CPU (tests/golden/reshape_class_keys.json)."""
+    out = {}
+    for t in ("weight", "bias"):
+        for l in range(n_same):
+            out[f"output_conv_layer.{l + 1}.{t}"] = f"same{l}.{t}"
+        for i in range(n_linear):
+            out[f"linear_layer.{2 * i + int(bool(relu_after_pooling))}.{t}"] = f"lin{i}.{t}"
+    return out
+
+
+class ReshapeClassBranch(nn.Module):
+    """The reference's class network WITHOUT pooling (`simple_class`, scannet_config/run.py:706-710; `cs8_dense8max4_reshape`):
+    identity input network, RoiAlign to `cut_shape` (8^3) straight out of the RPN stack's volume at its full width, max pool 2,
+    one 3^3 same-convolution per entry of `same_channels` (None keeps the width; a bare nn.Conv3d in the reference: no ReLU before
+    or between them), `Reshaper` (channel-major `x.view(R, -1)`, so `linear_layer.1.weight` loads as it is), ReLU Linear ReLU Linear.
+
+    forward(volume_slab [B X Y Z, feature_channels], size, batch, boxes, metadata=None) -> (class_scores [R, num_classes] fp32,
+    (bbox_tensor, boxes per sample, size)): DenseClassBranch.forward's contract (`metadata` is accepted for it; the volume
+    itself needs no index structure here).  The head computes in fp32: a bf16 volume is widened on entry.  With zero boxes the
+    reference raises (`view(0, -1)`); this returns [0, num_classes], as DenseClassBranch does.
+
+    fused=True: RoiAlign and the max pool are ONE pass (functional.RoiAlignPoolFunction: the [R 512, C] samples and their
+    gradient are never written -- 126 MB each way at C = 128, R = 480); False: roi.RoiAlign.forward_slab +
+    functional.DenseMaxPoolFunction, the same scores bit for bit.  The same-convolutions are SubmanifoldConvolution(3, ., ., 3)
+    on the fully active half-size box grids, with DenseClassBranch's BOX_BUCKET bucketing and per-bucket Metadata."""
+
+    def __init__(self, feature_channels, stride, same_channels=(8,), linear_channels=(64,), num_classes=18,
+                 cut_shape=(8, 8, 8), relu_after_pooling=True, fused=True):
+        super().__init__()
+        self.stride = stride
+        self.cut_shape = tuple(int(c) for c in cut_shape)
+        if len(self.cut_shape) != 3 or any(c % 2 or c < 2 for c in self.cut_shape):
+            raise ValueError(f"ReshapeClassBranch: cut_shape {self.cut_shape} must be even per axis (max pool 2)")
+        if not len(same_channels):
+            raise ValueError("ReshapeClassBranch: at least one same-convolution (same_channels)")
+        self.fused, self.relu_after_pooling = bool(fused), bool(relu_after_pooling)
+        self.roi_getter = roi.RoiAlign(self.cut_shape, clip_boxes=True, resize_boxes=stride)
+        levels, c = [], int(feature_channels)
+        for co in same_channels:
+            co = c if co is None else int(co)
+            levels.append(M.SubmanifoldConvolution(3, c, co, 3, True))
+            c = co
+        self.output_conv_layer = nn.ModuleList(levels)
+        self.half = tuple(v // 2 for v in self.cut_shape)
+        c *= self.half[0] * self.half[1] * self.half[2]
+        layers = []
+        for co in tuple(linear_channels) + (num_classes,):                # (module_factory.py:700-716, start_relu=relu_after_pooling)
+            layers += ([nn.ReLU(inplace=bool(layers))] if layers or self.relu_after_pooling else []) + [nn.Linear(c, co)]
+            c = co
+        self.linear_layer = nn.Sequential(*layers)
+        self.num_classes = int(num_classes)
+        self._md = {}                         # (size, batch, device) -> fully active Metadata
+
+    __getstate__ = DenseClassBranch.__getstate__
+    _metadata = DenseClassBranch._metadata
+    bucket = staticmethod(DenseClassBranch.bucket)
+
+    def forward(self, volume_slab, size, batch, boxes, metadata=None):
+        from . import functional as F
+        from .tensor import SparseConvNetTensor
+        size = tuple(int(v) for v in size)
+        prev = M.set_feature_storage(torch.float32)
+        try:
+            if volume_slab.dtype != torch.float32:
+                volume_slab = volume_slab.to(torch.float32)
+            bbox_tensor, counts, assoc = roi.transform_boxes_interpolation(boxes, size, True, self.stride)
+            selection = (bbox_tensor, counts, size)
+            r = bbox_tensor.shape[0]
+            if r == 0:
+                return volume_slab.new_zeros((0, self.num_classes)), selection
+            rb = self.bucket(r)
+            if self.fused:
+                sample = assoc.to(device=volume_slab.device, dtype=torch.int32)
+                pooled = F.RoiAlignPoolFunction.apply(volume_slab, bbox_tensor, sample, int(batch), size, self.cut_shape, rb)
+            else:
+                box_slab, _ = self.roi_getter.forward_slab(volume_slab, size, batch, boxes)
+                pooled = F.DenseMaxPoolFunction.apply(box_slab, r, self.cut_shape, rb)
+            box_md = self._metadata(self.half, rb, volume_slab.device)
+            x = SparseConvNetTensor(pooled, box_md, torch.as_tensor(self.half, dtype=torch.long))
+            for conv in self.output_conv_layer:                  # bare convolutions, one after the other
+                x = conv(x)
+            per = self.half[0] * self.half[1] * self.half[2]
+            vectors = F.BoxFlattenFunction.apply(x.features[:r * per], r, self.relu_after_pooling)
+        finally:
+            M.set_feature_storage(prev)
+        return self._linear(vectors), selection
+
+    def _linear(self, x):
+        """linear_layer behind the flatten, which has applied its first ReLU already (relu_after_pooling)."""
+        from . import functional as F
+        for i, m in enumerate(self.linear_layer):
+            if isinstance(m, nn.Linear):
+                x = F.NetworkInNetworkFunction.apply(x, m.weight.t(), m.bias)
+            elif i:                                              # (a ReLU at index 0 ran inside the flatten)
+                x = F.ReLUFunction.apply(x)
+        return x
+
+    def named_oracle_params(self):
+        out = {}
+        for l, cv in enumerate(self.output_conv_layer):
+            out[f"same{l}.weight"], out[f"same{l}.bias"] = cv.weight, cv.bias
+        for i, m in enumerate(m for m in self.linear_layer if isinstance(m, nn.Linear)):
+            out[f"lin{i}.weight"], out[f"lin{i}.bias"] = m.weight, m.bias
+        return out
+
+    def reference_key_map(self):
+        n_lin = len([m for m in self.linear_layer if isinstance(m, nn.Linear)])
+        return reshape_reference_key_map(len(self.output_conv_layer), n_lin, self.relu_after_pooling)
+
+    def load_reference_state_dict(self, state_dict, prefix=None, strict=True):
+        """Load the class-network part of a checkpoint written by the REFERENCE with its reshaping class network
+        (`class_network.` in InstanceSegmentationNetwork).  nn.Conv3d weights [co, ci, a, b, c] become W[(a 3 + b) 3 + c, ci, co];
+        the linear weights load as they are (both sides flatten channel-major).  prefix=None: the first key ending in
+        'output_conv_layer.1.weight' (a 5-d tensor) with a 'linear_layer.1.weight' sibling.
+        -> (missing reference keys, unused checkpoint keys under the prefix)."""
+        if prefix is None:
+            tail = "output_conv_layer.1.weight"
+            cands = [k[:-len(tail)] for k, v in state_dict.items() if k.endswith(tail) and v.dim() == 5]
             prefix = next((c for c in cands if c + "linear_layer.1.weight" in state_dict), cands[0] if cands else "")
         converted = {k: (conv3d_to_slab_weight(v) if k.startswith(prefix) and v.dim() == 5 else v) for k, v in state_dict.items()}
         return _load_mapped(self.named_oracle_params(), self.reference_key_map(), converted, prefix,

@@ -37,6 +37,13 @@
 // children scanned in (x, y, z) order, z fastest, a later child replaces the maximum only when it is greater or NaN, so on a
 // tie the first child wins -- nn.MaxPool3d's rule.  The forward stores that child's index 0..7 as a byte; the backward
 // sends dY to that child alone and writes 0 to the other seven.
+//
+// RoiAlign + max pool in one pass (scn_roialign_pool_fwd / _bwd; the class head without an input convolution cuts 8^3 boxes at
+// the RPN stack's full width): the un-pooled samples and their gradient are never written.  The forward evaluates a
+// pooled cell's 8 children with the forward's own sample function and keeps the maximum by the rule above -- Y and argmax are the
+// pair's, bit for bit; the backward is the gather above with dOut[r, i, j, k] read as dY[r, i/2, j/2, k/2] where argmax names
+// child (i & 1, j & 1, k & 1) and as 0 elsewhere -- the pair's dF as numbers.  Behind them scn_box_flatten_fwd / _bwd: the
+// reference's channel-major Reshaper of the box grids with the ReLU that follows it.
 #include "scn_common.h"
 
 namespace {
@@ -109,6 +116,14 @@ template <> struct Vec<float, 1> {
     __device__ void store(float* p) const { *p = v; }
     __device__ static Vec zero() { return {0.f}; }
     __device__ void fma(float a, const Vec& x) { v += a * x.v; }
+    __device__ Vec stored() const { return *this; }          // (what a store followed by a load gives: fp32 rows keep every bit)
+    // one corner of a forward sample.  Spelled out, not left to -ffp-contract: the scalar form has always rounded the product
+    // (the compiler packs this multiply with the weight's), the 16-byte forms have always fused it; pinned so that every
+    // kernel that evaluates a sample -- whatever is inlined around it -- gives the same bits
+    __device__ void corner(float a, const Vec& x) {
+#pragma clang fp contract(off)
+        v = v + a * x.v;
+    }
 };
 template <> struct Vec<float, 4> {
     float4 v;
@@ -116,6 +131,11 @@ template <> struct Vec<float, 4> {
     __device__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
     __device__ static Vec zero() { return {make_float4(0.f, 0.f, 0.f, 0.f)}; }
     __device__ void fma(float a, const Vec& x) { v.x += a * x.v.x; v.y += a * x.v.y; v.z += a * x.v.z; v.w += a * x.v.w; }
+    __device__ Vec stored() const { return *this; }
+    __device__ void corner(float a, const Vec& x) {
+        v.x = __builtin_fmaf(a, x.v.x, v.x); v.y = __builtin_fmaf(a, x.v.y, v.y);
+        v.z = __builtin_fmaf(a, x.v.z, v.z); v.w = __builtin_fmaf(a, x.v.w, v.w);
+    }
 };
 // 8 bf16 bit patterns in one 16-byte lane: widened exactly by load, rounded to nearest even by store (the only rounding)
 __device__ __forceinline__ unsigned f32_to_bf16(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
@@ -148,7 +168,55 @@ template <> struct Vec<uint16_t, 8> {
 #pragma unroll
         for (int l = 0; l < 8; ++l) v[l] += a * x.v[l];
     }
+    __device__ void corner(float a, const Vec& x) {
+#pragma unroll
+        for (int l = 0; l < 8; ++l) v[l] = __builtin_fmaf(a, x.v[l], v[l]);
+    }
+    __device__ Vec stored() const {                           // rounded to bf16 once, widened again
+        Vec r;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) r.v[l] = __uint_as_float(f32_to_bf16(v[l]) << 16);
+        return r;
+    }
 };
+
+// The RoiAlign sample of one lane: the 8 corners in (x, y, z) order, z fastest, each weighted (wx * wy) * wz -- the ONE
+// evaluation behind k_roialign_fwd and k_roialign_pool_fwd, so the two cannot drift.  `base` = the box's first table entry.
+template <typename T, int V>
+__device__ __forceinline__ Vec<T, V> roialign_sample(const T* __restrict__ F, const Tables& tb, int64_t base, const Geo& g,
+                                                      int b, const int xs[2], const float wxs[2], int j, int k, int c, int q) {
+    const int64_t ty = base + g.ex + j, tz = base + g.ex + g.ey + k;
+    const int ys[2] = {tb.lo[ty], tb.hi[ty]}, zs[2] = {tb.lo[tz], tb.hi[tz]};
+    float wys[2], wzs[2];
+    {
+#pragma clang fp contract(off)
+        wys[1] = tb.w[ty]; wys[0] = 1.f - wys[1];
+        wzs[1] = tb.w[tz]; wzs[0] = 1.f - wzs[1];
+    }
+    Vec<T, V> acc = Vec<T, V>::zero();
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+                float wt;
+                {
+#pragma clang fp contract(off)
+                    wt = (wxs[a] * wys[bb]) * wzs[cc];
+                }
+                const int64_t cell = (((int64_t)b * g.X + xs[a]) * g.Y + ys[bb]) * g.Z + zs[cc];
+                acc.corner(wt, Vec<T, V>::load(F + cell * c + q * V));
+            }
+    return acc;
+}
+
+// the x cells and weights of sample i of the box whose table starts at `base`: uniform over a workgroup
+__device__ __forceinline__ void x_sample(const Tables& tb, int64_t base, int i, int xs[2], float wxs[2]) {
+#pragma clang fp contract(off)
+    xs[0] = tb.lo[base + i]; xs[1] = tb.hi[base + i];
+    wxs[1] = tb.w[base + i]; wxs[0] = 1.f - wxs[1];
+}
 
 // one workgroup per (box, x sample): the x cells and weights are uniform; its ey * ez rows x C / V lanes in 32-bit arithmetic
 template <typename T, int V>
@@ -161,41 +229,58 @@ k_roialign_fwd(const T* __restrict__ F, Tables tb, const int32_t* __restrict__ s
     const int64_t base = r * g.E;
     int b = sample_of_box[r];
     b = b < 0 ? 0 : (b >= g.batch ? g.batch - 1 : b);
-    const int xs[2] = {tb.lo[base + i], tb.hi[base + i]};
+    int xs[2];
     float wxs[2];
-    {
-#pragma clang fp contract(off)
-        wxs[1] = tb.w[base + i]; wxs[0] = 1.f - wxs[1];
-    }
+    x_sample(tb, base, i, xs, wxs);
     const unsigned items = (unsigned)g.ey * g.ez * cv;
     T* out_plane = Out + (r * g.ex + i) * (int64_t)g.ey * g.ez * c;
     for (unsigned t = threadIdx.x; t < items; t += blockDim.x) {
         const unsigned row = t / (unsigned)cv, q = t - row * cv;
         const unsigned j = row / (unsigned)g.ez, k = row - j * g.ez;
-        const int64_t ty = base + g.ex + j, tz = base + g.ex + g.ey + k;
-        const int ys[2] = {tb.lo[ty], tb.hi[ty]}, zs[2] = {tb.lo[tz], tb.hi[tz]};
-        float wys[2], wzs[2];
-        {
-#pragma clang fp contract(off)
-            wys[1] = tb.w[ty]; wys[0] = 1.f - wys[1];
-            wzs[1] = tb.w[tz]; wzs[0] = 1.f - wzs[1];
+        roialign_sample<T, V>(F, tb, base, g, b, xs, wxs, (int)j, (int)k, c, (int)q).store(out_plane + (int64_t)row * c + q * V);
+    }
+}
+
+// RoiAlign and the 2^3 max pool in one pass: one workgroup per (box, pooled x), its ey/2 * ez/2 pooled rows x C / V lanes.  A
+// thread evaluates its 8 children (x, y, z order, z fastest: the max pool's scan) with roialign_sample, rounds each to the
+// storage type once (`stored`: what the un-fused pair writes and reads back between its two kernels), keeps the maximum by the
+// max pool's rule (a later child replaces it only when greater or NaN) and writes the value and the child's index.
+template <typename T, int V>
+__global__ void __launch_bounds__(256)
+k_roialign_pool_fwd(const T* __restrict__ F, Tables tb, const int32_t* __restrict__ sample_of_box, int cv, Geo g,
+                    T* __restrict__ Y, uint8_t* __restrict__ arg) {
+    const int c = cv * V;
+    const int ox = g.ex / 2, oy = g.ey / 2, oz = g.ez / 2;
+    const int io = (int)(blockIdx.x % (unsigned)ox);
+    const int64_t r = blockIdx.x / (unsigned)ox;
+    const int64_t base = r * g.E;
+    int b = sample_of_box[r];
+    b = b < 0 ? 0 : (b >= g.batch ? g.batch - 1 : b);
+    int xs[2][2];
+    float wxs[2][2];
+    x_sample(tb, base, 2 * io, xs[0], wxs[0]);
+    x_sample(tb, base, 2 * io + 1, xs[1], wxs[1]);
+    const unsigned items = (unsigned)oy * oz * cv;
+    for (unsigned t = threadIdx.x; t < items; t += blockDim.x) {
+        const unsigned row = t / (unsigned)cv, q = t - row * cv;
+        const unsigned jo = row / (unsigned)oz, ko = row - jo * oz;
+        Vec<T, V> best;
+        float* m = reinterpret_cast<float*>(&best);
+        uint8_t am[V];
+#pragma unroll
+        for (int ch = 0; ch < 8; ++ch) {
+            const int dx = ch >> 2, dy = (ch >> 1) & 1, dz = ch & 1;
+            const Vec<T, V> v = roialign_sample<T, V>(F, tb, base, g, b, xs[dx], wxs[dx], (int)(2 * jo) + dy, (int)(2 * ko) + dz,
+                                                      c, (int)q).stored();
+            const float* vf = reinterpret_cast<const float*>(&v);
+#pragma unroll
+            for (int l = 0; l < V; ++l)
+                if (ch == 0 || vf[l] > m[l] || vf[l] != vf[l]) { m[l] = vf[l]; am[l] = (uint8_t)ch; }
         }
-        Vec<T, V> acc = Vec<T, V>::zero();
+        const int64_t o = (((r * ox + io) * oy + jo) * oz + ko) * c + q * V;
+        best.store(Y + o);
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc) {
-                    float wt;
-                    {
-#pragma clang fp contract(off)
-                        wt = (wxs[a] * wys[bb]) * wzs[cc];
-                    }
-                    const int64_t cell = (((int64_t)b * g.X + xs[a]) * g.Y + ys[bb]) * g.Z + zs[cc];
-                    acc.fma(wt, Vec<T, V>::load(F + cell * c + q * V));
-                }
-        acc.store(out_plane + (int64_t)row * c + q * V);
+        for (int l = 0; l < V; ++l) arg[o + l] = am[l];
     }
 }
 
@@ -215,11 +300,14 @@ __device__ __forceinline__ float axis_weight(int l, int h, float wv, int cell) {
 
 constexpr int BWD_THREADS = 128;      // = the boxes whose x / y ranges one pass holds in LDS
 
-// grid (batch * X * Y, ceil(Z * cv / 128)): workgroup = one (sample, x, y) column, thread = one (z, channel group) of it
-template <typename T, int V>
+// grid (batch * X * Y, ceil(Z * cv / 128)): workgroup = one (sample, x, y) column, thread = one (z, channel group) of it.
+// POOL (the backward of k_roialign_pool_fwd): dOut is dY [R ex/2 ey/2 ez/2, C] and `arg` the forward's child bytes; the term of
+// sample (i, j, k) is dY[r, i/2, j/2, k/2] where arg names child (i & 1, j & 1, k & 1) and 0 elsewhere -- the same ordered sums
+// with the un-pooled gradient never written.  A lane none of whose channels chose the child adds only zeros: it skips the read.
+template <typename T, int V, bool POOL>
 __global__ void __launch_bounds__(BWD_THREADS)
-k_roialign_bwd(const T* __restrict__ dOut, Tables tb, const int32_t* __restrict__ sample_of_box, int64_t n_boxes, int cv, Geo g,
-               T* __restrict__ dF) {
+k_roialign_bwd(const T* __restrict__ dOut, const uint8_t* __restrict__ arg, Tables tb, const int32_t* __restrict__ sample_of_box,
+               int64_t n_boxes, int cv, Geo g, T* __restrict__ dF) {
     __shared__ int s_x0[BWD_THREADS], s_nx[BWD_THREADS], s_y0[BWD_THREADS], s_ny[BWD_THREADS];
     __shared__ int64_t s_range[2];
     const int c = cv * V;
@@ -262,9 +350,29 @@ k_roialign_bwd(const T* __restrict__ dOut, Tables tb, const int32_t* __restrict_
                 for (int j = y0; j < y0 + ny; ++j) {
                     const float ay = axis_weight(ly[j], hy[j], wy[j], y);
                     Vec<T, V> sk = Vec<T, V>::zero();
-                    const T* row = dOut + ((((int64_t)r * g.ex + i) * g.ey + j) * g.ez) * c + q * V;
-                    for (int k = k0; k < k0 + nk; ++k)
-                        sk.fma(axis_weight(lz[k], hz[k], wz[k], z), Vec<T, V>::load(row + (int64_t)k * c));
+                    if constexpr (POOL) {
+                        const int64_t prow = (((int64_t)r * (g.ex / 2) + (i >> 1)) * (g.ey / 2) + (j >> 1)) * (g.ez / 2);
+                        const int cij = ((i & 1) << 2) | ((j & 1) << 1);
+                        for (int k = k0; k < k0 + nk; ++k) {
+                            const int64_t o = (prow + (k >> 1)) * c + q * V;
+                            const int mine = cij | (k & 1);
+                            uint8_t am[V];
+                            __builtin_memcpy(am, arg + o, V);
+                            bool any = false;
+#pragma unroll
+                            for (int l = 0; l < V; ++l) any |= am[l] == mine;
+                            if (!any) continue;
+                            Vec<T, V> gv = Vec<T, V>::load(dOut + o);
+                            float* gf = reinterpret_cast<float*>(&gv);
+#pragma unroll
+                            for (int l = 0; l < V; ++l) gf[l] = am[l] == mine ? gf[l] : 0.f;
+                            sk.fma(axis_weight(lz[k], hz[k], wz[k], z), gv);
+                        }
+                    } else {
+                        const T* row = dOut + ((((int64_t)r * g.ex + i) * g.ey + j) * g.ez) * c + q * V;
+                        for (int k = k0; k < k0 + nk; ++k)
+                            sk.fma(axis_weight(lz[k], hz[k], wz[k], z), Vec<T, V>::load(row + (int64_t)k * c));
+                    }
                     sj.fma(ay, sk);
                 }
                 si.fma(ax, sj);
@@ -375,14 +483,24 @@ int pool_geo(const int64_t* extent_host, int64_t n_boxes, int c, int* o) {
 
 // The launches behind the entry points: rows of T in lanes of W elements when `wd` (16 bytes), else of N (fp32: 4 and 1, the
 // scalar form; bf16: 8 and 8 -- the entry point has refused every other row)
+// (argmax == nullptr: the plain forward into Out [R ex ey ez, C]; else the fused one: Out is Y [R ex/2 ey/2 ez/2, C])
 template <typename T, int W, int N>
 int roialign_fwd(const T* F, const Geo& g, int c, bool wd, const float* boxes, const int32_t* sample_of_box, int64_t n_boxes,
-                 void* table, T* Out, scn_stream_t stream) {
+                 void* table, T* Out, uint8_t* argmax, scn_stream_t stream) {
     const Tables tb = tables(table, n_boxes, g);
     hipLaunchKernelGGL(k_roialign_table, dim3(scn::ew_grid(n_boxes * g.E, 256)), dim3(256), 0, scn::S(stream), boxes, n_boxes, g, tb);
     SCN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_roialign_cells, dim3(scn::ew_grid(n_boxes * g.S, 256)), dim3(256), 0, scn::S(stream), n_boxes, g, tb);
     SCN_LAUNCH_CHECK();
+    if (argmax) {
+        const dim3 grid((unsigned)(n_boxes * (g.ex / 2)));
+        if (wd)
+            hipLaunchKernelGGL((k_roialign_pool_fwd<T, W>), grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c / W, g, Out, argmax);
+        else
+            hipLaunchKernelGGL((k_roialign_pool_fwd<T, N>), grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c / N, g, Out, argmax);
+        SCN_LAUNCH_CHECK();
+        return SCN_OK;
+    }
     const dim3 grid((unsigned)(n_boxes * g.ex));
     if (wd)
         hipLaunchKernelGGL((k_roialign_fwd<T, W>), grid, dim3(256), 0, scn::S(stream), F, tb, sample_of_box, c / W, g, Out);
@@ -392,17 +510,23 @@ int roialign_fwd(const T* F, const Geo& g, int c, bool wd, const float* boxes, c
     return SCN_OK;
 }
 
+// (argmax == nullptr: dOut is the un-pooled gradient; else dOut is dY and the kernel masks it by argmax)
 template <typename T, int W, int N>
-int roialign_bwd(const T* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch, const Geo& g, int c,
-                 bool wd, T* dF, scn_stream_t stream) {
+int roialign_bwd(const T* dOut, const uint8_t* argmax, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch,
+                 const Geo& g, int c, bool wd, T* dF, scn_stream_t stream) {
     const Tables tb = tables(const_cast<void*>(table), n_boxes, g);
     const int cv = wd ? c / W : c / N;
     SCN_REQUIRE(scn::cdiv((int64_t)g.Z * cv, BWD_THREADS) <= 65535);
     const dim3 grid((unsigned)(batch * g.X * g.Y), (unsigned)scn::cdiv((int64_t)g.Z * cv, BWD_THREADS));
-    if (wd)
-        hipLaunchKernelGGL((k_roialign_bwd<T, W>), grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, tb, sample_of_box, n_boxes, cv, g, dF);
-    else
-        hipLaunchKernelGGL((k_roialign_bwd<T, N>), grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, tb, sample_of_box, n_boxes, cv, g, dF);
+#define SCN_ROIALIGN_BWD(V, POOL)                                                                                           \
+    hipLaunchKernelGGL((k_roialign_bwd<T, V, POOL>), grid, dim3(BWD_THREADS), 0, scn::S(stream), dOut, argmax, tb, sample_of_box, \
+                       n_boxes, cv, g, dF)
+    if (argmax) {
+        if (wd) SCN_ROIALIGN_BWD(W, true); else SCN_ROIALIGN_BWD(N, true);
+    } else {
+        if (wd) SCN_ROIALIGN_BWD(W, false); else SCN_ROIALIGN_BWD(N, false);
+    }
+#undef SCN_ROIALIGN_BWD
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }
@@ -439,7 +563,7 @@ extern "C" int scn_roialign_fwd(const float* F, int batch, const int64_t* size_h
     if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
     if (n_boxes == 0) return SCN_OK;
     SCN_REQUIRE(F && boxes && sample_of_box && table && Out);
-    return roialign_fwd<float, 4, 1>(F, g, c, wide(c, F, Out), boxes, sample_of_box, n_boxes, table, Out, stream);
+    return roialign_fwd<float, 4, 1>(F, g, c, wide(c, F, Out), boxes, sample_of_box, n_boxes, table, Out, nullptr, stream);
 }
 
 extern "C" int scn_roialign_fwd_bf16(const uint16_t* F, int batch, const int64_t* size_host, int c, const float* boxes,
@@ -451,7 +575,7 @@ extern "C" int scn_roialign_fwd_bf16(const uint16_t* F, int batch, const int64_t
     if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
     if (n_boxes == 0) return SCN_OK;
     SCN_REQUIRE(F && boxes && sample_of_box && table && Out);
-    return roialign_fwd<uint16_t, 8, 8>(F, g, c, true, boxes, sample_of_box, n_boxes, table, Out, stream);
+    return roialign_fwd<uint16_t, 8, 8>(F, g, c, true, boxes, sample_of_box, n_boxes, table, Out, nullptr, stream);
 }
 
 extern "C" int scn_roialign_bwd(const float* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes, int batch,
@@ -466,7 +590,7 @@ extern "C" int scn_roialign_bwd(const float* dOut, const void* table, const int3
         return SCN_OK;
     }
     SCN_REQUIRE(dOut && table && sample_of_box);
-    return roialign_bwd<float, 4, 1>(dOut, table, sample_of_box, n_boxes, batch, g, c, wide(c, dOut, dF), dF, stream);
+    return roialign_bwd<float, 4, 1>(dOut, nullptr, table, sample_of_box, n_boxes, batch, g, c, wide(c, dOut, dF), dF, stream);
 }
 
 extern "C" int scn_roialign_bwd_bf16(const uint16_t* dOut, const void* table, const int32_t* sample_of_box, int64_t n_boxes,
@@ -482,7 +606,7 @@ extern "C" int scn_roialign_bwd_bf16(const uint16_t* dOut, const void* table, co
         return SCN_OK;
     }
     SCN_REQUIRE(dOut && table && sample_of_box);
-    return roialign_bwd<uint16_t, 8, 8>(dOut, table, sample_of_box, n_boxes, batch, g, c, true, dF, stream);
+    return roialign_bwd<uint16_t, 8, 8>(dOut, nullptr, table, sample_of_box, n_boxes, batch, g, c, true, dF, stream);
 }
 
 extern "C" int scn_dense_maxpool_fwd(const float* X, int64_t n_boxes, const int64_t* extent_host, int c, float* Y,
@@ -521,4 +645,120 @@ extern "C" int scn_dense_maxpool_bwd_bf16(const uint16_t* dY, const uint8_t* arg
     if (n_boxes == 0) return SCN_OK;
     SCN_REQUIRE(dY && argmax && dX);
     return maxpool_bwd<uint16_t, 8, 8>(dY, argmax, n_boxes, o, c, true, dX, stream);
+}
+
+// ---- RoiAlign + max pool in one pass (the class head without an input convolution cuts at the RPN stack's full width) ----
+namespace {
+
+int even_extract(const int64_t* extract_host) {
+    SCN_REQUIRE(extract_host);
+    for (int d = 0; d < 3; ++d) SCN_REQUIRE(extract_host[d] >= 2 && extract_host[d] % 2 == 0);
+    return SCN_OK;
+}
+
+}  // namespace
+
+extern "C" int scn_roialign_pool_fwd(const float* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                                     const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host, void* table,
+                                     float* Y, uint8_t* argmax, scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && c >= 1);
+    if (int rc = even_extract(extract_host)) return rc;
+    Geo g;
+    if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(F && boxes && sample_of_box && table && Y && argmax);
+    return roialign_fwd<float, 4, 1>(F, g, c, wide(c, F, Y), boxes, sample_of_box, n_boxes, table, Y, argmax, stream);
+}
+
+extern "C" int scn_roialign_pool_fwd_bf16(const uint16_t* F, int batch, const int64_t* size_host, int c, const float* boxes,
+                                          const int32_t* sample_of_box, int64_t n_boxes, const int64_t* extract_host,
+                                          void* table, uint16_t* Y, uint8_t* argmax, scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && c >= 1);
+    SCN_REQUIRE_BF16_LANES(c, F, Y);
+    if (int rc = even_extract(extract_host)) return rc;
+    Geo g;
+    if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(F && boxes && sample_of_box && table && Y && argmax);
+    return roialign_fwd<uint16_t, 8, 8>(F, g, c, true, boxes, sample_of_box, n_boxes, table, Y, argmax, stream);
+}
+
+extern "C" int scn_roialign_pool_bwd(const float* dY, const uint8_t* argmax, const void* table, const int32_t* sample_of_box,
+                                     int64_t n_boxes, int batch, const int64_t* size_host, int c, const int64_t* extract_host,
+                                     float* dF, scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && c >= 1 && dF);
+    if (int rc = even_extract(extract_host)) return rc;
+    Geo g;
+    if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
+    const int64_t cells = (int64_t)batch * g.X * g.Y * g.Z;
+    if (n_boxes == 0) {
+        SCN_HIP(hipMemsetAsync(dF, 0, (size_t)cells * c * sizeof(float), scn::S(stream)));
+        return SCN_OK;
+    }
+    SCN_REQUIRE(dY && argmax && table && sample_of_box);
+    return roialign_bwd<float, 4, 1>(dY, argmax, table, sample_of_box, n_boxes, batch, g, c, wide(c, dY, dF), dF, stream);
+}
+
+extern "C" int scn_roialign_pool_bwd_bf16(const uint16_t* dY, const uint8_t* argmax, const void* table,
+                                          const int32_t* sample_of_box, int64_t n_boxes, int batch, const int64_t* size_host,
+                                          int c, const int64_t* extract_host, uint16_t* dF, scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && c >= 1 && dF);
+    SCN_REQUIRE_BF16_LANES(c, dY, dF);
+    if (int rc = even_extract(extract_host)) return rc;
+    Geo g;
+    if (int rc = read_geo(size_host, extract_host, batch, n_boxes, &g)) return rc;
+    const int64_t cells = (int64_t)batch * g.X * g.Y * g.Z;
+    if (n_boxes == 0) {
+        SCN_HIP(hipMemsetAsync(dF, 0, (size_t)cells * c * sizeof(uint16_t), scn::S(stream)));      // (+0 in bf16 too)
+        return SCN_OK;
+    }
+    SCN_REQUIRE(dY && argmax && table && sample_of_box);
+    return roialign_bwd<uint16_t, 8, 8>(dY, argmax, table, sample_of_box, n_boxes, batch, g, c, true, dF, stream);
+}
+
+// ---- the reference's Reshaper behind the box grids: [R V, C] rows -> [R, C V] channel-major vectors, with the ReLU that
+// follows it in linear_layer folded in (`relu`).  One element per thread both ways: the side it WRITES is contiguous, the side
+// it reads is a box's own V x C block (a few KB: cached). ----
+namespace {
+
+__global__ void k_box_flatten_fwd(const float* __restrict__ X, int64_t n, int64_t v, int c, int relu, float* __restrict__ Y) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = t / (v * c), e = t - r * (v * c);
+        const int64_t ch = e / v, s = e - ch * v;
+        const float x = X[(r * v + s) * c + ch];
+        Y[t] = relu ? (x > 0.f || x != x ? x : 0.f) : x;      // (NaN stays NaN, as nn.ReLU keeps it)
+    }
+}
+
+__global__ void k_box_flatten_bwd(const float* __restrict__ X, const float* __restrict__ dY, int64_t n, int64_t v, int c,
+                                  int relu, float* __restrict__ dX) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = t / c, ch = t - row * c;
+        const int64_t r = row / v, s = row - r * v;
+        const float g = dY[(r * c + ch) * v + s];
+        dX[t] = !relu || X[t] > 0.f ? g : 0.f;
+    }
+}
+
+}  // namespace
+
+extern "C" int scn_box_flatten_fwd(const float* X, int64_t n_boxes, int64_t v, int c, int relu, float* Y, scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && v >= 1 && c >= 1 && v * c < (1ll << 31));
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(X && Y);
+    const int64_t n = n_boxes * v * c;
+    hipLaunchKernelGGL(k_box_flatten_fwd, dim3(scn::ew_grid(n, 256)), dim3(256), 0, scn::S(stream), X, n, v, c, relu, Y);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+extern "C" int scn_box_flatten_bwd(const float* X, const float* dY, int64_t n_boxes, int64_t v, int c, int relu, float* dX,
+                                   scn_stream_t stream) {
+    SCN_REQUIRE(n_boxes >= 0 && v >= 1 && c >= 1 && v * c < (1ll << 31));
+    if (n_boxes == 0) return SCN_OK;
+    SCN_REQUIRE(dY && dX && (X || !relu));
+    const int64_t n = n_boxes * v * c;
+    hipLaunchKernelGGL(k_box_flatten_bwd, dim3(scn::ew_grid(n, 256)), dim3(256), 0, scn::S(stream), X, dY, n, v, c, relu, dX);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
 }

@@ -1326,6 +1326,78 @@ class DenseMaxPoolFunction(torch.autograd.Function):
         return dX, None, None, None
 
 
+class RoiAlignPoolFunction(torch.autograd.Function):
+    """RoiAlignFunction then DenseMaxPoolFunction in one pass (scn_roialign_pool_fwd / _bwd): forward(F [B X Y Z, C], boxes,
+    sample_of_box, batch, size, extract (even), pad_boxes=0) -> [max(R, pad_boxes) ex/2 ey/2 ez/2, C].  The forward equals the
+    pair bit for bit, the backward as numbers; the [R ex ey ez, C] samples and their gradient are never written.  The rows of
+    the boxes R .. pad_boxes - 1 are zero and take no gradient, as in DenseMaxPoolFunction.  fp32 or a bf16-stored slab."""
+
+    @staticmethod
+    def forward(ctx, features, boxes, sample_of_box, batch, size, extract, pad_boxes=0):
+        X = _slab16(features, "RoiAlignPool")
+        hb = _is_bf16(X)
+        size, extract = tuple(int(s) for s in size), tuple(int(s) for s in extract)
+        batch, r, c = int(batch), int(boxes.shape[0]), X.shape[1]
+        if any(e % 2 or e < 2 for e in extract):
+            raise ValueError(f"RoiAlignPool: even extents required, got {extract}")
+        if X.shape[0] != batch * size[0] * size[1] * size[2]:
+            raise ValueError(f"RoiAlignPool: {X.shape[0]} rows are not a [{batch}, {size[0]}, {size[1]}, {size[2]}] volume")
+        if tuple(boxes.shape) != (r, 2, 3) or sample_of_box.shape[0] != r or sample_of_box.dtype != torch.int32:
+            raise ValueError("RoiAlignPool: boxes fp32 [R, 2, 3] and sample_of_box int32 [R] required")
+        boxes = _f32(boxes)
+        per = (extract[0] // 2) * (extract[1] // 2) * (extract[2] // 2)
+        rows = max(r, int(pad_boxes)) * per
+        Y = _new((rows, c), X, X.dtype)
+        arg = torch.empty((r * per, c), dtype=torch.uint8, device=X.device)
+        table = torch.empty(max(r, 1) * (3 * sum(extract) + 2 * sum(size)), dtype=torch.int32, device=X.device)
+        fwd = L.lib().scn_roialign_pool_fwd_bf16 if hb else L.lib().scn_roialign_pool_fwd
+        L.check(fwd(L.ptr(X), batch, _host3(size), c, L.ptr(boxes), L.ptr(sample_of_box), r, _host3(extract), L.ptr(table),
+                    L.ptr(Y), L.ptr(arg), L.stream()))
+        if rows > r * per:
+            Y[r * per:].zero_()
+        ctx.save_for_backward(table, sample_of_box, arg)
+        ctx.cfg = (batch, size, extract, r, c, per, hb)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        table, sample_of_box, arg = ctx.saved_tensors
+        batch, size, extract, r, c, per, hb = ctx.cfg
+        dY = dY.to(torch.bfloat16).contiguous() if hb else _f32(dY)          # (the padding boxes' rows lie behind r * per)
+        dF = _new((batch * size[0] * size[1] * size[2], c), dY, dY.dtype)
+        bwd = L.lib().scn_roialign_pool_bwd_bf16 if hb else L.lib().scn_roialign_pool_bwd
+        L.check(bwd(L.ptr(dY), L.ptr(arg), L.ptr(table), L.ptr(sample_of_box), r, batch, _host3(size), c, _host3(extract),
+                    L.ptr(dF), L.stream()))
+        return dF, None, None, None, None, None, None
+
+
+class BoxFlattenFunction(torch.autograd.Function):
+    """forward(X fp32 [R V, C], n_boxes R, relu=False) -> [R, C V], channel-major (column ch V + s: the reference's
+    `Reshaper` on [R, C, x, y, z]), with the ReLU that follows it folded in when `relu` (scn_box_flatten_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, features, n_boxes, relu=False):
+        X = _f32(_feat(features))
+        r, c = int(n_boxes), X.shape[1]
+        if r < 0 or (r == 0 and X.shape[0]) or (r and X.shape[0] % r):
+            raise ValueError(f"BoxFlatten: {X.shape[0]} rows are not {r} boxes")
+        v = X.shape[0] // r if r else 1
+        Y = _new((r, c * v), X)
+        L.check(L.lib().scn_box_flatten_fwd(L.ptr(X), r, v, c, int(bool(relu)), L.ptr(Y), L.stream()))
+        ctx.save_for_backward(X if relu else None)
+        ctx.cfg = (r, v, c, bool(relu))
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        (X,) = ctx.saved_tensors
+        r, v, c, relu = ctx.cfg
+        dY = _f32(dY)
+        dX = _new((r * v, c), dY)
+        L.check(L.lib().scn_box_flatten_bwd(L.ptr(X) if relu else None, L.ptr(dY), r, v, c, int(relu), L.ptr(dX), L.stream()))
+        return dX, None, None
+
+
 # ------------------------------------------------------------------------------------------------------
 # The permutation half of the reference's up-sampling RPN heads (anchor_network.py:127-219; scn_anchor_up.hip)
 # ------------------------------------------------------------------------------------------------------

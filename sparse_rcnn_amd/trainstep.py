@@ -91,8 +91,10 @@ class SparseStepModel(torch.nn.Module):
     """Backbone (+ mask branch for cfg3) as one module, so that one flat parameter buffer covers the step."""
 
     def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False, with_class=False,
-                 with_segmentation=False, upsample_heads=False, class_storage=None):
-        """class_storage (with_class="dense" on bf16 storage only; None: nothing changes): "bf16" builds the dense class branch
+                 with_segmentation=False, upsample_heads=False, class_storage=None, simple_class=False):
+        """simple_class (with_class="dense" only; False: nothing changes): the dense arm's head is the reference's class network
+        WITHOUT pooling (classhead.ReshapeClassBranch; `simple_class`, run.py:706-710) on the same kept volume, fp32.
+        class_storage (with_class="dense" on bf16 storage only; None: nothing changes): "bf16" builds the dense class branch
         with storage=torch.bfloat16 and hands it the RPN's volume in its stored dtype (`rpn.volume_stored`).
         upsample_heads (with_rpn="reference" only; False: nothing changes): the reference's committed RPN heads,
         rpn.AnchorNetworkUpsample with its extra strides and anchor groups, in place of the 1x1 heads.  On bf16-stored
@@ -117,6 +119,11 @@ class SparseStepModel(torch.nn.Module):
             raise ValueError("class_storage='bf16' stores the DENSE class branch's slabs in bf16: it needs the dense arm "
                              "(dense_class=True) on bf16 storage (dtype='bf16')")
         self.class_storage = class_storage
+        if simple_class and with_class != "dense":
+            raise ValueError("simple_class=True is a head of the dense arm: it needs dense_class=True")
+        if simple_class and class_storage:
+            raise ValueError("simple_class=True computes in fp32 (it widens a bf16 volume on entry): class_storage='bf16' "
+                             "belongs to DenseClassBranch")
         if upsample_heads and with_rpn != "reference":
             raise ValueError("upsample_heads=True needs with_rpn='reference' (the reference's two anchor levels)")
         if with_rpn == "reference" and upsample_heads:
@@ -148,12 +155,15 @@ class SparseStepModel(torch.nn.Module):
         if with_class:
             if self.rpn is None:
                 raise ValueError("with_class needs an RPN (the class branch reads its coarsest level)")
-            from .classhead import ClassBranch, DenseClassBranch
+            from .classhead import ClassBranch, DenseClassBranch, ReshapeClassBranch
             if with_class == "dense":
                 src = self.rpn.levels[self.rpn.class_output_index] if hasattr(self.rpn, "levels") else self.rpn
                 self.class_level = self.rpn_levels[self.rpn.class_output_index if hasattr(self.rpn, "levels") else 0]
-                self.class_branch = DenseClassBranch(src.width, src.stride,
-                                                     **(dict(storage=torch.bfloat16) if class_storage else {}))
+                if simple_class:
+                    self.class_branch = ReshapeClassBranch(src.width, src.stride)
+                else:
+                    self.class_branch = DenseClassBranch(src.width, src.stride,
+                                                         **(dict(storage=torch.bfloat16) if class_storage else {}))
             else:
                 self.class_level = self.rpn_levels[-1]
                 self.class_branch = ClassBranch(channels[self.class_level], 2 ** self.class_level)
@@ -168,8 +178,8 @@ class SparseStepModel(torch.nn.Module):
     def run_class(self, interims, boxes):
         """The class branch on `boxes`: the sparse arm reads the encoder level, the dense arm the volume the RPN kept in the
         same forward (run_rpn comes first)."""
-        from .classhead import DenseClassBranch
-        if isinstance(self.class_branch, DenseClassBranch):
+        from .classhead import DenseClassBranch, ReshapeClassBranch
+        if isinstance(self.class_branch, (DenseClassBranch, ReshapeClassBranch)):
             if self.rpn.volume is None:
                 raise L.ScnError("the dense class branch reads the RPN's kept volume: run_rpn first")
             slab, size, batch, md = self.rpn.volume_stored if self.class_storage else self.rpn.volume
@@ -182,8 +192,14 @@ class SceneStep:
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
-                 upsample_heads=False, class_storage=None):
-        """class_storage (with dense_class=True and dtype="bf16"; None: nothing changes): "bf16" keeps the dense class branch's
+                 upsample_heads=False, class_storage=None, simple_class=False):
+        """simple_class (with dense_class=True; False: nothing changes): the class branch is the reference's class network WITHOUT
+        pooling (classhead.ReshapeClassBranch; `simple_class`, run.py:706-710, the `cs8_dense8max4_reshape` runs): RoiAlign to 8^3
+        straight out of the RPN stack's volume at its full width, max pool 2, one 3^3 same-convolution to 8 channels, flatten,
+        ReLU Linear(512, 64) ReLU Linear(64, 18) -- RoiAlign and max pool as one pass (scn_roialign_pool_fwd / _bwd).  fp32: in a
+        bf16 step the head widens the volume on entry; with class_storage="bf16" ValueError.  Selector, losses, predict() and
+        evaluate() are those of the dense arm.
+        class_storage (with dense_class=True and dtype="bf16"; None: nothing changes): "bf16" keeps the dense class branch's
         slabs bf16-stored (classhead.DenseClassBranch(storage=torch.bfloat16): input convolution, RoiAlign, max pool and strided
         levels on bf16 slabs with fp32 accumulation; linear layers and scores fp32) and hands it the RPN stack's volume as the
         stack stored it, instead of widening the volume to an fp32 branch.
@@ -256,6 +272,11 @@ class SceneStep:
         if class_storage and not (dense_class and dtype == "bf16"):
             raise ValueError("class_storage='bf16' needs dense_class=True and dtype='bf16'")
         self.class_storage = class_storage
+        if simple_class and not dense_class:
+            raise ValueError("simple_class=True is a head of the dense arm: it needs dense_class=True")
+        if simple_class and class_storage:
+            raise ValueError("simple_class=True computes in fp32: class_storage='bf16' belongs to the pooling dense head")
+        self.simple_class = bool(simple_class)
         if upsample_heads and workload != "ref-crop-rpn":
             raise ValueError("upsample_heads=True is the reference's RPN head: only ref-crop-rpn has its two anchor levels")
         self.upsample_heads = bool(upsample_heads)
@@ -338,7 +359,8 @@ class SceneStep:
                                      with_class="dense" if self.dense_class else self.class_loss,
                                      with_segmentation=self.segmentation_loss,
                                      **(dict(upsample_heads=True) if self.upsample_heads else {}),
-                                     **(dict(class_storage=class_storage) if class_storage else {})).to(self.device)
+                                     **(dict(class_storage=class_storage) if class_storage else {}),
+                                     **(dict(simple_class=True) if self.simple_class else {})).to(self.device)
         if self.with_rpn:
             self._init_rpn()
         self.rpn_loss = bool(rpn_loss)
@@ -873,7 +895,15 @@ class SceneStep:
             s += f"; ground truth: the first {self.n_gt} synthetic boxes per sample"
         if self.class_loss:
             cb = self.model.class_branch
-            s += (("; the DENSE class branch (1^3 conv + 1 unit @32 on the stride-" + str(cb.stride) + " volume of the RPN's dilation "
+            s += (("; the RESHAPING class head of the dense arm (`simple_class`: no input convolution; RoiAlign to " +
+                   "x".join(map(str, cb.cut_shape)) + " and max pool 2 in one pass out of the stride-" + str(cb.stride) +
+                   " volume of the RPN's dilation stack at its full width (scn_roialign_pool_fwd / _bwd" +
+                   ("" if cb.fused else ": OFF, the two-call pair") + "), " +
+                   ", ".join(f"3^3 same-conv {m.nIn}->{m.nOut}" for m in cb.output_conv_layer) + " on fully active box grids, "
+                   "channel-major flatten, Linear " + "-".join(str(m.in_features) for m in cb.linear_layer
+                                                                if isinstance(m, torch.nn.Linear)) + f"-{cb.num_classes}, fp32"
+                   ") trains the stack too, on the reference's class loss: ") if self.simple_class else
+                  ("; the DENSE class branch (1^3 conv + 1 unit @32 on the stride-" + str(cb.stride) + " volume of the RPN's dilation "
                    "stack, RoiAlign to " + "x".join(map(str, cb.cut_shape)) + " (scn_roialign.hip), max pool 2 without clamp, "
                    "2^3/2 conv + unit @64 and @128 on fully active box grids, mean pool, Linear 128-64-18" +
                    (", its slabs bf16-STORED from the stack's stored volume to the mean pool (class_storage bf16: "
