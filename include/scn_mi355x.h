@@ -79,7 +79,8 @@ extern "C" {
  *      additive within 5: + scn_roialign_fwd_bf16 / _bwd_bf16, scn_dense_maxpool_fwd_bf16 / _bwd_bf16 (166 entry points);
  *      additive within 5: + scn_relu_fwd_bf16 / _bwd_bf16 (168 entry points);
  *      additive within 5: + scn_wgrad_plan_describe (169 entry points);
- *      additive within 5: + scn_roialign_pool_fwd / _bwd, their _bf16 forms, scn_box_flatten_fwd / _bwd (175 entry points) */
+ *      additive within 5: + scn_roialign_pool_fwd / _bwd, their _bf16 forms, scn_box_flatten_fwd / _bwd (175 entry points);
+ *      additive within 5: + scn_loss_combine / scn_loss_combine_bwd (177 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -980,6 +981,37 @@ int scn_xent_fwd(const float* logits, int64_t n, int c, const int64_t* targets, 
 int scn_xent_bwd(const float* grad_loss, const float* logits, int64_t n, int c, const int64_t* targets, const float* weights,
                  int64_t ignore_index, const void* scratch, float* dlogits, scn_stream_t stream);
 int scn_softmax_argmax(const float* logits, int64_t n, int c, float* probabilities, int64_t* indices, scn_stream_t stream);
+
+/* ---- the loss container (ndsis/modules/loss.py Loss.forward :101-191: the criteria's values combined with five log-weights) ----
+ * Both calls are one launch of one wave, graph-capturable (nothing is allocated, copied or waited for) and bitwise identical
+ * from run to run.  `terms` and `log_weights` are HOST arrays of SCN_LOSS_TERMS DEVICE pointers to 0-dim fp32 values, copied
+ * into the kernel arguments:
+ *   terms       = (rpn_score, rpn_bbox, class, mask, segmentation); a NULL entry: the term is absent
+ *   log_weights = (rpn_class, rpn_bbox, class, mask, segmentation), none NULL: the reference's parameters -log(weight)
+ * Term i is scaled by c_i = exp(-w[p(i)]) with the reference's crossing p = (1, 0, 2, 3, 4): the rpn_score term uses the
+ * rpn_bbox weight and the rpn_bbox term the rpn_class weight (loss.py:111-114).  Over the present terms, in the order above,
+ * each fp32 operation rounded once:
+ *   loss = ((0 + t_0 c_0) + t_1 c_1) + ...      extra = ((0 + w[p(0)]) + w[p(1)]) + ...      combined = loss + extra
+ * An absent term adds nothing, and neither does its weight.
+ *
+ * scn_loss_combine: record fp32 [SCN_LOSS_RECORD] = (loss `_total_`, combined `_total_multitask_`, t_0 .. t_4 with 0 where
+ * absent, the number of present terms that are NaN).  root_grad fp32 [SCN_LOSS_TERMS] (may be NULL) = scale * c_i, 0 where
+ * absent: the gradient of scale * combined at term i.  weight_grad (may be NULL): HOST array of SCN_LOSS_TERMS DEVICE
+ * pointers in the order of log_weights, entries may be NULL; for a present term i, *weight_grad[p(i)] += scale * (1 - t_i c_i)
+ * (accumulated: micro-batches add up; the caller zeroes); the slot of an absent term's weight is not touched.  Distinct
+ * entries must not alias.  running (may be NULL): double [SCN_LOSS_RECORD + 1], the record's entries added to the first
+ * SCN_LOSS_RECORD sums and 1 to the last (the caller zeroes it; one running record per stream at a time).  scale: finite.
+ * Every pointer 4-byte aligned (running: 8), else SCN_EINVAL.  All stores go to these fixed-size buffers.
+ *
+ * scn_loss_combine_bwd: the same quantities times an upstream gradient read on the device: term_grad fp32 [SCN_LOSS_TERMS]
+ * (may be NULL) = *grad * c_i, weight_grad fp32 [SCN_LOSS_TERMS] in the order of log_weights (may be NULL) [p(i)] =
+ * *grad * (1 - t_i c_i); both 0 where the term is absent.  Written, not accumulated. */
+#define SCN_LOSS_TERMS 5
+#define SCN_LOSS_RECORD 8
+int scn_loss_combine(const float* const* terms, const float* const* log_weights, float scale, float* record, float* root_grad,
+                     float* const* weight_grad, double* running, scn_stream_t stream);
+int scn_loss_combine_bwd(const float* grad, const float* const* terms, const float* const* log_weights, float* term_grad,
+                         float* weight_grad, scn_stream_t stream);
 
 /* ---- evaluation (ndsis/training/evaluation.py: MaskOverlapCalculator / BboxOverlapCalculator, PrecisionRecallCurve.
  * calc_tp_indicator, ConfusionCalculator, BinaryMaskConfusionCalculator; ndsis/utils/mask.py:62-148) ----

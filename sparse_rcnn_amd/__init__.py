@@ -17,7 +17,7 @@ from .modules import (AddTable, AveragePooling, BatchNormLeakyReLU, BatchNormReL
 from .tensor import SparseConvNetTensor                                    # noqa: F401
 from .custom_operations import SparseGlobalPool, split_batch               # noqa: F401  (device forms of the reference's own helpers)
 from . import optim                                                         # noqa: F401  (optim.Adam: the reference's optimizer)
-from . import loss                                                          # noqa: F401  (loss.RpnLoss, loss.MaskLoss, loss.ClassLoss, loss.CrossEntropyLoss: the reference's losses)
+from . import loss                                                          # noqa: F401  (loss.RpnLoss, loss.MaskLoss, loss.ClassLoss, loss.CrossEntropyLoss: the reference's losses; loss.Loss: its container)
 from . import classhead                                                     # noqa: F401  (classhead.ClassBranch, classhead.SegmentationHead)
 from . import sample                                                        # noqa: F401  (sample.convert_sample, sample.collate: stored scene -> training batch)
 

@@ -198,6 +198,8 @@ _SIGS = {
     "scn_sample_pack_drawn": (C.c_int, [p, i64, p, p, p, i32, p, C.c_uint64, C.c_uint64, f32, i32, f32, i32, i32, i32, i32, p, p, p,
                                         p, i64, p, p]),
     "scn_sample_cut_start": (C.c_int, [p, i64, p, p, C.c_uint64, C.c_uint64, p, p]),
+    "scn_loss_combine": (C.c_int, [C.POINTER(p), C.POINTER(p), f32, p, p, C.POINTER(p), p, p]),
+    "scn_loss_combine_bwd": (C.c_int, [p, C.POINTER(p), C.POINTER(p), p, p, p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -214,6 +216,7 @@ PYRAMID_DESC_LEN = 8 + PYRAMID_MAX_LEVELS * PYRAMID_LEVEL_STRIDE
 COLSUM_BLOCKS = 512
 SAMPLE_MAX_INSTANCES = 1023      # SCN_SAMPLE_MAX_INSTANCES
 ANCHOR_UP_MAX_GROUPS = 16        # SCN_ANCHOR_UP_MAX_GROUPS
+LOSS_TERMS, LOSS_RECORD = 5, 8   # SCN_LOSS_TERMS, SCN_LOSS_RECORD
 RNG_HOST, RNG_CUT, RNG_COLOR, RNG_NORMAL, RNG_COLOR_COMMON, RNG_NORMAL_COMMON = range(6)     # SCN_RNG_*: the streams
 
 

@@ -14,6 +14,9 @@
 //   k_xent_bwd     recomputes the row's softmax from the logits (the forward pass keeps nothing per row) and writes
 //                  g * w_t * (softmax - onehot) / W, or zeros for a dropped row.
 //   k_softmax_argmax   probabilities (optional) and the first index of the row's maximum, taken on the logits.
+//   k_loss_combine / k_loss_combine_bwd   the reference's `Loss` container (loss.py:101-191): the five 0-dim loss terms times
+//                  exp(-log-weight), summed in fp32 in the reference's order, plus the used log-weights; root and weight
+//                  gradients and the reporting record in the same launch.  One wave; lane i < 5 owns term i.
 // No float atomics; two runs on the same inputs are bitwise identical.
 #include "scn_common.h"
 
@@ -346,6 +349,127 @@ extern "C" int scn_softmax_argmax(const float* logits, int64_t n, int c, float* 
     else
         hipLaunchKernelGGL(k_softmax_argmax<false>, dim3(blocks), dim3(kThreads), 0, S(stream), logits, n, sh, probabilities,
                            (long long*)indices);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+// ---- the loss container (ndsis/modules/loss.py Loss.forward :101-191) ---------------------------------------------------
+namespace {
+
+constexpr int kTerms = SCN_LOSS_TERMS;
+
+struct CombineArgs {                                         // device pointers, carried in the kernel arguments
+    const float* term[kTerms];                               // NULL: the term is absent
+    const float* log_weight[kTerms];
+    float* weight_grad[kTerms];                              // NULL: not wanted
+};
+
+// The reference's crossing (loss.py:111-114): the rpn_score term is scaled by loss_rpn_bbox_weight, the rpn_bbox term by
+// loss_rpn_class_weight.
+__device__ __forceinline__ int weight_of_term(int i) { return i == 0 ? 1 : i == 1 ? 0 : i; }
+
+struct LaneTerm {
+    bool present;
+    float t, w, c, p;                                        // term, its log-weight, exp(-w), t * c
+    float* wg;
+};
+
+// Lane `lane` < 5 loads its term; the selects walk the argument struct with constant indices (no scratch copy of it).
+__device__ __forceinline__ LaneTerm load_term(const CombineArgs& a, int lane) {
+    const float *tp = nullptr, *wp = nullptr;
+    float* gp = nullptr;
+#pragma unroll
+    for (int k = 0; k < kTerms; ++k)
+        if (lane == k) {
+            tp = a.term[k];
+            wp = a.log_weight[weight_of_term(k)];
+            gp = a.weight_grad[weight_of_term(k)];
+        }
+    LaneTerm r;
+    r.present = lane < kTerms && tp != nullptr;
+    r.t = r.present ? *tp : 0.f;
+    r.w = r.present ? *wp : 0.f;
+    r.c = r.present ? expf(-r.w) : 0.f;
+    r.p = r.t * r.c;
+    r.wg = r.present ? gp : nullptr;
+    return r;
+}
+
+__global__ __launch_bounds__(64) void k_loss_combine(const CombineArgs a, float scale, float* __restrict__ record,
+                                                     float* __restrict__ root_grad, double* __restrict__ running) {
+    const int lane = (int)threadIdx.x;
+    const LaneTerm r = load_term(a, lane);
+    float loss = 0.f, extra = 0.f, nans = 0.f;               // the reference starts both sums from default_loss = 0
+    float mine = 0.f;                                        // record entry `lane` (lanes 0 .. 7)
+#pragma unroll
+    for (int k = 0; k < kTerms; ++k) {                       // every lane adds the same values in the reference's order
+        const bool pk = __shfl((int)r.present, k, 64) != 0;
+        const float pv = __shfl(r.p, k, 64), wv = __shfl(r.w, k, 64), tv = __shfl(r.t, k, 64);
+        if (pk) {
+            loss = loss + pv;
+            extra = extra + wv;
+            if (tv != tv) nans += 1.f;
+        }
+        if (lane == 2 + k) mine = tv;                        // (0 where the term is absent)
+    }
+    const float combined = loss + extra;
+    if (lane == 0) mine = loss;
+    if (lane == 1) mine = combined;
+    if (lane == 2 + kTerms) mine = nans;
+    if (lane < SCN_LOSS_RECORD) record[lane] = mine;
+    if (lane < kTerms) {
+        if (root_grad) root_grad[lane] = scale * r.c;
+        if (r.wg) *r.wg = *r.wg + scale * (1.f - r.p);
+    }
+    if (running) {                                           // double sums of the record's entries, then the call count
+        if (lane < SCN_LOSS_RECORD) running[lane] = running[lane] + (double)mine;
+        if (lane == SCN_LOSS_RECORD) running[lane] = running[lane] + 1.0;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_loss_combine_bwd(const CombineArgs a, const float* __restrict__ grad,
+                                                         float* __restrict__ term_grad, float* __restrict__ weight_grad) {
+    const int lane = (int)threadIdx.x;
+    const LaneTerm r = load_term(a, lane);
+    const float g = *grad;
+    if (lane < kTerms) {
+        if (term_grad) term_grad[lane] = r.present ? g * r.c : 0.f;
+        if (weight_grad) weight_grad[weight_of_term(lane)] = r.present ? g * (1.f - r.p) : 0.f;
+    }
+}
+
+int combine_args(CombineArgs& a, const float* const* terms, const float* const* log_weights, float* const* weight_grad) {
+    for (int k = 0; k < kTerms; ++k) {
+        a.term[k] = terms[k];
+        a.log_weight[k] = log_weights[k];
+        a.weight_grad[k] = weight_grad ? weight_grad[k] : nullptr;
+        if (!a.log_weight[k] || ((uintptr_t)a.log_weight[k] & 3) || ((uintptr_t)a.term[k] & 3) ||
+            ((uintptr_t)a.weight_grad[k] & 3))
+            return 1;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int scn_loss_combine(const float* const* terms, const float* const* log_weights, float scale, float* record,
+                                float* root_grad, float* const* weight_grad, double* running, scn_stream_t stream) {
+    SCN_REQUIRE(terms && log_weights && record && ((uintptr_t)record & 3) == 0 && ((uintptr_t)root_grad & 3) == 0);
+    SCN_REQUIRE(((uintptr_t)running & 7) == 0 && isfinite(scale));
+    CombineArgs a;
+    SCN_REQUIRE(combine_args(a, terms, log_weights, weight_grad) == 0);
+    hipLaunchKernelGGL(k_loss_combine, dim3(1), dim3(64), 0, S(stream), a, scale, record, root_grad, running);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+extern "C" int scn_loss_combine_bwd(const float* grad, const float* const* terms, const float* const* log_weights,
+                                    float* term_grad, float* weight_grad, scn_stream_t stream) {
+    SCN_REQUIRE(grad && terms && log_weights && ((uintptr_t)grad & 3) == 0);
+    SCN_REQUIRE(((uintptr_t)term_grad & 3) == 0 && ((uintptr_t)weight_grad & 3) == 0);
+    CombineArgs a;
+    SCN_REQUIRE(combine_args(a, terms, log_weights, nullptr) == 0);
+    hipLaunchKernelGGL(k_loss_combine_bwd, dim3(1), dim3(64), 0, S(stream), a, grad, term_grad, weight_grad);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

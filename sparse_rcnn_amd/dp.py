@@ -69,6 +69,8 @@ class FlatParams:
             off += n
         self._datas = [p.data for p in self.params]
         self._events, self._ev_used = [], 0
+        self._index = {id(p): i for i, p in enumerate(self.params)}
+        self._in_place = set()        # parameters whose `.grad` IS their view of flat_grad since the last zero_grad (adopt_views)
         self._setup_buckets(n_buckets)
 
     # ---- overlapped, bucketed all-reduce -----------------------------------------------------------------------
@@ -109,9 +111,44 @@ class FlatParams:
         for b, (ids, _) in enumerate(self.buckets):
             for i in ids:
                 self._bucket_of[i] = b
-        for i, p in enumerate(self.params):
-            p.register_post_accumulate_grad_hook(self._make_hook(i))
+        self._hooks = [self._make_hook(i) for i in range(len(self.params))]
+        for p, h in zip(self.params, self._hooks):
+            p.register_post_accumulate_grad_hook(h)
         self._reset_buckets()
+
+    def mark_ready(self, params):
+        """Count `params` as having their gradient, as their post-accumulate hooks would: for parameters whose `.grad` a kernel
+        fills outside autograd (the loss container's log-weights, trainstep.SceneStep).  Nothing to do without buckets."""
+        if not self.buckets:
+            return
+        for p in params:
+            self._hooks[self._index[id(p)]](p)
+
+    def adopt_views(self, params):
+        """Make the views of the flat gradient buffer the `.grad` of `params`: a kernel outside autograd then accumulates into
+        the buffer in place (the caller zeroes the views at the step's first micro-batch).  Packing neither copies these
+        gradients onto themselves nor zeroes them with the parameters that received none.  Until the next zero_grad().
+        -> the views, in the order of `params`."""
+        views = []
+        for p in params:
+            i = self._index[id(p)]
+            p.grad = self.grad_views[i]
+            self._in_place.add(i)
+            views.append(self.grad_views[i])
+        return views
+
+    def _pack(self, ids, flat_slice):
+        """The gradients of parameters `ids` into their views inside `flat_slice`; zeros for parameters that received none."""
+        grads = [(i, self.params[i].grad) for i in ids]
+        have = [(self.grad_views[i], g) for i, g in grads if g is not None and i not in self._in_place]
+        none = [self.grad_views[i] for i, g in grads if g is None]
+        if none:
+            if self._in_place:                   # (a kernel-filled view lies in the slice: zero only what has no gradient)
+                torch._foreach_zero_(none)
+            else:
+                flat_slice.zero_()
+        if have:
+            torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
 
     def _reset_buckets(self):
         self._pending = [len(ids) for ids, _ in self.buckets]
@@ -157,11 +194,7 @@ class FlatParams:
 
     def _launch_bucket(self, b):
         ids, flat_slice = self.buckets[b]
-        have = [(self.grad_views[i], self.params[i].grad) for i in ids if self.params[i].grad is not None]
-        if len(have) != len(ids):
-            flat_slice.zero_()
-        if have:
-            torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
+        self._pack(ids, flat_slice)
         if self.rank_weight != 1.0:
             flat_slice.mul_(self.rank_weight)
         self._works.append(dist.all_reduce(flat_slice, op=dist.ReduceOp.SUM, async_op=True))
@@ -169,16 +202,13 @@ class FlatParams:
     def zero_grad(self):
         for p in self.params:
             p.grad = None
+        self._in_place.clear()
         if self.buckets:
             self._reset_buckets()
 
     def gather_grads(self):
         """Pack the per-parameter gradients into the flat bucket (zeros for parameters that received none)."""
-        have = [(v, p.grad) for v, p in zip(self.grad_views, self.params) if p.grad is not None]
-        if len(have) != len(self.params):
-            self.flat_grad.zero_()
-        if have:
-            torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
+        self._pack(range(len(self.params)), self.flat_grad)
         self.flat_grad_valid = True
 
     # ---- exposed all-reduce time (HIP events on the compute stream around the final waits) ---------------------

@@ -13,7 +13,8 @@ Nothing on this path waits on the host: no `.item()`, `.cpu()` or `nonzero`.  Th
 the boxes only, so they can be queued before the network that produces rpn_score / rpn_bbox runs (`RpnLoss.prepare`).
 Each data-parallel rank normalises over its own samples (the reference's batch is one process).
 
-The mask loss (OverlapCalculator, TrainSelector, MaskLoss: the second half of this file) follows the same rules.
+The mask loss (OverlapCalculator, TrainSelector, MaskLoss: the second half of this file) follows the same rules, and so do the
+class and segmentation losses and the container that combines all of them (`Loss`: the end of this file).
 """
 from __future__ import annotations
 
@@ -810,3 +811,344 @@ class SegmentationPredictor(nn.Module):
 
     def forward(self, tensor):
         return softmax_argmax(tensor)
+
+
+# ---- the loss container ---------------------------------------------------------------------------------------------------
+# The reference's `Loss` (ndsis/modules/loss.py:12-209): the four criteria above behind one call, their values combined with
+# five log-weight parameters (learned with multitask_loss=True; the optimizer's third group, scannet_config/run.py:1441-1444).
+#
+#     rpn_score_loss, rpn_bbox_loss, class_loss, mask_loss, segmentation_loss (0-dim, on the device; absent ones left out)
+#     --scn_loss_combine-->  combined = sum t_i exp(-w_i) + sum w_i, and the 8-float record behind `sublosses`   (1 launch)
+#     backward: scn_loss_combine_bwd -> the five term gradients and the five weight gradients                       (1 launch)
+#
+# The reference reads seven values back per step (`.item()`, loss.py:116-189); here the record stays on the device until a
+# value of the mapping is asked for.
+
+import collections.abc
+
+__all__ += ["Loss", "LossCombiner", "LossRecord", "loss_combine", "TERM_NAMES", "WEIGHT_NAMES"]
+
+TERM_NAMES = ("rpn_score", "rpn_bbox", "class", "mask", "segmentation")
+# the log-weight parameters in the kernel's order, and the one that scales each term: the reference crosses the two RPN
+# weights (loss.py:111-114: rpn_score_loss * exp(-loss_rpn_bbox_weight), rpn_bbox_loss * exp(-loss_rpn_class_weight))
+WEIGHT_NAMES = ("loss_rpn_class_weight", "loss_rpn_bbox_weight", "loss_class_weight", "loss_mask_weight",
+                "loss_segmentation_weight")
+WEIGHT_OF_TERM = (1, 0, 2, 3, 4)
+RECORD_NAMES = ("_total_", "_total_multitask_") + TERM_NAMES + ("nan_terms",)
+
+combine_launches = 0                       # scn_loss_combine calls made through loss_combine (tests count them)
+
+
+def _scalar_f32(t, name):
+    if not torch.is_tensor(t):
+        raise ValueError(f"{name}: a tensor is required, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise L.ScnError(f"{name}: a GPU tensor is required (there is no CPU path)")
+    if t.dtype != torch.float32 or t.dim() != 0:
+        raise ValueError(f"{name}: a 0-dim fp32 tensor is required, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _pointer_table(tensors):
+    return (C.c_void_p * L.LOSS_TERMS)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def loss_combine(terms, log_weights, scale=1.0, root_grad=None, weight_grads=None, running=None):
+    """scn_loss_combine (include/scn_mi355x.h): terms = 5 device scalars in TERM_NAMES' order (None: absent), log_weights = 5
+    device scalars in WEIGHT_NAMES' order -> the record, fp32 [8] (RECORD_NAMES).  root_grad: fp32 [5] written with
+    scale * exp(-w); weight_grads: 5 device scalars (or None entries) that receive += scale * (1 - t exp(-w)); running:
+    float64 [9] sums.  One launch, no host wait."""
+    global combine_launches
+    terms, log_weights = list(terms), list(log_weights)
+    if len(terms) != L.LOSS_TERMS or len(log_weights) != L.LOSS_TERMS:
+        raise ValueError(f"{L.LOSS_TERMS} terms and {L.LOSS_TERMS} log-weights required")
+    for n, t in zip(TERM_NAMES, terms):
+        if t is not None:
+            _scalar_f32(t, n)
+    for n, w in zip(WEIGHT_NAMES, log_weights):
+        _scalar_f32(w, n)
+    dev = log_weights[0].device
+    if root_grad is not None and (root_grad.dtype != torch.float32 or root_grad.numel() < L.LOSS_TERMS or not root_grad.is_cuda
+                                  or not root_grad.is_contiguous()):
+        raise ValueError(f"root_grad: contiguous fp32 GPU [{L.LOSS_TERMS}] required")
+    if running is not None and (running.dtype != torch.float64 or running.numel() < L.LOSS_RECORD + 1 or not running.is_cuda
+                                or not running.is_contiguous()):
+        raise ValueError(f"running: contiguous float64 GPU [{L.LOSS_RECORD + 1}] required")
+    wg = None
+    if weight_grads is not None:
+        weight_grads = list(weight_grads)
+        if len(weight_grads) != L.LOSS_TERMS:
+            raise ValueError(f"weight_grads: {L.LOSS_TERMS} entries required")
+        for n, g in zip(WEIGHT_NAMES, weight_grads):
+            if g is not None:
+                _scalar_f32(g, n + " gradient")
+        wg = _pointer_table(weight_grads)
+    record = torch.empty(L.LOSS_RECORD, dtype=torch.float32, device=dev)
+    L.check(L.lib().scn_loss_combine(_pointer_table(terms), _pointer_table(log_weights), float(scale), L.ptr(record),
+                                     L.ptr(root_grad), wg, L.ptr(running), L.stream()))
+    combine_launches += 1
+    return record
+
+
+class LossRecord(collections.abc.Mapping):
+    """The reference's `sublosses` dict over the device record: keys `_total_`, `_total_multitask_` and the present terms in
+    the reference's order; the values become Python floats at the first access, through ONE copy of the 8 floats.
+    `.tensor`: the device record (RECORD_NAMES); `.isnan`: whether a present term was NaN."""
+
+    def __init__(self, tensor, present):
+        self.tensor = tensor
+        self._keys = RECORD_NAMES[:2] + tuple(n for n, p in zip(TERM_NAMES, present) if p)
+        self._host = None
+
+    def _values(self):
+        if self._host is None:
+            self._host = self.tensor.tolist()
+        return self._host
+
+    def __getitem__(self, key):
+        if key not in self._keys:
+            raise KeyError(key)
+        return self._values()[RECORD_NAMES.index(key)]
+
+    def __iter__(self):
+        return iter(self._keys)
+
+    def __len__(self):
+        return len(self._keys)
+
+    @property
+    def isnan(self):
+        return self._values()[L.LOSS_RECORD - 1] > 0
+
+    def __repr__(self):
+        return f"LossRecord({dict(self) if self._host is not None else list(self._keys)})"
+
+
+class _LossCombineFunction(torch.autograd.Function):
+    """(owner, t_0 .. t_4 or None, w_0 .. w_4) -> combined.  Backward: one launch, the gradients are views of one buffer."""
+
+    @staticmethod
+    def forward(ctx, owner, *tw):
+        terms, weights = tw[:L.LOSS_TERMS], tw[L.LOSS_TERMS:]
+        record = loss_combine(terms, weights, 1.0, running=owner._running_for(weights[0].device))
+        owner._last_record = record
+        ctx.present = tuple(t is not None for t in terms)
+        ctx.save_for_backward(*[t for t in terms if t is not None], *weights)
+        return record[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        weights = saved[len(saved) - L.LOSS_TERMS:]
+        it = iter(saved)
+        terms = [next(it) if p else None for p in ctx.present]
+        gg = g if (g.dtype == torch.float32 and g.is_contiguous()) else g.float().contiguous()
+        buf = torch.empty(2 * L.LOSS_TERMS, dtype=torch.float32, device=gg.device)
+        L.check(L.lib().scn_loss_combine_bwd(L.ptr(gg), _pointer_table(terms), _pointer_table(weights), buf.data_ptr(),
+                                             buf.data_ptr() + 4 * L.LOSS_TERMS, L.stream()))
+        used = [False] * L.LOSS_TERMS
+        for i, p in enumerate(ctx.present):
+            used[WEIGHT_OF_TERM[i]] = p
+        need = ctx.needs_input_grad
+        out = [None]
+        out += [buf[i] if (ctx.present[i] and need[1 + i]) else None for i in range(L.LOSS_TERMS)]
+        out += [buf[L.LOSS_TERMS + j] if (used[j] and need[1 + L.LOSS_TERMS + j]) else None for j in range(L.LOSS_TERMS)]
+        return tuple(out)
+
+
+class LossCombiner(nn.Module):
+    """The five log-weight parameters of the reference's `Loss` (`loss_*_weight` = -log(weight), 0-dim fp32, requires_grad =
+    multitask_loss; `default_loss`) and the combination of term values with them.  `Loss` adds the criteria; a training step
+    that computes its terms itself (trainstep.SceneStep) owns this part alone.  weights: the five `loss_*_weight` values in
+    WEIGHT_NAMES' order; has: which of (rpn, class, mask, segmentation) get_weights() reports."""
+
+    def __init__(self, weights=(1, 1, 1, 1, 1), multitask_loss=False, has=(True, True, True, True)):
+        super().__init__()
+        weights = tuple(weights)
+        if len(weights) != L.LOSS_TERMS:
+            raise ValueError(f"{L.LOSS_TERMS} weights required")
+        for n, v in zip(WEIGHT_NAMES, weights):
+            if not (float(v) > 0 and float(v) < float("inf")):
+                raise ValueError(f"{n}: a positive finite weight required (its parameter is -log(weight)), got {v}")
+        self.multitask_loss = bool(multitask_loss)
+        self._has = tuple(bool(h) for h in has)
+        self.default_loss = nn.Parameter(torch.zeros([], dtype=torch.float32), requires_grad=False)
+        for n, v in zip(WEIGHT_NAMES, weights):
+            setattr(self, n, nn.Parameter(-torch.log(torch.tensor(v, dtype=torch.float32)), requires_grad=self.multitask_loss))
+        self._running = {}
+        self._last_record = None
+
+    def has(self):
+        return self._has
+
+    def log_weights(self):
+        return [getattr(self, n) for n in WEIGHT_NAMES]
+
+    def _running_for(self, device):
+        key = (device.type, device.index)
+        buf = self._running.get(key)
+        if buf is None:
+            buf = self._running[key] = torch.zeros(L.LOSS_RECORD + 1, dtype=torch.float64, device=device)
+        return buf
+
+    def combine(self, terms):
+        """terms: 5 device scalars in TERM_NAMES' order, None where absent -> (combined_loss, LossRecord)."""
+        terms = list(terms)
+        combined = _LossCombineFunction.apply(self, *terms, *self.log_weights())
+        return combined, LossRecord(self._last_record, [t is not None for t in terms])
+
+    def get_weights(self):
+        """The reference's dict (loss.py:193-209), its naming included: `rpn_score` reports exp(-loss_rpn_class_weight)
+        although that weight scales the rpn_bbox term.  One copy."""
+        w = torch.exp(-torch.stack([p.detach() for p in self.log_weights()])).tolist()
+        out = {}
+        rpn, cls, mask, seg = self.has()
+        if rpn:
+            out["rpn_score"], out["rpn_bbox"] = w[0], w[1]
+        if cls:
+            out["class"] = w[2]
+        if mask:
+            out["mask"] = w[3]
+        if seg:
+            out["segment"] = w[4]
+        return out
+
+    def running_means(self):
+        """Means of the record's entries (RECORD_NAMES; an absent term counts as 0) over the calls since reset_running(), and
+        `steps`, their number.  One copy per device the container ran on; {} before the first call."""
+        sums = None
+        for buf in self._running.values():
+            v = buf.tolist()
+            sums = v if sums is None else [a + b for a, b in zip(sums, v)]
+        if not sums or not sums[-1]:
+            return {}
+        out = {n: s / sums[-1] for n, s in zip(RECORD_NAMES, sums)}
+        out["steps"] = int(sums[-1])
+        return out
+
+    def reset_running(self):
+        for buf in self._running.values():
+            buf.zero_()
+
+
+class Loss(LossCombiner):
+    """`Loss(...)` of the reference (loss.py:12-209) with its signature and defaults: the criteria of this module behind one
+    call -- RpnLoss(BatchwiseBboxTargetSelector(**bbox_target_selector_kwargs), sigma), ClassLossSelector + ClassLoss,
+    MaskLoss (selector and loss fused), CrossEntropyLoss(segmentation_weights, ignore_index=-100), each built only when its
+    `calc_*` flag is on -- and the five parameters `loss_*_weight` = -log(weight), 0-dim fp32, learned when multitask_loss.
+    `default_loss` is kept, so the reference's state_dict keys map one to one.  seed: the selector's draw.
+
+    forward(batch, outputs) -> (combined_loss, sublosses) with the reference's keys (`gt_bbox`, `gt_label`, `gt_mask`,
+    `gt_segmentation`; `rpn_score`, `rpn_bbox`, `rpn_target_calculator`, `mpn_class`, `mpn_mask`, `spn_segmentation`,
+    `is_training`, `mpn_{class,mask}_coord_selection`, `mpn_{class,mask}_box_selection`, `roi_bbox`) and presence rules
+    (loss.py:106-171).  `mpn_*_coord_selection` is the branch's selection (RoiSelection, counts, splits) and
+    `mpn_*_box_selection` the TrainSelector's descriptors, as this package's MaskBranch / ClassBranch return them.
+    combined_loss: 0-dim device tensor, one autograd node over scn_loss_combine / scn_loss_combine_bwd (differentiable once);
+    sublosses: a LossRecord.  Nothing waits on the host.
+    The `len(...)` presence checks: the reference's `len(selected_class_pred)` / `len(selected_mask_pred)` count per-sample
+    lists, so they hold for any batch with a sample.  The class check here counts the same lists.  The mask check counts the
+    ROWS of `mpn_mask` (selector and loss are one module here): a batch whose mask rows exist but hold no positive is present
+    on both sides -- the criterion returns 0 (no valid row), the term is reported as 0, and its log-weight is still added to
+    `_total_multitask_` and gets the gradient 1 -- while a crop without any row makes the mask term ABSENT here, where the
+    reference reports 0 and adds the weight.
+
+    Refused (ValueError): calc_bbox with batchwise_subsample=False, sparse=False with calc_mask, a dtype other than fp32."""
+
+    def __init__(self, sigma=2., class_target_overlap_threshold=0.15, batchwise_subsample=False, class_weights=None,
+                 mask_class_weights=None, class_class_weights=None, segmentation_weights=None, sparse=False,
+                 loss_rpn_class_weight=1, loss_rpn_bbox_weight=1, loss_class_weight=1, loss_mask_weight=1,
+                 loss_segmentation_weight=1, multitask_loss=False, dtype=torch.get_default_dtype(), *, calc_bbox, calc_class,
+                 calc_mask, calc_segmentation, mask_positive_threshold, class_positive_threshold, class_negative_threshold,
+                 class_negative_label, seed=0, **bbox_target_selector_kwargs):
+        if dtype != torch.float32:
+            raise ValueError(f"Loss: dtype torch.float32 required (the criteria and the combining kernel are fp32), got {dtype}")
+        if calc_bbox and not batchwise_subsample:
+            raise ValueError("Loss: calc_bbox=True with batchwise_subsample=False (the reference's default) needs "
+                             "SamplewiseBboxTargetSelector, which is not provided on the device: pass batchwise_subsample=True, "
+                             "as the reference's committed configuration does (scannet_config/run.py)")
+        if calc_mask and not sparse:
+            raise ValueError("Loss: calc_mask=True with sparse=False needs DenseMaskLossSelector, which is not provided: the "
+                             "mask loss here is the sparse one (sparse=True)")
+        super().__init__((loss_rpn_class_weight, loss_rpn_bbox_weight, loss_class_weight, loss_mask_weight,
+                          loss_segmentation_weight), multitask_loss)
+        self.rpn_loss = (RpnLoss(BatchwiseBboxTargetSelector(seed=seed, **bbox_target_selector_kwargs), sigma)
+                         if calc_bbox else None)
+        self.overlap_calculator = OverlapCalculator() if (calc_class or calc_mask) else None
+        if calc_class:
+            self.class_loss_selector = ClassLossSelector(class_positive_threshold, class_negative_threshold,
+                                                         class_negative_label)
+            self.class_loss = ClassLoss(class_weights=class_class_weights)
+        else:
+            self.class_loss_selector = self.class_loss = None
+        self.mask_positive_threshold = mask_positive_threshold
+        self.mask_loss = MaskLoss(class_weights=mask_class_weights) if calc_mask else None
+        self.segmentation_loss = (CrossEntropyLoss(weight=segmentation_weights, ignore_index=-100)
+                                  if calc_segmentation else None)
+
+    def has(self):
+        return (self.rpn_loss is not None, self.class_loss is not None, self.mask_loss is not None,
+                self.segmentation_loss is not None)
+
+    def forward(self, batch, outputs):
+        terms = [None] * L.LOSS_TERMS
+        if "rpn_score" in outputs and "rpn_bbox" in outputs and self.rpn_loss is not None:
+            terms[0], terms[1] = self.rpn_loss(batch["gt_bbox"], outputs["rpn_target_calculator"], outputs["rpn_score"],
+                                               outputs["rpn_bbox"])
+        want_class = "mpn_class" in outputs and self.class_loss is not None
+        want_mask = "mpn_mask" in outputs and self.mask_loss is not None
+        overlaps = None
+        if (want_class or want_mask) and not outputs["is_training"]:
+            overlaps = self.overlap_calculator(outputs["roi_bbox"], batch["gt_bbox"])
+        if want_class:
+            pred, gts = self.class_loss_selector(outputs["mpn_class"], outputs["mpn_class_coord_selection"],
+                                                 outputs["mpn_class_box_selection"], overlaps, batch["gt_label"])
+            if len(pred):
+                terms[2] = self.class_loss(pred, gts)
+        if want_mask:
+            descs = outputs["mpn_mask_box_selection"]
+            if descs is None:          # the loss over all proposals: LossFilter(mask_positive_threshold)'s association
+                descs = [(None, None, None, torch.where(mx >= self.mask_positive_threshold, am, torch.full_like(am, -1)))
+                         for _, _, mx, am in overlaps]
+            if len(outputs["mpn_mask"]):
+                terms[3] = self.mask_loss(outputs["mpn_mask"], outputs["mpn_mask_coord_selection"], descs, batch["gt_label"],
+                                          batch["gt_mask"])
+        if "spn_segmentation" in outputs and self.segmentation_loss is not None:
+            terms[4] = self.segmentation_loss(outputs["spn_segmentation"], batch["gt_segmentation"])
+        return self.combine(terms)
+
+    # -- checkpoints ----------------------------------------------------------------------------------------------------
+    def load_reference_state_dict(self, state_dict, prefix="", strict=True):
+        """Load the reference `Loss`'s part of a checkpoint: `default_loss` and the five `loss_*_weight`; the criteria's class
+        weights (`mask_loss.class_weights`, `class_loss.loss.weight`, `segmentation_loss.weight`) where this container has the
+        criterion; `mask_loss.default_loss` is the reference MaskLoss's constant 0.
+        -> (missing reference keys, unused checkpoint keys under the prefix)."""
+        own = ("default_loss",) + WEIGHT_NAMES
+        used, missing = set(), []
+        with torch.no_grad():
+            for n in own:
+                v = state_dict.get(prefix + n)
+                if v is None:
+                    missing.append(n)
+                    continue
+                if tuple(v.shape) != ():
+                    raise ValueError(f"{prefix + n}: a 0-dim value required, got {tuple(v.shape)}")
+                getattr(self, n).copy_(v.to(torch.float32))
+                used.add(prefix + n)
+            for key, crit in (("mask_loss.class_weights", self.mask_loss),
+                              ("class_loss.loss.weight", self.class_loss.loss if self.class_loss is not None else None),
+                              ("segmentation_loss.weight", self.segmentation_loss)):
+                v = state_dict.get(prefix + key)
+                if v is not None and crit is not None:
+                    w = v.detach().to(torch.float32).contiguous()
+                    if isinstance(crit, MaskLoss):
+                        crit.class_weights = w
+                    else:
+                        crit.weight = w
+                    used.add(prefix + key)
+            if prefix + "mask_loss.default_loss" in state_dict and self.mask_loss is not None:
+                used.add(prefix + "mask_loss.default_loss")
+        unused = [k for k in state_dict if k.startswith(prefix) and k not in used]
+        if strict and (missing or unused):
+            raise KeyError(f"Loss.load_reference_state_dict: missing {missing}, unused {unused}")
+        return missing, unused

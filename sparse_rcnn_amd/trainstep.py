@@ -192,8 +192,20 @@ class SceneStep:
                  target=None, channels=None, grid=None, n_boxes=None, lr=None, weighting="equal", batches_per_step=1,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
-                 upsample_heads=False, class_storage=None, simple_class=False):
-        """simple_class (with dense_class=True; False: nothing changes): the class branch is the reference's class network WITHOUT
+                 upsample_heads=False, class_storage=None, simple_class=False, multitask_loss=False, loss_weights=None):
+        """loss_weights (None: nothing changes): a dict over `rpn_class`, `rpn_bbox`, `class`, `mask`, `segmentation` with the
+        reference's `loss_*_weight` values (default 1 each; run.py keeps `loss_segmentation_weight=1/8` as an option).  A key of
+        a loss that is off, an unknown key or a value that is not positive and finite: ValueError.
+        multitask_loss (False: nothing changes): the five log-weights -log(weight) are parameters of the step's model
+        (`model.loss_combiner`, loss.LossCombiner: the reference's `Loss(multitask_loss=True)`, loss.py:44-58), sit in the flat
+        buffer, are all-reduced with the rest and updated by FlatAdam / SGD.
+        With multitask_loss, or any weight other than 1, the step owns the reference's loss container: per micro-batch ONE
+        scn_loss_combine launch between forward and backward writes the gradients the loss roots are back-propagated with --
+        exp(-log-weight) / batches_per_step each, the two RPN roots with the reference's crossed weights (loss.py:111-114) -- and
+        adds the log-weights' gradients into their views of the flat gradient buffer.  `.loss_record`: the reference's
+        `sublosses` mapping of the last micro-batch (loss.LossRecord, on the device until read); `.loss_weights()`: the
+        reference's `get_weights()`.  Otherwise no container is built and no such launch is made.
+        simple_class (with dense_class=True; False: nothing changes): the class branch is the reference's class network WITHOUT
         pooling (classhead.ReshapeClassBranch; `simple_class`, run.py:706-710, the `cs8_dense8max4_reshape` runs): RoiAlign to 8^3
         straight out of the RPN stack's volume at its full width, max pool 2, one 3^3 same-convolution to 8 channels, flatten,
         ReLU Linear(512, 64) ReLU Linear(64, 18) -- RoiAlign and max pool as one pass (scn_roialign_pool_fwd / _bwd).  fp32: in a
@@ -246,7 +258,7 @@ class SceneStep:
         synthetic.make_segmentation of the scene's instances.  Its gradient REPLACES the seeded N(0, 1) gradient on the
         backbone output; the loss stays on the device as `.segmentation_losses`.
         With several losses on, the roots are summed with weight 1: the reference's `Loss` as configured (multitask_loss=False,
-        every weight 1, loss.py:44-58, run.py:876-898).
+        every weight 1, loss.py:44-58, run.py:876-898) -- unless loss_weights / multitask_loss say otherwise (above).
         n_gt (the `-rpn` workloads): the ground-truth instances per sample both losses see are the first n_gt synthetic boxes
         (None: all of them; ref-crop-rpn has 256 per crop, which would put > 3000 boxes through the mask branch).
         optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
@@ -288,6 +300,27 @@ class SceneStep:
         if n_gt is not None and int(n_gt) < 1:
             raise ValueError("n_gt >= 1 required")
         self.n_gt = None if n_gt is None else int(n_gt)
+        loss_on = {"rpn_class": bool(rpn_loss), "rpn_bbox": bool(rpn_loss), "class": bool(class_loss), "mask": bool(mask_loss),
+                   "segmentation": bool(segmentation_loss)}
+        weights = dict.fromkeys(loss_on, 1.0)
+        if loss_weights is not None:
+            if not isinstance(loss_weights, dict):
+                raise ValueError("loss_weights: a dict over " + ", ".join(loss_on) + " required")
+            for key, v in loss_weights.items():
+                if key not in loss_on:
+                    raise ValueError(f"loss_weights: unknown key {key!r} (the keys: " + ", ".join(loss_on) + ")")
+                if not loss_on[key]:
+                    raise ValueError(f"loss_weights[{key!r}]: that loss is off in this step")
+                v = float(v)
+                if not (v > 0 and v < float("inf")):
+                    raise ValueError(f"loss_weights[{key!r}]: a positive finite weight required, got {v}")
+                weights[key] = v
+        if multitask_loss and not any(loss_on.values()):
+            raise ValueError("multitask_loss=True needs at least one of rpn_loss, mask_loss, class_loss, segmentation_loss: it "
+                             "learns the weights of those losses")
+        # the loss container exists only when it has something to do: a learned or a non-unit weight
+        self._loss_weights = weights if (multitask_loss or any(v != 1.0 for v in weights.values())) else None
+        self.multitask_loss = bool(multitask_loss)
         if batches is not None:
             if not workload.endswith("-rpn"):
                 raise ValueError("batches= applies to the -rpn workloads (the ground truth feeds the RPN, mask and class losses)")
@@ -361,6 +394,12 @@ class SceneStep:
                                      **(dict(upsample_heads=True) if self.upsample_heads else {}),
                                      **(dict(class_storage=class_storage) if class_storage else {}),
                                      **(dict(simple_class=True) if self.simple_class else {})).to(self.device)
+        self.combiner = self.loss_record = None
+        if self._loss_weights is not None:
+            from .loss import LossCombiner
+            self.combiner = self.model.loss_combiner = LossCombiner(
+                tuple(self._loss_weights.values()), self.multitask_loss,
+                has=(bool(rpn_loss), bool(class_loss), bool(mask_loss), bool(segmentation_loss))).to(self.device)
         if self.with_rpn:
             self._init_rpn()
         self.rpn_loss = bool(rpn_loss)
@@ -416,6 +455,22 @@ class SceneStep:
                     sc["seg_target"] = torch.cat(make_segmentation(labels, masks)).to(self.device)
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
+        if self.combiner is not None:
+            self._root_grad = torch.zeros(L.LOSS_TERMS, dtype=torch.float32, device=self.device)
+            self._root_grad_views = [self._root_grad[i] for i in range(L.LOSS_TERMS)]
+            self._weight_params = self._weight_grad_views = self._weight_grad_slab = None
+            if self.multitask_loss:
+                # the five log-weights are the model's last parameters: their gradient views lie back to back in the flat buffer
+                index = {id(p): i for i, p in enumerate(self.flat.params)}
+                self._weight_params = self.combiner.log_weights()
+                self._weight_grad_views = [self.flat.grad_views[index[id(p)]] for p in self._weight_params]
+                first = self._weight_grad_views[0].storage_offset()
+                if [v.storage_offset() for v in self._weight_grad_views] != list(range(first, first + L.LOSS_TERMS)):
+                    raise L.ScnError("SceneStep: the log-weights are not adjacent in the flat gradient buffer")
+                self._weight_grad_slab = self.flat.flat_grad[first:first + L.LOSS_TERMS]
+                on = (self.rpn_loss, self.rpn_loss, self.class_loss, self.mask_loss, self.segmentation_loss)
+                self._weights_on = [p for p, o in zip(self._weight_params, on) if o]
+                self._weight_grad_views = [v if o else None for v, o in zip(self._weight_grad_views, on)]
         self.adam = None
         if optimizer == "adam":
             from .optim import FlatAdam
@@ -510,6 +565,41 @@ class SceneStep:
             nx = self._scenes[(k + 1) % self.batches_per_step]
             self._md_next = self.model.backbone.prefetch_in_thread(nx["coords"], nx["size"], nx["batch_size"])
 
+    def _combine_losses(self, terms, term_pos, root_grads, zero):
+        """The loss container's launch of one micro-batch, between forward and backward: root_grads[term_pos[i]] becomes the
+        device scalar exp(-log-weight of term i) / batches_per_step, and with multitask_loss the log-weights' gradients are
+        added into their views of the flat gradient buffer (zeroed at the step's first micro-batch), which become their
+        `.grad`."""
+        from . import loss as RL
+        cb = self.combiner
+        views = None
+        if self.multitask_loss:
+            # only the weights of the losses that are on get a gradient: the others keep `grad is None`, as in the reference
+            views = self._weight_grad_views
+            if zero:
+                self._weight_grad_slab.zero_()
+            self.flat.adopt_views(self._weights_on)
+        record = RL.loss_combine(terms, cb.log_weights(), 1.0 / self.batches_per_step, root_grad=self._root_grad,
+                                 weight_grads=views, running=cb._running_for(self._root_grad.device))
+        self.loss_record = RL.LossRecord(record, [t is not None for t in terms])
+        for i, pos in term_pos.items():
+            root_grads[pos] = self._root_grad_views[i]
+        if self.multitask_loss and self.flat.sync:
+            self.flat.mark_ready(self._weights_on)       # (bucketed all-reduce: autograd never reaches these parameters)
+
+    def loss_weights(self):
+        """The reference's `Loss.get_weights()` for the losses of this step: exp(-log-weight) under its keys `rpn_score`,
+        `rpn_bbox`, `class`, `mask`, `segment` (one copy; without a container every weight is 1)."""
+        if self.combiner is not None:
+            return self.combiner.get_weights()
+        out = {}
+        if self.rpn_loss:
+            out["rpn_score"] = out["rpn_bbox"] = 1.0
+        for key, on in (("class", self.class_loss), ("mask", self.mask_loss), ("segment", self.segmentation_loss)):
+            if on:
+                out[key] = 1.0
+        return out
+
     def upstream_grads(self, k=0):
         """(dY of the backbone output, dY of the mask logits or None) of micro-batch k, BEFORE the 1 / batches_per_step scale."""
         return self._gys.get(k), self._gms.get(k)
@@ -533,6 +623,7 @@ class SceneStep:
         # cfg3-rpn: the RPN reads the ENCODER outputs only (model.py:141-160), so its heads, top-k and NMS are queued between
         # encoder and decoder, and the one host wait of the selection falls while the decoder's kernels run
         rpn_state = {}
+        terms, term_pos = [None] * L.LOSS_TERMS, {}     # the loss container's view of this micro-batch: values, root positions
 
         def rpn_after_encoder(interims):
             rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
@@ -566,6 +657,7 @@ class SceneStep:
             self.segmentation_losses = self.segmentation_criterion(seg_logits, seg_target)
             self.segmentation_out = (seg_logits, seg_target)
             root0, gys = self.segmentation_losses, self._seg_grad
+            terms[4], term_pos[4] = self.segmentation_losses, 0
             self.n_active = int(out.features.shape[0]) * self.batches_per_step
         else:
             gy = self._gys.get(k)
@@ -616,6 +708,8 @@ class SceneStep:
                     if calc.anchors.data_ptr() != anchors.data_ptr() or calc.anchors.shape != anchors.shape:
                         raise L.ScnError("SceneStep: the RPN loss's anchors are not the ones the RPN returned")
                     self.rpn_losses = self.rpn_criterion.loss(rpn_prep, rpn_score, rpn_bbox)
+                    terms[0], terms[1] = self.rpn_losses
+                    term_pos[0], term_pos[1] = len(roots), len(roots) + 1
                     roots += list(self.rpn_losses)           # (score_loss + bbox_loss) / batches_per_step
                     root_grads += [self._rpn_grad, self._rpn_grad]
                 else:
@@ -639,6 +733,7 @@ class SceneStep:
                 sel_scores, sel_labels = self.class_loss_selector(class_scores, csel, cdescs, overlaps, sc["gt_label"])
                 self.class_losses = self.class_criterion(sel_scores, sel_labels)
                 self.class_out = (class_scores, csel, cdescs, sel_labels)
+                terms[2], term_pos[2] = self.class_losses, len(roots)
                 roots.append(self.class_losses)
                 root_grads.append(self._class_grad)
             logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
@@ -649,7 +744,9 @@ class SceneStep:
                     logits.retain_grad()
                 self.mask_out = (selection, descs)
                 self.mask_losses = self.mask_criterion(logits, selection, descs, sc["gt_label"], sc["gt_mask"])
+                terms[3] = self.mask_losses
                 if self.mask_losses.requires_grad:
+                    term_pos[3] = len(roots)
                     roots.append(self.mask_losses)
                     root_grads.append(self._mask_grad)
                 self.n_roi_rows = int(logits.shape[0])
@@ -671,6 +768,8 @@ class SceneStep:
             # (an empty crop -- no proposal caught a point: the mask branch contributes nothing on this rank)
             if zero:
                 self.flat.zero_grad()
+            if self.combiner is not None:
+                self._combine_losses(terms, term_pos, root_grads, zero)
             _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
         self.out, self.logits, self.fin = out, logits, fin
 
@@ -918,6 +1017,14 @@ class SceneStep:
             s += ("; the segmentation head (SubM 1^3 to 20 classes, one row per point) trains on the reference's segmentation "
                   "loss: cross entropy against the instances' labels + 2, -100 (ignored) outside every instance; its gradient "
                   "replaces the synthetic one at the backbone output (scn_xent.hip)")
+        if self.combiner is not None:
+            s += ("; the losses are combined by the reference's loss container (loss.LossCombiner: loss = sum of term x "
+                  "exp(-log-weight) + the log-weights, the two RPN weights crossed as in loss.py:111-114; "
+                  + ("multitask_loss: the five log-weights are parameters in the flat buffer" if self.multitask_loss
+                     else "fixed weights " + ", ".join(f"{k} {v:g}" for k, v in self._loss_weights.items()))
+                  + "): one scn_loss_combine launch per micro-batch between forward and backward writes the roots' gradients"
+                  + (" and adds the log-weights' gradients into the flat gradient buffer" if self.multitask_loss else "")
+                  + " (scn_xent.hip)")
         if self.batches_per_step > 1:
             s += (f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
                   "voxels = all of them")
