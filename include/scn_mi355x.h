@@ -740,10 +740,12 @@ enum {
     SCN_OP_WGRAD_IDENT = 10, /* identity list: NiN / SubM 1^3 / Linear; aux = element offset into grads[w] (joined parts)     */
     SCN_OP_COLSUM = 11,      /* scn_colsum(_bf16): bias gradient alone                                                        */
     SCN_OP_ADD = 12,         /* y = x + x1 (scn_add / scn_add_bf16): the two gradient paths of a skip connection             */
-    SCN_OP_CAST = 13         /* storage cast: SCN_XF_BF16 set = fp32 -> bf16, else bf16 -> fp32                               */
+    SCN_OP_CAST = 13,        /* storage cast: SCN_XF_BF16 set = fp32 -> bf16, else bf16 -> fp32                               */
+    SCN_OP_RELU = 14,        /* y = max(x, 0) (scn_relu_fwd / _bf16), y may be x: the closing ReLU of a main-path residual unit */
+    SCN_OP_RELU_BWD = 15     /* y = x1 where m > 0, else 0 (scn_relu_bwd / _bf16): m = the slab the ReLU read OR wrote         */
 };
 #define SCN_XF_BF16 (1 << 16)        /* op flag: the op's feature slabs are bf16-stored                                      */
-#define SCN_XF_COARSE_ROWS (1 << 17) /* op flag (GEMM_IDENT / WGRAD_IDENT / COLSUM / ADD / CAST): rows = n_coarse of `level` */
+#define SCN_XF_COARSE_ROWS (1 << 17) /* op flag (GEMM_IDENT / WGRAD_IDENT / COLSUM / ADD / CAST / RELU / RELU_BWD): rows = n_coarse of `level` */
 
 typedef struct scn_exec_level {
     int64_t n;                       /* rows of this level */
@@ -773,7 +775,7 @@ typedef struct scn_exec_op {
     int32_t cin, cout;               /* of the CALL (backward-data calls swap the layer's) */
     int32_t x, y;                    /* buffer ids: source slab, destination slab (wgrad ops: X operand, dY operand) */
     int32_t r, m;                    /* residual operand, relu-mask operand; -1: none */
-    int32_t x1, y1;                  /* ROWS2: second source / second destination; WGRAD2: second operand pair; ADD: x1 */
+    int32_t x1, y1;                  /* ROWS2: second source / second destination; WGRAD2: second operand pair; ADD: x1; RELU_BWD: x1 = dY */
     int32_t c1;                      /* ROWS2: channels of the second source (fwd) / second destination (bwd) */
     int32_t w, b;                    /* params[] ids (weight or bf16 image, bias) -- wgrad / colsum ops: grads[] ids; -1: none */
     int32_t aux;                     /* WGRAD_IDENT: element offset into grads[w]; WGRAD_*: unused */

@@ -181,6 +181,16 @@ int run_op(const Ctx& c0, const scn_exec_op& o, void* own_scratch = nullptr) {
         if (h) return scn_cast_f32_to_bf16(B<float>(c, o.x), count, B<u16>(c, o.y), st);
         return scn_cast_bf16_to_f32(B<u16>(c, o.x), count, B<float>(c, o.y), st);
     }
+    case SCN_OP_RELU: {              // rows * cin elements; y == x: in place (every element is read once, by the thread that writes it)
+        const int64_t count = rows_of(o, L) * o.cin;
+        if (h) return scn_relu_fwd_bf16(B<u16>(c, o.x), count, B<u16>(c, o.y), st);
+        return scn_relu_fwd(B<float>(c, o.x), count, B<float>(c, o.y), st);
+    }
+    case SCN_OP_RELU_BWD: {          // y = x1 masked by the sign of m
+        const int64_t count = rows_of(o, L) * o.cin;
+        if (h) return scn_relu_bwd_bf16(B<u16>(c, o.m), B<u16>(c, o.x1), count, B<u16>(c, o.y), st);
+        return scn_relu_bwd(B<float>(c, o.m), B<float>(c, o.x1), count, B<float>(c, o.y), st);
+    }
     default:
         return scn::fail(SCN_EINVAL, "scn_exec_run: unknown op %s%lld", "", o.op);
     }

@@ -12,6 +12,8 @@ One node per LEVEL rather than per network: the parameter gradients of a level l
 ends, so the bucketed gradient all-reduce of dp.py still overlaps with the rest of backward, skip connections stay ordinary
 autograd edges, and the encoder outputs (`SparseUNet.interims`, the RPN's inputs in the reference) stay differentiable.
 
+Residual units: the plain pre-activation unit and the reference's bottleneck / main-path-ReLU forms (`_unit_blocks`).
+
 Not covered (the layer-by-layer path runs instead): batch norm, `bf16_blocks=True` (casts around every run of units),
 channel plans the two-source NetworkInNetwork kernel does not take, empty levels, and any step in which
 `profiling.TIMER` brackets single launches with events.
@@ -38,6 +40,7 @@ i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
 
 OP_GEMM_IDENT, OP_CONV_SUBM, OP_CONV_CHILD, OP_RULES_CHILD, OP_ROWS2 = 1, 2, 3, 4, 5
 OP_WGRAD_SUBM, OP_WGRAD2_SUBM, OP_WGRAD_DOWN, OP_WGRAD_UP, OP_WGRAD_IDENT, OP_COLSUM, OP_ADD, OP_CAST = 6, 7, 8, 9, 10, 11, 12, 13
+OP_RELU, OP_RELU_BWD = 14, 15
 XF_BF16, XF_COARSE_ROWS = 1 << 16, 1 << 17
 BACK = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
 
@@ -201,9 +204,16 @@ class Stage:
 
     # ---- residual units ----------------------------------------------------------------------------------------------
     def units_fwd(self, level, c, x, blocks, out_id=None):
-        """blocks: [(conv1, conv2)] of x + SubM3(ReLU(SubM3(ReLU(x)))) at `c` physical channels.  -> (output id, saved)"""
+        """blocks (`_unit_blocks`): (conv1, conv2) of x + SubM3(ReLU(SubM3(ReLU(x)))) at `c` physical channels, or a tagged tuple of
+        one of the other unit forms (`_form_fwd`).  -> (output id, saved)"""
         saved = []
-        for k, (c1, c2) in enumerate(blocks):
+        for k, blk in enumerate(blocks):
+            if isinstance(blk[0], str):                      # a bottleneck / main-path-ReLU unit (_unit_blocks)
+                y = out_id if (out_id is not None and k == len(blocks) - 1) else self.buf(level, c)
+                saved.append(self._form_fwd(level, c, x, y, blk))
+                x = y
+                continue
+            c1, c2 = blk
             m1, m2 = self.mod(c1, c), self.mod(c2, c)
             y1 = self.buf(level, c)
             y = out_id if (out_id is not None and k == len(blocks) - 1) else self.buf(level, c)
@@ -216,7 +226,13 @@ class Stage:
 
     def units_bwd(self, level, c, g, saved, din_id=None):
         """Backward of units_fwd: g = gradient of the last block's output -> id of the gradient of the first block's input."""
-        for k, (x, y1, m1, m2) in enumerate(reversed(saved)):
+        for k, sv in enumerate(reversed(saved)):
+            if isinstance(sv[0], str):
+                dx = din_id if (din_id is not None and k == len(saved) - 1) else self.buf(level, c, kind="b")
+                self._form_bwd(level, c, g, dx, sv)
+                g = dx
+                continue
+            x, y1, m1, m2 = sv
             dy1 = self.buf(level, c, kind="b")
             dx = din_id if (din_id is not None and k == len(saved) - 1) else self.buf(level, c, kind="b")
             self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dy1, m=y1, w=self.weight(m2, c, c, 27, BACK, True), flags=BACK | self.hb)
@@ -226,6 +242,65 @@ class Stage:
             self.op(self.bwd, OP_WGRAD2_SUBM, level, c, c, x=x, y=dy1, x1=y1, y1=g, w=gw, b=gb, flags=L.F_RELU_IN | self.hb)
             g = dx
         return g
+
+    # ---- the reference's other unit forms (unet.py header; module_factory.py:127-183) ----------------------------------------
+    # Each op is the call the layer-by-layer path makes for that layer (modules.Sequential: ReLU fused into the next
+    # convolution's gather, the AddTable into the last convolution's epilogue).  Backward, the two gradient paths of x meet in
+    # an SCN_OP_ADD -- layer by layer autograd adds them -- because the row GEMM has no "residual after the mask" epilogue and
+    # a bf16 slab must be rounded before the add to give autograd's bits.  The closing ReLU of a main-path unit is one
+    # SCN_OP_RELU in place on the unit's result; its backward masks by that result (y > 0 exactly where the sum was).
+    def _form_fwd(self, level, c, x, y, blk):
+        hb, relu = self.hb, L.F_RELU_IN | self.hb
+        form, main = blk[0], blk[0] in ("main", "both")
+        first = hb if main else relu                        # main_path_relu: no activation on the way in
+        if form == "main":
+            _, c1, c2 = blk
+            m1, m2 = self.mod(c1, c), self.mod(c2, c)
+            y1 = self.buf(level, c)
+            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=x, y=y1, w=self.weight(m1, c, c, 27, 0, True), b=self.param("b", m1), flags=first)
+            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=y1, y=y, r=x, w=self.weight(m2, c, c, 27, 0, True), b=self.param("b", m2), flags=relu)
+            sv = (form, x, y, y1, m1, m2)
+        else:
+            _, n1, kk, n2 = blk
+            ci = n1.nOut
+            m1, mk, m2 = self.mod(n1, c), self.mod(kk, ci), self.mod(n2, ci)
+            a, b = self.buf(level, ci), self.buf(level, ci)
+            self.op(self.fwd, OP_GEMM_IDENT, level, c, ci, x=x, y=a, w=self.param("w", m1), b=self.param("b", m1), flags=first)
+            self.op(self.fwd, OP_CONV_SUBM, level, ci, ci, x=a, y=b, w=self.weight(mk, ci, ci, 27, 0, True), b=self.param("b", mk), flags=relu)
+            self.op(self.fwd, OP_GEMM_IDENT, level, ci, c, x=b, y=y, r=x, w=self.param("w", m2), b=self.param("b", m2), flags=relu)
+            sv = (form, x, y, a, b, ci, m1, mk, m2)
+        if main:
+            self.op(self.fwd, OP_RELU, level, c, 0, x=y, y=y, flags=hb)
+        return sv
+
+    def _form_bwd(self, level, c, g, dx, sv):
+        hb, relu = self.hb, L.F_RELU_IN | self.hb
+        form, x, y = sv[:3]
+        main = form in ("main", "both")
+        first = hb if main else relu
+        if main:
+            gs = self.buf(level, c, kind="b")
+            self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=y, x1=g, y=gs, flags=hb)
+            g = gs
+        t = self.buf(level, c, kind="b")                    # the branch's gradient of x, before the skip's is added
+        if form == "main":
+            y1, m1, m2 = sv[3:]
+            dy1 = self.buf(level, c, kind="b")
+            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dy1, m=y1, w=self.weight(m2, c, c, 27, BACK, True), flags=BACK | hb)
+            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=dy1, y=t, w=self.weight(m1, c, c, 27, BACK, True), flags=BACK | hb)
+            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=hb)
+            self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=y1, y=g, w=self.gregion((m2, "w")), b=self.gregion((m2, "b")), flags=relu)
+            self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=x, y=dy1, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
+            return
+        a, b, ci, m1, mk, m2 = sv[3:]
+        db, da = self.buf(level, ci, kind="b"), self.buf(level, ci, kind="b")
+        self.op(self.bwd, OP_GEMM_IDENT, level, c, ci, x=g, y=db, m=b, w=self.param("w", m2), flags=BACK | hb)
+        self.op(self.bwd, OP_CONV_SUBM, level, ci, ci, x=db, y=da, m=a, w=self.weight(mk, ci, ci, 27, BACK, True), flags=BACK | hb)
+        self.op(self.bwd, OP_GEMM_IDENT, level, ci, c, x=da, y=t, m=-1 if main else x, w=self.param("w", m1), flags=BACK | hb)
+        self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=hb)
+        self.op(self.bwd, OP_WGRAD_IDENT, level, ci, c, x=b, y=g, w=self.gregion((m2, "w")), b=self.gregion((m2, "b")), flags=relu)
+        self.op(self.bwd, OP_WGRAD_SUBM, level, ci, ci, x=a, y=db, w=self.gregion((mk, "w")), b=self.gregion((mk, "b")), flags=relu)
+        self.op(self.bwd, OP_WGRAD_IDENT, level, c, ci, x=x, y=da, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
 
     # ---- finish -----------------------------------------------------------------------------------------------------
     def freeze(self):
@@ -240,6 +315,8 @@ class Stage:
         self.b_entries = [(k, 2 * d[1] + 1) for k, d in enumerate(self.params) if d[0] == "b"]
         self.img_entries = [(k, 2 * d[1]) + tuple(d[2:]) for k, d in enumerate(self.params) if d[0] not in ("w", "b")]
         self.grad_views = {}                              # tuple of parameter shapes -> (region offsets, total, views)
+        # a main-path unit that ends the stage: its backward masks by the stage's OUTPUT slab, which then is saved for backward
+        self.bwd_reads_out = any(getattr(op, f) == self.out_id for op in self.bwd for f in ("x", "y", "r", "m", "x1", "y1"))
         self._lean_slots()
         covered = sorted(m for reg in self.gregions for m in reg)
         want = sorted((i, k) for i in range(len(self.mods)) for k in ("w", "b"))
@@ -312,6 +389,51 @@ def _plain_blocks(unit_seq):
                 and c1.groups == 1 and c2.groups == 1):
             return None
         out.append((c1, c2))
+    return out
+
+
+def _unit_blocks(unit_seq):
+    """_plain_blocks with the reference's other unit forms: a plain unit stays (conv1, conv2); the others come as
+    ("bottleneck" | "both", N1, K, N2) and ("main", K1, K2) -- "both" and "main" close with a ReLU (main_path_relu).  None when
+    a block is none of them (batch norm, a layer without bias, channel padding, groups)."""
+    out = []
+    for block in unit_seq:
+        plain = _plain_blocks([block])
+        if plain is not None:
+            out += plain
+            continue
+        if not (type(block) is M.Sequential and len(block) in (2, 3) and type(block[0]) is M.ConcatTable
+                and type(block[1]) is M.AddTable and len(block[0]._modules) == 2):
+            return None
+        main = len(block) == 3
+        if main and type(block[2]) is not M.ReLU:
+            return None
+        a, inner = list(block[0]._modules.values())
+        if type(a) is not M.Identity or type(inner) is not M.Sequential:
+            return None
+        mods = list(inner._modules.values())
+        if not main:                                         # relu_first: the branch opens with the activation
+            if not mods or type(mods[0]) is not M.ReLU:
+                return None
+            mods = mods[1:]
+        if len(mods) not in (3, 5) or any(type(m) is not M.ReLU for m in mods[1::2]):
+            return None
+        convs = mods[0::2]
+        if any(type(m) is not M.SubmanifoldConvolution or m.bias is None or m.groups != 1 or m.pad_out_to for m in convs):
+            return None
+        sizes = tuple(m.filter_size for m in convs)
+        c = convs[0].nIn
+        if sizes == (3, 3):
+            if not main or any((m.nIn, m.nOut) != (c, c) for m in convs):
+                return None
+            out.append(("main", *convs))
+        elif sizes == (1, 3, 1):
+            ci = convs[0].nOut
+            if (convs[1].nIn, convs[1].nOut, convs[2].nIn, convs[2].nOut) != (ci, ci, ci, c):
+                return None
+            out.append(("both" if main else "bottleneck", *convs))
+        else:
+            return None
     return out
 
 
@@ -638,7 +760,7 @@ class StageFunction(torch.autograd.Function):
         # the packed weight images and the input slabs.  They stay alive exactly as long as autograd keeps the graph
         # (retain_graph=True: a second backward reads the same slabs; otherwise they are released when backward ends and a
         # second backward raises autograd's own "backward through the graph a second time" error).
-        ctx.save_for_backward(*[t for t in phys if t is not None], ws, *images, *inputs)
+        ctx.save_for_backward(*[t for t in phys if t is not None], ws, *images, *inputs, *([out] if stage.bwd_reads_out else []))
         return out
 
     @staticmethod
@@ -724,14 +846,18 @@ def _record_relu_masks(stage, ns, ws, offs, inputs, out):
     ext = dict(zip(stage.in_ids, inputs))
     ext[stage.out_id] = out
     for op in stage.fwd:
-        if not (op.flags & L.F_RELU_IN):
+        if op.op == OP_RELU:                             # in place: the result has the sign mask of what the ReLU read
+            src = op.y
+        elif op.flags & L.F_RELU_IN:
+            src = op.x
+        else:
             continue
-        lv, ch, es, kind = stage.bufs[op.x]
-        if op.x in ext:
-            t = ext[op.x]
+        lv, ch, es, kind = stage.bufs[src]
+        if src in ext:
+            t = ext[src]
         else:
             nb = ns[lv] * ch * es
-            t = ws[where[op.x]:where[op.x] + nb].view(torch.float32 if es == 4 else torch.bfloat16).view(ns[lv], ch)
+            t = ws[where[src]:where[src] + nb].view(torch.float32 if es == 4 else torch.bfloat16).view(ns[lv], ch)
         F._rec_relu(t)
 
 

@@ -313,6 +313,12 @@ class Sequential(torch.nn.Sequential):
                 if type(a) is Identity and type(inner) is Sequential and inner._ends_with_subm():
                     input = inner(input, residual=input.features)
                     i += 2
+                    if (i < len(mods) and type(mods[i]) is ReLU and FEATURE_STORAGE is torch.float32
+                            and input.features.dtype == torch.bfloat16):
+                        # the closing ReLU of a main-path unit (module_factory.py:163-168) inside a network that stores its
+                        # slabs in bf16 itself (SparseUNet bf16_blocks="all"): on the stored slab, as the step executor runs it
+                        input = _out(input, F.ReLUFunction.apply(input.features))
+                        i += 1
                     continue
             last = residual is not None and (i == len(mods) - 1 or (i == len(mods) - 2 and type(m) is ReLU))
             if (FUSE_RELU and type(m) is ReLU and i + 1 < len(mods)

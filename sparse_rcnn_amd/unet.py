@@ -2,11 +2,18 @@
 U-Net, expressed with this package's scn-API modules.
 
   encoder level l : {l = 0: SubM 1^3 Cin->C0 | l > 0: Convolution 2^3/2 C(l-1)->Cl}            (module_factory.py:438-486)
-                    + num_units x  [ x + SubM3(ReLU(SubM3(ReLU(x)))) ]                            (:127-183, relu_first)
+                    + num_units x  residual unit                                                  (:127-183, relu_first)
   decoder level l : ReLU -> Deconvolution 2^3/2 -> JoinTable([up, skip]) -> NetworkInNetwork(2C->C)
                     -> num_units x residual                                                       (:533-578; custom_container.py:70-83)
 
-Flags reproduced: relu_first=True, main_path_relu=False, bottleneck_divisor=0, drop_input_relu=True, num_units=2,
+Residual unit (get_residual_block, relu_first=True; act = ReLU, or BatchNormReLU with batchnorm; c = C // bottleneck_divisor;
+N = SubM 1^3, what the factory's get_channel_changer builds on the sparse side; K = SubM 3^3):
+  bottleneck_divisor=0, main_path_relu=False (default) :  y = x + K2(act(K1(act(x))))
+  bottleneck_divisor=d                                 :  y = x + N2(act(K(act(N1(act(x))))))        N1: C->c, K: c->c, N2: c->C
+  main_path_relu=True                                  :  y = act(x + K2(act(K1(x))))                no activation on the way in (:163-171)
+  both                                                 :  y = act(x + N2(act(K(act(N1(x))))))
+
+Flags reproduced: relu_first=True, main_path_relu and bottleneck_divisor as given, drop_input_relu=True, num_units=2,
 use_residuals=True, concat=True, batchnorm=False (scannet_config/run.py:516-519,609-623).
 """
 from __future__ import annotations
@@ -18,30 +25,57 @@ from . import modules as M
 from .ioLayers import InputLayer
 
 
-def residual_block(c, batchnorm=False):
-    """module_factory.py:51-57 sparse_residual(inner_block, Identity, None) with relu_first inner block."""
-    def act():
-        return M.BatchNormReLU(c) if batchnorm else M.ReLU()
-    inner = M.Sequential(act(), M.SubmanifoldConvolution(3, c, c, 3, not batchnorm),
-                         act(), M.SubmanifoldConvolution(3, c, c, 3, not batchnorm))
-    return M.Sequential(M.ConcatTable(M.Identity(), inner), M.AddTable())
+def inner_width(c, bottleneck_divisor):
+    """Width of a bottleneck unit's middle: C // bottleneck_divisor (module_factory.py:136); 0 is no unit at all."""
+    ci = int(c) // int(bottleneck_divisor)
+    if ci == 0:
+        raise ValueError(f"bottleneck_divisor={bottleneck_divisor} leaves a unit of {c} channels no inner channel "
+                         f"({c} // {bottleneck_divisor} == 0)")
+    return ci
 
 
-def units(c, num_units=2, batchnorm=False):
-    return M.Sequential(*[residual_block(c, batchnorm) for _ in range(num_units)])
+def residual_block(c, batchnorm=False, bottleneck_divisor=0, main_path_relu=False):
+    """module_factory.py:127-183 get_residual_block(relu_first=True) inside :51-57 sparse_residual(inner_block, Identity,
+    activation): the forms of the header comment, in the reference's nesting."""
+    def act(ch):
+        return M.BatchNormReLU(ch) if batchnorm else M.ReLU()
+    if bottleneck_divisor:
+        ci = inner_width(c, bottleneck_divisor)
+        body = [M.SubmanifoldConvolution(3, c, ci, 1, not batchnorm), act(ci),
+                M.SubmanifoldConvolution(3, ci, ci, 3, not batchnorm), act(ci),
+                M.SubmanifoldConvolution(3, ci, c, 1, not batchnorm)]
+    else:
+        body = [M.SubmanifoldConvolution(3, c, c, 3, not batchnorm), act(c), M.SubmanifoldConvolution(3, c, c, 3, not batchnorm)]
+    if main_path_relu:                                       # the activation closes the unit instead of opening its branch
+        return M.Sequential(M.ConcatTable(M.Identity(), M.Sequential(*body)), M.AddTable(), act(c))
+    return M.Sequential(M.ConcatTable(M.Identity(), M.Sequential(act(c), *body)), M.AddTable())
 
 
-def reference_key_map(n_levels, num_units=2):
+def units(c, num_units=2, batchnorm=False, bottleneck_divisor=0, main_path_relu=False):
+    return M.Sequential(*[residual_block(c, batchnorm, bottleneck_divisor, main_path_relu) for _ in range(num_units)])
+
+
+def unit_conv_indices(bottleneck_divisor=0, main_path_relu=False):
+    """Positions of a unit's convolutions inside its inner Sequential (ConcatTable[1]): the activations between them take
+    the others, and relu_first without main_path_relu puts one in front."""
+    n = 3 if bottleneck_divisor else 2
+    first = 0 if main_path_relu else 1
+    return tuple(first + 2 * v for v in range(n))
+
+
+def reference_key_map(n_levels, num_units=2, bottleneck_divisor=0, main_path_relu=False):
     """state_dict key of the reference's FeatureExtractor (sparse + U-Net: `main_network` = SequentialInterims of encoder
     levels, `unet.module_list` = SkipConnectionReuniter per decoder level; module_factory.py:438-578, model.py:364-391)
     -> this package's parameter name (`SparseUNet.named_oracle_params`).  Checked against the key list of a reference
-    FeatureExtractor built on this package (tests/golden/dropin_feature_extractor.json)."""
+    FeatureExtractor built on this package (tests/golden/dropin_feature_extractor.json; the bottleneck / main-path-ReLU
+    forms: tests/golden/unit_forms_keys.json)."""
     out = {}
+    conv_at = unit_conv_indices(bottleneck_divisor, main_path_relu)
     for l in range(n_levels):
         for t in ("weight", "bias"):
             out[f"main_network.{l}.0.0.{t}"] = f"enc{l}.in.{t}"
             for u in range(num_units):
-                for v, idx in enumerate((1, 3)):                 # Sequential(ReLU, SubM, ReLU, SubM) inside ConcatTable[1]
+                for v, idx in enumerate(conv_at):                # the unit's convolutions inside ConcatTable[1]
                     out[f"main_network.{l}.1.{u}.0.1.{idx}.{t}"] = f"enc{l}.res{u}.conv{v}.{t}"
     for i in range(n_levels - 1):
         l = n_levels - 2 - i
@@ -49,7 +83,7 @@ def reference_key_map(n_levels, num_units=2):
             out[f"unet.module_list.{i}.input_stage.1.{t}"] = f"dec{l}.up.{t}"
             out[f"unet.module_list.{i}.channel_changer.{t}"] = f"dec{l}.nin.{t}"
             for u in range(num_units):
-                for v, idx in enumerate((1, 3)):
+                for v, idx in enumerate(conv_at):
                     out[f"unet.module_list.{i}.output_stage.{u}.0.1.{idx}.{t}"] = f"dec{l}.res{u}.conv{v}.{t}"
     return out
 
@@ -59,8 +93,11 @@ class SparseUNet(nn.Module):
     resolution; ``.interims`` holds the encoder outputs (the reference's SequentialInterims, custom_container.py:5-12)."""
 
     def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False,
-                 identity_first=False, min_channels=0):
-        """identity_first: level 0 of the encoder is the reference's FLD('I') -- no layer at all, channels[0] == cin
+                 identity_first=False, min_channels=0, bottleneck_divisor=0, main_path_relu=False):
+        """bottleneck_divisor, main_path_relu: the form of every residual unit (header comment; the defaults build what this
+        class always built).  bf16_blocks="all" then also needs every unit's inner width C // bottleneck_divisor to be a
+        multiple of 8; bf16_blocks=True (the fused bf16 node of the plain unit) has no form for them: ValueError.
+        identity_first: level 0 of the encoder is the reference's FLD('I') -- no layer at all, channels[0] == cin
         (the mask head's internal U-Net: scannet_config/run.py:756-775, I -> B32/2 -> B48/2 -> B64/2; the decoder's
         level 0 still has its NiN(2 cin -> cin) + residual units, module_factory.py:533-578).
         min_channels: a decoder level is at least this wide (module_factory.py:789-804, `unet_params['min_channels'] = 16` in
@@ -69,6 +106,9 @@ class SparseUNet(nn.Module):
         16 channels: the mask network cut from the raw point features alone (7 channels in, 16 out)."""
         super().__init__()
         self.channels = tuple(channels)
+        self.bottleneck_divisor, self.main_path_relu = int(bottleneck_divisor or 0), bool(main_path_relu)
+        if self.bottleneck_divisor < 0:
+            raise ValueError("bottleneck_divisor >= 0 required")
         self.dec_channels = tuple(max(int(c), int(min_channels)) for c in self.channels[:-1])
         self.out_channels = self.dec_channels[0] if self.dec_channels else self.channels[0]
         self.identity_first = bool(identity_first)
@@ -84,6 +124,20 @@ class SparseUNet(nn.Module):
         self.bf16_blocks = bool(bf16_blocks) and not self.bf16_all
         if bf16_blocks and (batchnorm or any(c % 8 for c in self.channels[1 if identity_first else 0:])):
             raise ValueError("bf16_blocks needs channel counts that are multiples of 8 and no batch norm")
+        new_form = bool(self.bottleneck_divisor) or self.main_path_relu
+        if new_form and self.bf16_blocks:
+            raise ValueError("bf16_blocks=True runs the plain residual unit as one fused bf16 node: with bottleneck_divisor or "
+                             "main_path_relu use bf16_blocks='all'")
+        if self.bottleneck_divisor:
+            widths = [w for l, w in enumerate(self.channels) if not (l == 0 and self.identity_first)] + list(self.dec_channels)
+            inner = sorted({inner_width(w, self.bottleneck_divisor) for w in widths})
+            if self.bf16_all and any(ci % 8 for ci in inner):
+                raise ValueError(f"bf16_blocks needs channel counts that are multiples of 8: bottleneck_divisor="
+                                 f"{self.bottleneck_divisor} gives inner widths {inner}")
+        if new_form and self.identity_first and self.channels[0] % 8:
+            raise ValueError("bottleneck_divisor / main_path_relu are not combined with a channel-padded level 0 "
+                             f"(identity_first on {self.channels[0]} channels)")
+        unit_kw = dict(bottleneck_divisor=self.bottleneck_divisor, main_path_relu=self.main_path_relu) if new_form else {}
         enc = []
         for l, c in enumerate(self.channels):
             if l == 0 and self.identity_first:
@@ -91,7 +145,7 @@ class SparseUNet(nn.Module):
                 continue
             head = (M.SubmanifoldConvolution(3, cin, c, 1, True) if l == 0
                     else M.Convolution(3, self.channels[l - 1], c, (2, 2, 2), (2, 2, 2), True))
-            enc.append(M.Sequential(head, units(c, num_units, batchnorm)))
+            enc.append(M.Sequential(head, units(c, num_units, batchnorm, **unit_kw)))
         self.encoder = nn.ModuleList(enc)
         dec = []
         for l in range(len(self.channels) - 2, -1, -1):
@@ -101,7 +155,7 @@ class SparseUNet(nn.Module):
                 up=M.Sequential(M.ReLU(), M.Deconvolution(3, cup, d, (2, 2, 2), (2, 2, 2), True)),
                 join=M.JoinTable(),
                 nin=M.NetworkInNetwork(d + c, d, True),
-                units=units(d, num_units, batchnorm))))
+                units=units(d, num_units, batchnorm, **unit_kw))))
         self.decoder = nn.ModuleList(dec)
         # identity_first with a level-0 width that is no multiple of 8 (the mask head's 23): the level runs on slabs
         # zero-padded to `phys0` columns (16-byte rows: vector kernels in fp32, bf16 storage possible at all); the caller
@@ -245,7 +299,7 @@ class SparseUNet(nn.Module):
 
     def _exec_plan(self):
         """Launch plans of the levels, compiled once from the module tree; False when this network is not covered (batch
-        norm, bf16_blocks=True, a block that is not the plain pre-activation unit, channel counts the two-source
+        norm, bf16_blocks=True, a block that is none of the residual-unit forms, channel counts the two-source
         NetworkInNetwork kernel does not take)."""
         plan = self.__dict__.get("_exec_plan_cache")
         if plan is not None:
@@ -255,8 +309,8 @@ class SparseUNet(nn.Module):
         ch, L = self.channels, len(self.channels)
         ok = not self.bf16_blocks and all(c % 8 == 0 for c in ch[1:]) and (self.phys0 % 8 == 0)
         ok = ok and self.dec_channels == tuple(ch[:-1])      # (min_channels in effect: the layer-by-layer path)
-        enc_blocks = [EX._plain_blocks(lvl[1]) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
-        dec_blocks = [EX._plain_blocks(d["units"]) for d in self.decoder]
+        enc_blocks = [EX._unit_blocks(lvl[1]) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
+        dec_blocks = [EX._unit_blocks(d["units"]) for d in self.decoder]
         heads = [lvl[0] for l, lvl in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
         ok = ok and EX._require_bias(*heads, *[d["up"][1] for d in self.decoder], *[d["nin"] for d in self.decoder])
         if ok and all(b is not None for b in enc_blocks + dec_blocks):
@@ -368,7 +422,9 @@ class SparseUNet(nn.Module):
         units_of += [(f"dec{len(self.channels) - 2 - i}", d["units"]) for i, d in enumerate(self.decoder)]
         for prefix, unit_seq in units_of:
             for u, block in enumerate(unit_seq):
-                for v, bn in enumerate(m for m in block[0][1] if isinstance(m, M._BatchNorm)):
+                bns = [m for m in block[0][1] if isinstance(m, M._BatchNorm)]
+                bns += [m for m in list(block)[2:] if isinstance(m, M._BatchNorm)]     # main_path_relu: the closing activation
+                for v, bn in enumerate(bns):
                     out[f"{prefix}.res{u}.bn{v}.running_mean"] = bn.running_mean
                     out[f"{prefix}.res{u}.bn{v}.running_var"] = bn.running_var
         return out
@@ -379,6 +435,9 @@ class SparseUNet(nn.Module):
             inner = block[0][1]
             for v, bn in enumerate(m for m in inner if isinstance(m, M._BatchNorm)):
                 out[f"{prefix}.res{u}.bn{v}.weight"], out[f"{prefix}.res{u}.bn{v}.bias"] = bn.weight, bn.bias
+            if len(block) > 2 and isinstance(block[2], M._BatchNorm):      # main_path_relu: the unit's closing activation
+                v = sum(isinstance(m, M._BatchNorm) for m in inner)
+                out[f"{prefix}.res{u}.bn{v}.weight"], out[f"{prefix}.res{u}.bn{v}.bias"] = block[2].weight, block[2].bias
             convs = [m for m in inner if isinstance(m, M.SubmanifoldConvolution)]
             for v, cv in enumerate(convs):
                 out[f"{prefix}.res{u}.conv{v}.weight"] = cv.weight
@@ -396,7 +455,8 @@ class SparseUNet(nn.Module):
             tail = "main_network.0.0.0.weight"
             prefix = next((k[:-len(tail)] for k in state_dict if k.endswith(tail)), "")
         own = self.named_oracle_params()
-        kmap = reference_key_map(len(self.channels))
+        num_units = len(self.decoder[0]["units"]) if len(self.decoder) else len(self.encoder[0][1])
+        kmap = reference_key_map(len(self.channels), num_units, self.bottleneck_divisor, self.main_path_relu)
         missing, used = [], set()
         with torch.no_grad():
             for rk, name in kmap.items():
@@ -426,9 +486,11 @@ class SparseUNet(nn.Module):
 class Backbone(nn.Module):
     """InputLayer(mode 4) + SparseUNet: what model.py:414-431 runs for sparse + include_unet."""
 
-    def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False):
+    def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False,
+                 bottleneck_divisor=0, main_path_relu=False):
         super().__init__()
-        self.unet = SparseUNet(cin, channels, num_units, batchnorm, bf16_blocks)
+        self.unet = SparseUNet(cin, channels, num_units, batchnorm, bf16_blocks, bottleneck_divisor=bottleneck_divisor,
+                               main_path_relu=main_path_relu)
 
     # How a forward without prepared metadata builds its index structures: False = step by step from Python (row-count
     # waits overlapped with kernel queueing: faster when nothing else can run meanwhile), True = one scn_pyramid_build
