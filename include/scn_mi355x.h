@@ -80,7 +80,8 @@ extern "C" {
  *      additive within 5: + scn_relu_fwd_bf16 / _bwd_bf16 (168 entry points);
  *      additive within 5: + scn_wgrad_plan_describe (169 entry points);
  *      additive within 5: + scn_roialign_pool_fwd / _bwd, their _bf16 forms, scn_box_flatten_fwd / _bwd (175 entry points);
- *      additive within 5: + scn_loss_combine / scn_loss_combine_bwd (177 entry points) */
+ *      additive within 5: + scn_loss_combine / scn_loss_combine_bwd (177 entry points);
+ *      additive within 5: + scn_conv_tiles_plan_describe (178 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -346,6 +347,25 @@ void scn_conv_tiles_path_counts(int64_t out[4], int reset);
  * than half the chip's waves -- the coarse levels of the reference's six-level plan (scannet_config/run.py:539-549: 2 983 /
  * 734 / 180 rows), deep levels of an ROI batch.  Same arithmetic per product, an element's sum associated by wave share. */
 int64_t scn_conv_tiles_split_count(int reset);
+/* Which path a scn_conv_tiles call takes (host only: launches nothing, allocates nothing; tests and tools).  The launcher
+ * takes every decision from the function that fills this report, under the developer switches set at the time of the call.
+ *   with_arrival: the call passes an `arrival` array.
+ *   xw_ptr_bits: bits 0-3 = the low 4 bits of X | W; bits 4-7 = the low 4 bits of W alone (a subset of bits 0-3: the
+ *   weight staging of a column-contiguous W depends on W's alignment only, the row gathers on both).
+ *   epilogue_ptr_bits: the low 4 bits of Y | bias | residual | relu_mask | scratch.
+ *   out[0]  stream: 1 = the call runs on the opt-in weight-streaming kernel (SCN_TS_STREAM=1, scn_conv_tss.hip); the other
+ *           fields then describe the k_conv_ts launch the call would make without the switch
+ *   out[1]  FULLK (raw-buffer fast path; 0: the general kernel)  out[2] WT (SCN_F_W_TRANSPOSED)
+ *   out[3]  VECN (16-byte weight staging along Cout)  out[4] PART (Cin no multiple of 32)
+ *   out[5]  TAIL (dead halves skipped, slices weighted)  out[6] a K-chunk tail of <= 16 channels exists  out[7] a column tail
+ *   out[8]  FUSED (in-launch K reduction)  out[9] the four-waves-per-tile loop  out[10] PROG: offsets staged before the barrier
+ *   out[11] K-chunks  out[12] column chunks
+ *   out[13] the largest number of workgroups a (column chunk, K-chunk) slice gets  out[14] workgroups of the launch
+ *   out[15] 1: the K-chunk sum of the call (its second launch, or scn_conv_tiles_finish) moves 16 bytes per thread, 0: 4
+ * n_out == 0 (the launcher returns without a launch): all zero.  SCN_EINVAL for arguments the launcher rejects and for
+ * pointer bits that are not 4-byte aligned. */
+int scn_conv_tiles_plan_describe(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags, int with_arrival,
+                                 int xw_ptr_bits, int epilogue_ptr_bits, int64_t out[16]);
 /* Second half of a scn_conv_tiles call made with SCN_F_SPLIT_SUM: adds the K-chunk slabs (no-op when cin <= 32: the
  * tile kernel has written Y).  Same arguments as that call. */
 int scn_conv_tiles_finish(int cin, int64_t n_out, const float* bias, const float* residual, const float* relu_mask,

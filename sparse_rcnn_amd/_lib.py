@@ -61,6 +61,7 @@ _SIGS = {
     "scn_wgrad_tiles32": (C.c_int, [p, i64, p, i64, p, p, p, p, p, p, i32, p]),
     "scn_conv_tiles_path_counts": (None, [C.POINTER(i64), i32]),
     "scn_conv_tiles_split_count": (i64, [i32]),
+    "scn_conv_tiles_plan_describe": (C.c_int, [i64, i32, i32, i64, i32, i32, i32, i32, i32, C.POINTER(i64)]),
     "scn_conv_tiles_finish": (C.c_int, [i32, i64, p, p, p, p, i32, i32, p, p]),
     "scn_conv_tiles_bf16_image_bytes": (i64, [i32, i32, i32]),
     "scn_conv_tiles_bf16_pack": (C.c_int, [p, i32, i32, i32, i32, p, p]),

@@ -731,9 +731,134 @@ extern "C" int64_t scn_conv_tiles_arrival_counters(int cin, int64_t n_out, int c
 }
 
 namespace scn {
+bool conv_tiles_stream_eligible(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags, unsigned xw_bits);
 int conv_tiles_stream(const float* X, int64_t n_in, int cin, const int32_t* tstab, const uint32_t* tile_mask,
                       const int32_t* perm, int n_off, int64_t n_out, const float* W, const float* bias, const float* residual,
                       const float* relu_mask, float* Y, int cout, int flags, hipStream_t st, bool* launched);
+}
+
+// The K-chunk sum moves 16 bytes per thread when every buffer it touches allows it (epi_bits: the low 4 bits of
+// slabs | Y | bias | residual | relu_mask; the slabs start 256 bytes into the scratch)
+static bool ts_finish_v4(int cout, unsigned epi_bits) { return cout % 4 == 0 && (epi_bits & 15) == 0; }
+
+// Everything the host decides about one scn_conv_tiles call -- the ONE place it is decided: the launcher launches what this
+// says, scn_conv_tiles_plan_describe reports it.
+//   x_bits / w_bits: the low 4 bits of X / W; epi_bits: of Y | bias | residual | relu_mask | scratch.
+struct TsPlan {
+    int64_t nt;                         // tiles
+    int n_chunks, n_kc;                 // column chunks, K-chunks
+    bool stream;                        // the opt-in weight-streaming kernel takes the call (scn_conv_tss.hip)
+    bool fused;                         // in-launch K reduction
+    bool wt, vec, vecn, fullk, part;    // k_conv_ts<WT, VEC, VECN, FULLK, PART, ...>
+    bool k_tail, n_tail, tail;          // a dead K half / column block exists; TAIL
+    bool split4;                        // the four-waves-per-tile loop
+    int prog_g0;                        // PROG: offsets staged before the barrier
+    size_t lds;
+    int wg_per_cu;
+    int64_t n_tg;                       // workgroups per slice of a launch without TAIL
+    TsSlices slices;                    // ... with TAIL, by slice class
+    int64_t grid_x;
+    bool finish_v4;                     // k_conv_ts_sum<4> (else <1>) where the call's K-chunk sum is a launch of its own
+};
+
+static TsPlan ts_plan(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags, bool with_arrival, unsigned x_bits,
+                      unsigned w_bits, unsigned epi_bits) {
+    TsPlan p;
+    p.nt = cdiv(n_out, TS_T);
+    p.n_chunks = (int)cdiv(cout, TS_CT);
+    p.n_kc = (int)cdiv(cin, TS_KC);
+    const int64_t nt = p.nt;
+    const int n_chunks = p.n_chunks, n_kc = p.n_kc;
+    // layers that would split K over workgroups at Cin = 64 / 128: the offset-outer weight-streaming kernel (scn_conv_tss.hip)
+    // (the fused mode's callers; the two-launch cross-check keeps k_conv_ts)
+    p.stream = n_kc > 1 && with_arrival &&
+               scn::conv_tiles_stream_eligible(n_in, cin, n_off, n_out, cout, flags, (x_bits | w_bits) & 15);
+    // the in-launch K reduction needs the caller's zeroed arrival counters and 32-bit slab offsets; without them (or when
+    // the caller asks for the two-launch form) the partial sums go to row-major slabs and k_conv_ts_sum adds them
+    p.fused = n_kc > 1 && with_arrival && !(flags & SCN_F_SPLIT_SUM) &&
+              nt * n_chunks * n_kc * (int64_t)(TS_T * TS_CT * 4) < (1ll << 31);
+    p.wt = flags & SCN_F_W_TRANSPOSED;
+    p.vec = (cin % 4 == 0) && ((x_bits & 15) == 0) && ((w_bits & 15) == 0);
+    p.vecn = (cout % 4 == 0) && ((w_bits & 15) == 0);
+    // the fast path addresses X through a raw buffer descriptor: 32-bit byte offsets, 24-bit row indices
+    p.fullk = p.vec && n_in < (1ll << 23) && n_in * cin * 4 < (1ll << 32) - (1ll << 24) &&
+              n_out < (1ll << 23) && n_out * cout * 4 < (1ll << 32) - (1ll << 24);
+    // Latency-bound levels (scn_conv_ts_small.inc): with fewer (tile, slice) pairs than half the chip's waves a launch is ONE
+    // tile's serial chain of up to 27 dependent gathers, so four waves share a tile.  Decided from the tile and slice counts
+    // alone: every form of a layer (fused / two-launch K reduction, TAIL / padded slices) takes the same loop.
+    // SCN_TS_SPLIT=0: never (A/B; the cross-check in the tests -- the two loops associate an element's sum differently).
+    const scn::SwitchVal sp_sw = scn::sw(scn::SW_TS_SPLIT);            // (scn_debug_set: the tests switch it inside one process)
+    const int64_t sp_max = scn::sw(scn::SW_TS_SPLIT_MAX).set ? scn::sw(scn::SW_TS_SPLIT_MAX).i : 2048;   // (developer switch)
+    p.split4 = p.fullk && nt * n_chunks * n_kc <= sp_max && !(sp_sw.set && sp_sw.i == 0);
+    const int tiles_per_round = p.split4 ? TS_NW / 4 : TS_NW;
+    p.lds = (size_t)n_off * TS_KC * TS_CT * sizeof(float) + 16 + (p.split4 ? (size_t)2 * (TS_NW / 4) * 3 * 2 * 64 * 16 : 0);   // two buffers of partial tiles
+    p.wg_per_cu = (int)((160 * 1024) / p.lds);
+    if (p.wg_per_cu > 2) p.wg_per_cu = 2;              // 16 waves each: 2 workgroups fill a CU
+    if (p.wg_per_cu < 1) p.wg_per_cu = 1;
+    // grid sized to the chip: workgroups per (column chunk, K-chunk) slice; a workgroup should see at least ~16 tiles
+    p.n_tg = ((int64_t)scn::cu_budget() * p.wg_per_cu) / ((int64_t)n_chunks * n_kc);
+    if (p.n_tg > cdiv(nt, tiles_per_round)) p.n_tg = cdiv(nt, tiles_per_round);
+    if (p.n_tg < 1) p.n_tg = 1;
+    p.part = cin % TS_KC != 0;
+    // TAIL: a dead K half or a dead column block exists (the reference's 48 / 80 / 112-channel layers): those MFMAs are
+    // skipped and the slices get workgroups in proportion to their cost.  Estimated cost of a tile step relative to a
+    // full 16-MFMA step: one dead half 0.70, both 0.50 (the per-step fixed work -- index load, gathers, ~15 VALU -- does
+    // not shrink with the MFMAs; calibrated with tools/ablate_conv_tail.py on the 48 / 80 / 112-channel layers:
+    // profiles/r3_ablate_conv_tail.txt).
+    p.k_tail = cin % TS_KC != 0 && cin % TS_KC <= 16;
+    p.n_tail = cout % TS_CT != 0 && cout % TS_CT <= 16;
+    p.tail = p.fullk && (p.k_tail || p.n_tail) && !scn::sw(scn::SW_TS_NO_TAIL).set;
+    p.slices = {0, 0, 0, 0};
+    p.grid_x = p.n_tg * n_chunks * n_kc;
+    if (p.tail) {
+        const double w_half = scn::sw(scn::SW_TS_W_HALF).set ? scn::sw(scn::SW_TS_W_HALF).f : 0.70;
+        const double w_both = scn::sw(scn::SW_TS_W_BOTH).set ? scn::sw(scn::SW_TS_W_BOTH).f : 0.50;
+        const int ncf = n_chunks - (p.n_tail ? 1 : 0), nkf = n_kc - (p.k_tail ? 1 : 0);
+        const double wsum = (double)nkf * ncf + (p.n_tail ? nkf * w_half : 0.0) + (p.k_tail ? ncf * w_half : 0.0) +
+                            (p.n_tail && p.k_tail ? w_both : 0.0);
+        const int64_t total_wg = (int64_t)scn::cu_budget() * p.wg_per_cu, cap = cdiv(nt, tiles_per_round);   // a workgroup should see at least ~16 tiles
+        auto share = [&](double w) { int64_t g = (int64_t)(total_wg * w / wsum); return (int)(g > cap ? cap : (g < 1 ? 1 : g)); };
+        p.slices.g_full = share(1.0);
+        p.slices.g_ntail = p.n_tail ? share(w_half) : 0;
+        p.slices.g_ktail = p.k_tail ? share(w_half) : 0;
+        p.slices.g_both = p.n_tail && p.k_tail ? share(w_both) : 0;
+        p.grid_x = (int64_t)nkf * ncf * p.slices.g_full + (int64_t)nkf * p.slices.g_ntail + (int64_t)ncf * p.slices.g_ktail +
+                   p.slices.g_both;
+    }
+    // progressive staging of the forward slice (PROG in the kernel): SCN_TS_PROG = offsets staged before the barrier (4 / 8 / 12;
+    // 0 = the classic staging)
+    p.prog_g0 = 0;
+    if (p.fullk && !p.wt && p.vecn && !p.part && !p.tail && !p.split4 && n_off == 27 && cout % TS_CT == 0) {
+        const scn::SwitchVal pg = scn::sw(scn::SW_TS_PROG);
+        p.prog_g0 = pg.set ? (int)pg.i : 0;
+        if (p.prog_g0 < 0 || p.prog_g0 > 12) p.prog_g0 = 0;
+        p.prog_g0 = (p.prog_g0 + 3) / 4 * 4;
+    }
+    p.finish_v4 = ts_finish_v4(cout, epi_bits);
+    return p;
+}
+
+extern "C" int scn_conv_tiles_plan_describe(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags,
+                                            int with_arrival, int xw_ptr_bits, int epilogue_ptr_bits, int64_t out[16]) {
+    SCN_REQUIRE(out != nullptr);
+    SCN_REQUIRE(n_off >= 1 && n_off <= 27 && n_out >= 0 && n_in >= 0 && cin >= 1 && cout >= 1);
+    const unsigned xw = (unsigned)xw_ptr_bits & 15u, w = ((unsigned)xw_ptr_bits >> 4) & 15u;
+    SCN_REQUIRE(xw_ptr_bits >= 0 && xw_ptr_bits < 256 && epilogue_ptr_bits >= 0 && epilogue_ptr_bits < 16);
+    SCN_REQUIRE((xw & 3) == 0 && (w & ~xw) == 0 && (epilogue_ptr_bits & 3) == 0);
+    memset(out, 0, 16 * sizeof(int64_t));
+    if (n_out == 0) return SCN_OK;
+    const TsPlan p = ts_plan(n_in, cin, n_off, n_out, cout, flags, with_arrival != 0, xw, w, (unsigned)epilogue_ptr_bits);
+    int64_t g_max = p.n_tg;
+    if (p.tail) {
+        g_max = p.slices.g_full;
+        if (p.slices.g_ntail > g_max) g_max = p.slices.g_ntail;
+        if (p.slices.g_ktail > g_max) g_max = p.slices.g_ktail;
+        if (p.slices.g_both > g_max) g_max = p.slices.g_both;
+    }
+    const int64_t v[16] = {p.stream, p.fullk, p.wt, p.vecn, p.part, p.tail, p.k_tail, p.n_tail, p.fused, p.split4, p.prog_g0,
+                           p.n_kc, p.n_chunks, g_max, p.grid_x, p.finish_v4};
+    memcpy(out, v, sizeof(v));
+    return SCN_OK;
 }
 
 extern "C" int scn_conv_tiles(const float* X, int64_t n_in, int cin, const int32_t* tstab, const uint32_t* tile_mask,
@@ -743,12 +868,13 @@ extern "C" int scn_conv_tiles(const float* X, int64_t n_in, int cin, const int32
     SCN_REQUIRE(n_off >= 1 && n_off <= 27 && n_out >= 0 && n_in >= 0 && cin >= 1 && cout >= 1);
     if (n_out == 0) return SCN_OK;
     SCN_REQUIRE(X && tstab && tile_mask && perm && tile_order && W && Y);
-    const int64_t nt = cdiv(n_out, TS_T);
-    const int n_chunks = (int)cdiv(cout, TS_CT);
-    const int n_kc = (int)cdiv(cin, TS_KC);
     SCN_REQUIRE(scratch);
-    if (n_kc > 1 && arrival != nullptr) {        // (the fused mode's callers; the two-launch cross-check keeps k_conv_ts)
-        // layers that would split K over workgroups at Cin = 64 / 128: the offset-outer weight-streaming kernel (scn_conv_tss.hip)
+    float* slabs = (float*)((char*)scratch + ts_counter_bytes(cin, cout));
+    const TsPlan pl = ts_plan(n_in, cin, n_off, n_out, cout, flags, arrival != nullptr, (unsigned)((uintptr_t)X & 15),
+                              (unsigned)((uintptr_t)W & 15),
+                              (unsigned)(((uintptr_t)slabs | (uintptr_t)Y | (uintptr_t)bias | (uintptr_t)residual |
+                                          (uintptr_t)relu_mask) & 15));
+    if (pl.stream) {
         bool launched = false;
         const int rc = scn::conv_tiles_stream(X, n_in, cin, tstab, tile_mask, perm, n_off, n_out, W, bias, residual, relu_mask,
                                               Y, cout, flags, S(stream), &launched);
@@ -759,72 +885,17 @@ extern "C" int scn_conv_tiles(const float* X, int64_t n_in, int cin, const int32
             return SCN_OK;
         }
     }
-    float* slabs = (float*)((char*)scratch + ts_counter_bytes(cin, cout));
-    // the in-launch K reduction needs the caller's zeroed arrival counters and 32-bit slab offsets; without them (or when
-    // the caller asks for the two-launch form) the partial sums go to row-major slabs and k_conv_ts_sum adds them
-    const bool fused = n_kc > 1 && arrival != nullptr && !(flags & SCN_F_SPLIT_SUM) &&
-                       nt * n_chunks * n_kc * (int64_t)(TS_T * TS_CT * 4) < (1ll << 31);
+    const int64_t nt = pl.nt;
+    const int n_chunks = pl.n_chunks, n_kc = pl.n_kc;
+    const bool fused = pl.fused, wt = pl.wt, vecn = pl.vecn, fullk = pl.fullk, part = pl.part, tail = pl.tail, split4 = pl.split4;
     int* counters = (int*)arrival;
-    const bool wt = flags & SCN_F_W_TRANSPOSED;
-    const bool vec = (cin % 4 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)W & 15) == 0);
-    const bool vecn = (cout % 4 == 0) && (((uintptr_t)W & 15) == 0);
-    // the fast path addresses X through a raw buffer descriptor: 32-bit byte offsets, 24-bit row indices
-    const bool fullk = vec && n_in < (1ll << 23) && n_in * cin * 4 < (1ll << 32) - (1ll << 24) &&
-                       n_out < (1ll << 23) && n_out * cout * 4 < (1ll << 32) - (1ll << 24);
-    // Latency-bound levels (scn_conv_ts_small.inc): with fewer (tile, slice) pairs than half the chip's waves a launch is ONE
-    // tile's serial chain of up to 27 dependent gathers, so four waves share a tile.  Decided from the tile and slice counts
-    // alone: every form of a layer (fused / two-launch K reduction, TAIL / padded slices) takes the same loop.
-    // SCN_TS_SPLIT=0: never (A/B; the cross-check in the tests -- the two loops associate an element's sum differently).
-    const scn::SwitchVal sp_sw = scn::sw(scn::SW_TS_SPLIT);            // (scn_debug_set: the tests switch it inside one process)
-    const int64_t sp_max = scn::sw(scn::SW_TS_SPLIT_MAX).set ? scn::sw(scn::SW_TS_SPLIT_MAX).i : 2048;   // (developer switch)
-    const bool split4 = fullk && nt * n_chunks * n_kc <= sp_max && !(sp_sw.set && sp_sw.i == 0);
-    const int tiles_per_round = split4 ? TS_NW / 4 : TS_NW;
-    const size_t lds = (size_t)n_off * TS_KC * TS_CT * sizeof(float) + 16 + (split4 ? (size_t)2 * (TS_NW / 4) * 3 * 2 * 64 * 16 : 0);   // two buffers of partial tiles
-    int wg_per_cu = (int)((160 * 1024) / lds);
-    if (wg_per_cu > 2) wg_per_cu = 2;                  // 16 waves each: 2 workgroups fill a CU
-    if (wg_per_cu < 1) wg_per_cu = 1;
-    // grid sized to the chip: workgroups per (column chunk, K-chunk) slice; a workgroup should see at least ~16 tiles
-    int64_t n_tg = ((int64_t)scn::cu_budget() * wg_per_cu) / ((int64_t)n_chunks * n_kc);
-    if (n_tg > cdiv(nt, tiles_per_round)) n_tg = cdiv(nt, tiles_per_round);
-    if (n_tg < 1) n_tg = 1;
-    const bool part = cin % TS_KC != 0;
-    // TAIL: a dead K half or a dead column block exists (the reference's 48 / 80 / 112-channel layers): those MFMAs are
-    // skipped and the slices get workgroups in proportion to their cost.  Estimated cost of a tile step relative to a
-    // full 16-MFMA step: one dead half 0.70, both 0.50 (the per-step fixed work -- index load, gathers, ~15 VALU -- does
-    // not shrink with the MFMAs; calibrated with tools/ablate_conv_tail.py on the 48 / 80 / 112-channel layers:
-    // profiles/r3_ablate_conv_tail.txt).
-    const bool k_tail = cin % TS_KC != 0 && cin % TS_KC <= 16, n_tail = cout % TS_CT != 0 && cout % TS_CT <= 16;
-    const bool tail = fullk && (k_tail || n_tail) && !scn::sw(scn::SW_TS_NO_TAIL).set;
-    TsSlices slices = {0, 0, 0, 0};
-    int64_t grid_x = n_tg * n_chunks * n_kc;
-    if (tail) {
-        const double w_half = scn::sw(scn::SW_TS_W_HALF).set ? scn::sw(scn::SW_TS_W_HALF).f : 0.70;
-        const double w_both = scn::sw(scn::SW_TS_W_BOTH).set ? scn::sw(scn::SW_TS_W_BOTH).f : 0.50;
-        const int ncf = n_chunks - (n_tail ? 1 : 0), nkf = n_kc - (k_tail ? 1 : 0);
-        const double wsum = (double)nkf * ncf + (n_tail ? nkf * w_half : 0.0) + (k_tail ? ncf * w_half : 0.0) +
-                            (n_tail && k_tail ? w_both : 0.0);
-        const int64_t total_wg = (int64_t)scn::cu_budget() * wg_per_cu, cap = cdiv(nt, tiles_per_round);   // a workgroup should see at least ~16 tiles
-        auto share = [&](double w) { int64_t g = (int64_t)(total_wg * w / wsum); return (int)(g > cap ? cap : (g < 1 ? 1 : g)); };
-        slices.g_full = share(1.0);
-        slices.g_ntail = n_tail ? share(w_half) : 0;
-        slices.g_ktail = k_tail ? share(w_half) : 0;
-        slices.g_both = n_tail && k_tail ? share(w_both) : 0;
-        grid_x = (int64_t)nkf * ncf * slices.g_full + (int64_t)nkf * slices.g_ntail + (int64_t)ncf * slices.g_ktail + slices.g_both;
-    }
-    // progressive staging of the forward slice (PROG in the kernel): SCN_TS_PROG = offsets staged before the barrier (4 / 8 / 12;
-    // 0 = the classic staging)
-    int prog_g0 = 0;
-    if (fullk && !wt && vecn && !part && !tail && !split4 && n_off == 27 && cout % TS_CT == 0) {
-        const scn::SwitchVal pg = scn::sw(scn::SW_TS_PROG);
-        prog_g0 = pg.set ? (int)pg.i : 0;
-        if (prog_g0 < 0 || prog_g0 > 12) prog_g0 = 0;
-        prog_g0 = (prog_g0 + 3) / 4 * 4;
-    }
-    const int kflags = (flags & 0xFFFFFF) | (prog_g0 << 24);
+    const size_t lds = pl.lds;
+    const TsSlices slices = pl.slices;
+    const int kflags = (flags & 0xFFFFFF) | (pl.prog_g0 << 24);
     g_ts_paths[fullk ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
     if (n_kc > 1) g_ts_paths[fused ? 2 : 3].fetch_add(1, std::memory_order_relaxed);
     if (split4) g_ts_split.fetch_add(1, std::memory_order_relaxed);
-    dim3 grid((unsigned)grid_x);
+    dim3 grid((unsigned)pl.grid_x);
     hipStream_t st = S(stream);
 #define LAUNCH_TS_F(T, V, VN, FK, PT, FU, TL, SP)                                                                   \
     do {                                                                                                            \
@@ -1009,8 +1080,8 @@ extern "C" int scn_conv_tiles_finish(int cin, int64_t n_out, const float* bias, 
     SCN_REQUIRE(Y && scratch);
     float* slabs = (float*)((char*)scratch + ts_counter_bytes(cin, cout));
     hipStream_t st = S(stream);
-    const bool v4 = cout % 4 == 0 && ((((uintptr_t)slabs | (uintptr_t)Y | (uintptr_t)bias | (uintptr_t)residual |
-                                        (uintptr_t)relu_mask) & 15) == 0);
+    const bool v4 = ts_finish_v4(cout, (unsigned)(((uintptr_t)slabs | (uintptr_t)Y | (uintptr_t)bias | (uintptr_t)residual |
+                                                   (uintptr_t)relu_mask) & 15));
     const int rl = (flags & SCN_F_RESIDUAL_LAST) ? 1 : 0;
     if (v4)
         hipLaunchKernelGGL(k_conv_ts_sum<4>, dim3(scn::ew_grid(n_out * cout / 4, 256)), dim3(256), 0, st,

@@ -258,22 +258,29 @@ __global__ __launch_bounds__(NW * 64) void k_conv_tss(
 }  // namespace
 
 namespace scn {
+// Whether conv_tiles_stream takes a call (host only; xw_bits: the low 4 bits of X | W) -- also what the path report of
+// scn_conv_tiles (scn_conv_tiles_plan_describe) says.
+// OFF by default: measured SLOWER than k_conv_ts on the cfg-2 scene (profiles/r4_tss_fp32_streaming_experiment.txt:
+// 86.5 / 114.4 us per launch at levels 1 / 2 with 4-wave workgroups, 119 / 144 with 16 / 8, against 69.4 / 65.9) -- the
+// lockstep over the union of a batch's offset masks idles the waves whose tile lacks an offset, and the mask-sorted
+// tiles of a surface scene differ too much for any batch size to hide that.  SCN_TS_STREAM=1 runs it (tests, A/B).
+bool conv_tiles_stream_eligible(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags, unsigned xw_bits) {
+    if (scn::sw(scn::SW_TS_STREAM).i != 1) return false;            // (scn_debug_set: the tests switch it inside one process)
+    const int ks = cin / 32;
+    return cin % 32 == 0 && (ks == 2 || ks == 4) && cout % SS_CT == 0 && (n_off == 27 || n_off == 8) &&
+           !(flags & SCN_F_SPLIT_SUM) && (xw_bits & 15) == 0 &&
+           n_in < (1ll << 23) && n_in * cin * 4 < (1ll << 32) - (1ll << 24) && n_out < (1ll << 23) &&
+           n_out * cout * 4 < (1ll << 32) - (1ll << 24) && (int64_t)n_off * cin * cout * 4 < (1ll << 31);
+}
+
 // *launched = true: the layer ran here; false: not eligible (the caller runs k_conv_ts).  -> status
 int conv_tiles_stream(const float* X, int64_t n_in, int cin, const int32_t* tstab, const uint32_t* tile_mask,
                       const int32_t* perm, int n_off, int64_t n_out, const float* W, const float* bias, const float* residual,
                       const float* relu_mask, float* Y, int cout, int flags, hipStream_t st, bool* launched) {
     *launched = false;
-    // OFF by default: measured SLOWER than k_conv_ts on the cfg-2 scene (profiles/r4_tss_fp32_streaming_experiment.txt:
-    // 86.5 / 114.4 us per launch at levels 1 / 2 with 4-wave workgroups, 119 / 144 with 16 / 8, against 69.4 / 65.9) -- the
-    // lockstep over the union of a batch's offset masks idles the waves whose tile lacks an offset, and the mask-sorted
-    // tiles of a surface scene differ too much for any batch size to hide that.  SCN_TS_STREAM=1 runs it (tests, A/B).
-    if (scn::sw(scn::SW_TS_STREAM).i != 1) return SCN_OK;           // (scn_debug_set: the tests switch it inside one process)
+    if (!conv_tiles_stream_eligible(n_in, cin, n_off, n_out, cout, flags, (unsigned)(((uintptr_t)X | (uintptr_t)W) & 15)))
+        return SCN_OK;
     const int ks = cin / 32;
-    const bool ok = cin % 32 == 0 && (ks == 2 || ks == 4) && cout % SS_CT == 0 && (n_off == 27 || n_off == 8) &&
-                    !(flags & SCN_F_SPLIT_SUM) && (((uintptr_t)X | (uintptr_t)W) & 15) == 0 &&
-                    n_in < (1ll << 23) && n_in * cin * 4 < (1ll << 32) - (1ll << 24) && n_out < (1ll << 23) &&
-                    n_out * cout * 4 < (1ll << 32) - (1ll << 24) && (int64_t)n_off * cin * cout * 4 < (1ll << 31);
-    if (!ok) return SCN_OK;
     const int64_t nt = cdiv(n_out, SS_T);
     const int n_chunks = cout / SS_CT;
     const bool wt = flags & SCN_F_W_TRANSPOSED;
