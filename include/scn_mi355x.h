@@ -81,7 +81,8 @@ extern "C" {
  *      additive within 5: + scn_wgrad_plan_describe (169 entry points);
  *      additive within 5: + scn_roialign_pool_fwd / _bwd, their _bf16 forms, scn_box_flatten_fwd / _bwd (175 entry points);
  *      additive within 5: + scn_loss_combine / scn_loss_combine_bwd (177 entry points);
- *      additive within 5: + scn_conv_tiles_plan_describe (178 entry points) */
+ *      additive within 5: + scn_conv_tiles_plan_describe (178 entry points);
+ *      additive within 5: + the executor op SCN_OP_ADD_RELU, no new entry point (178 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -762,7 +763,11 @@ enum {
     SCN_OP_ADD = 12,         /* y = x + x1 (scn_add / scn_add_bf16): the two gradient paths of a skip connection             */
     SCN_OP_CAST = 13,        /* storage cast: SCN_XF_BF16 set = fp32 -> bf16, else bf16 -> fp32                               */
     SCN_OP_RELU = 14,        /* y = max(x, 0) (scn_relu_fwd / _bf16), y may be x: the closing ReLU of a main-path residual unit */
-    SCN_OP_RELU_BWD = 15     /* y = x1 where m > 0, else 0 (scn_relu_bwd / _bf16): m = the slab the ReLU read OR wrote         */
+    SCN_OP_RELU_BWD = 15,    /* y = x1 where m > 0, else 0 (scn_relu_bwd / _bf16): m = the slab the ReLU read OR wrote         */
+    SCN_OP_ADD_RELU = 16     /* y = x + max(x1, 0) over rows * cin elements in ONE pass, x1 left as it is, y may be x: the end of a
+                              * post-activation residual unit (module_factory.py:163-171, relu_first=False).  The only op that is not
+                              * an entry point of its own; scn_relu_fwd's expression, scn_add's operand order and (bf16) one
+                              * rounding: bit-equal to SCN_OP_RELU (x1 -> r) followed by SCN_OP_ADD (x, r -> y)                    */
 };
 #define SCN_XF_BF16 (1 << 16)        /* op flag: the op's feature slabs are bf16-stored                                      */
 #define SCN_XF_COARSE_ROWS (1 << 17) /* op flag (GEMM_IDENT / WGRAD_IDENT / COLSUM / ADD / CAST / RELU / RELU_BWD): rows = n_coarse of `level` */

@@ -84,6 +84,10 @@ inline int ew_grid(int64_t work_items, int block) {
     return (int)g;
 }
 
+// y = x + max(x1, 0) in one pass (scn_elem.hip / scn_elem_bf16.hip): the step executor's SCN_OP_ADD_RELU.  y may be x.
+int add_relu(const float* X, const float* X1, int64_t count, float* Y, scn_stream_t stream);
+int add_relu_bf16(const uint16_t* X, const uint16_t* X1, int64_t count, uint16_t* Y, scn_stream_t stream);
+
 }  // namespace scn
 
 // ---- device-side key packing / hashing (shared by index kernels) ----

@@ -63,6 +63,37 @@ extern "C" int scn_add(const float* A, const float* B, int64_t count, float* Y, 
     return ew_launch<2>(A, B, count, Y, stream);
 }
 
+// y = x + max(t, 0): the end of a post-activation residual unit in one pass (3 slab passes where scn_relu_fwd + scn_add move 5).
+// k_ew<0>'s ReLU expression and k_ew<2>'s operand order, so the result has the bits of that pair.  y may be x (no __restrict__
+// on the two): every element is read once, by the thread that writes it.
+__global__ void k_add_relu(const float* x, const float* __restrict__ t, long long count, float* y, int vec) {
+    const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long done = 0;
+    if (vec) {
+        const long long n4 = count >> 2;
+        for (long long i = tid; i < n4; i += stride) {
+            const float4 u = ((const float4*)x)[i], w = ((const float4*)t)[i];
+            ((float4*)y)[i] = make_float4(u.x + fmaxf(w.x, 0.f), u.y + fmaxf(w.y, 0.f), u.z + fmaxf(w.z, 0.f),
+                                          u.w + fmaxf(w.w, 0.f));
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + tid; i < count; i += stride) y[i] = x[i] + fmaxf(t[i], 0.f);
+}
+
+// (library-internal, scn_common.h: reached through the step executor's SCN_OP_ADD_RELU, not an entry point of the C ABI)
+int scn::add_relu(const float* X, const float* X1, int64_t count, float* Y, scn_stream_t stream) {
+    SCN_REQUIRE(count >= 0);
+    if (count == 0) return SCN_OK;
+    SCN_REQUIRE(X && X1 && Y);
+    const int vec = (((uintptr_t)X | (uintptr_t)X1 | (uintptr_t)Y) & 15) == 0;
+    hipLaunchKernelGGL(k_add_relu, dim3(scn::ew_grid(cdiv(count, 4), 256)), dim3(256), 0, S(stream), X, X1, (long long)count, Y,
+                       vec);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // row gathers / scatters.  One thread per (row, 4-channel group) when c % 4 == 0, else per element.
 // ------------------------------------------------------------------------------------------------

@@ -100,6 +100,28 @@ static int relu_b_launch(const uint16_t* a, const uint16_t* b, int64_t count, ui
     return SCN_OK;
 }
 
+// ---- x + max(t, 0) on stored slabs: the end of a post-activation residual unit ------------------------------------------
+// relu_b's expression on the widened branch value, k_add_b's sum and single rounding: the bits of scn_relu_fwd_bf16 followed by
+// scn_add_bf16 (the ReLU's result is a bf16 value, so the pair rounds once as well).  y may be x.
+__device__ __forceinline__ us add_relu_b(us x, us t) { return bn(bw(x) + fmaxf(bw(t), 0.f)); }
+__device__ __forceinline__ unsigned add_relu2_b(unsigned x, unsigned t) {
+    return (unsigned)add_relu_b((us)(x & 0xffffu), (us)(t & 0xffffu)) | ((unsigned)add_relu_b((us)(x >> 16), (us)(t >> 16)) << 16);
+}
+
+__global__ void k_add_relu_b(const us* x, const us* __restrict__ t, long long count, us* y, int vec) {
+    const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    long long done = 0;
+    if (vec) {
+        const long long n8 = count >> 3;
+        for (long long i = tid; i < n8; i += stride) {
+            const uint4 u = ((const uint4*)x)[i], w = ((const uint4*)t)[i];
+            ((uint4*)y)[i] = make_uint4(add_relu2_b(u.x, w.x), add_relu2_b(u.y, w.y), add_relu2_b(u.z, w.z), add_relu2_b(u.w, w.w));
+        }
+        done = n8 << 3;
+    }
+    for (long long i = done + tid; i < count; i += stride) y[i] = add_relu_b(x[i], t[i]);
+}
+
 // ---- row gather (OutputLayer, ROI feature gather): a byte copy of 2c-byte rows ------------------------------------
 __global__ void k_gather_rows_b(const us* __restrict__ X, const int* __restrict__ rows, long long m, int c,
                                 us* __restrict__ Y, int vec) {
@@ -212,6 +234,17 @@ extern "C" int scn_add_bf16(const uint16_t* A, const uint16_t* B, int64_t count,
     SCN_REQUIRE(A && B && Y);
     hipLaunchKernelGGL(k_add_b, dim3(scn::ew_grid(count, 256)), dim3(256), 0, S(stream), (const us*)A, (const us*)B,
                        (long long)count, (us*)Y);
+    SCN_LAUNCH_CHECK();
+    return SCN_OK;
+}
+
+int scn::add_relu_bf16(const uint16_t* X, const uint16_t* X1, int64_t count, uint16_t* Y, scn_stream_t stream) {
+    SCN_REQUIRE(count >= 0);
+    if (count == 0) return SCN_OK;
+    SCN_REQUIRE(X && X1 && Y);
+    const int vec = (((uintptr_t)X | (uintptr_t)X1 | (uintptr_t)Y) & 15) == 0;
+    hipLaunchKernelGGL(k_add_relu_b, dim3(scn::ew_grid(cdiv(count, 8), 256)), dim3(256), 0, S(stream), (const us*)X,
+                       (const us*)X1, (long long)count, (us*)Y, vec);
     SCN_LAUNCH_CHECK();
     return SCN_OK;
 }

@@ -191,6 +191,11 @@ int run_op(const Ctx& c0, const scn_exec_op& o, void* own_scratch = nullptr) {
         if (h) return scn_relu_bwd_bf16(B<u16>(c, o.m), B<u16>(c, o.x1), count, B<u16>(c, o.y), st);
         return scn_relu_bwd(B<float>(c, o.m), B<float>(c, o.x1), count, B<float>(c, o.y), st);
     }
+    case SCN_OP_ADD_RELU: {          // y = x + max(x1, 0): x1 (the branch) stays for the backward mask
+        const int64_t count = rows_of(o, L) * o.cin;
+        if (h) return scn::add_relu_bf16(B<u16>(c, o.x), B<u16>(c, o.x1), count, B<u16>(c, o.y), st);
+        return scn::add_relu(B<float>(c, o.x), B<float>(c, o.x1), count, B<float>(c, o.y), st);
+    }
     default:
         return scn::fail(SCN_EINVAL, "scn_exec_run: unknown op %s%lld", "", o.op);
     }

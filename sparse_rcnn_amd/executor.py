@@ -12,7 +12,9 @@ One node per LEVEL rather than per network: the parameter gradients of a level l
 ends, so the bucketed gradient all-reduce of dp.py still overlaps with the rest of backward, skip connections stay ordinary
 autograd edges, and the encoder outputs (`SparseUNet.interims`, the RPN's inputs in the reference) stay differentiable.
 
-Residual units: the plain pre-activation unit and the reference's bottleneck / main-path-ReLU forms (`_unit_blocks`).
+Units: the plain pre-activation residual unit, the reference's bottleneck / main-path-ReLU forms, its post-activation units
+(relu_first=False) and its plain convolution blocks (use_residuals=False) (`_unit_blocks`); input stages with the ReLU in front
+of the layer, behind it, or dropped (`_stage_relus`).
 
 Not covered (the layer-by-layer path runs instead): batch norm, `bf16_blocks=True` (casts around every run of units),
 channel plans the two-source NetworkInNetwork kernel does not take, empty levels, and any step in which
@@ -40,7 +42,7 @@ i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
 
 OP_GEMM_IDENT, OP_CONV_SUBM, OP_CONV_CHILD, OP_RULES_CHILD, OP_ROWS2 = 1, 2, 3, 4, 5
 OP_WGRAD_SUBM, OP_WGRAD2_SUBM, OP_WGRAD_DOWN, OP_WGRAD_UP, OP_WGRAD_IDENT, OP_COLSUM, OP_ADD, OP_CAST = 6, 7, 8, 9, 10, 11, 12, 13
-OP_RELU, OP_RELU_BWD = 14, 15
+OP_RELU, OP_RELU_BWD, OP_ADD_RELU = 14, 15, 16
 XF_BF16, XF_COARSE_ROWS = 1 << 16, 1 << 17
 BACK = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
 
@@ -249,16 +251,32 @@ class Stage:
     # an SCN_OP_ADD -- layer by layer autograd adds them -- because the row GEMM has no "residual after the mask" epilogue and
     # a bf16 slab must be rounded before the add to give autograd's bits.  The closing ReLU of a main-path unit is one
     # SCN_OP_RELU in place on the unit's result; its backward masks by that result (y > 0 exactly where the sum was).
+    #
+    # Post-activation units (relu_first=False, "post" / "post_bottleneck"): y = x + act(t), t the branch's last convolution.  No
+    # activation on the way in, no residual in the last convolution's epilogue; ONE SCN_OP_ADD_RELU ends the unit and leaves t
+    # as it is, which is the mask of the backward's SCN_OP_RELU_BWD.  The skip's gradient is dy itself, the branch's is masked.
+    # Plain blocks (use_residuals=False): "plain_pre" = K(ReLU(x)), the ReLU in the gather; "plain_post" = ReLU(K(x)), the ReLU
+    # one in-place SCN_OP_RELU on the block's result, its backward masked by that result.
     def _form_fwd(self, level, c, x, y, blk):
         hb, relu = self.hb, L.F_RELU_IN | self.hb
         form, main = blk[0], blk[0] in ("main", "both")
-        first = hb if main else relu                        # main_path_relu: no activation on the way in
-        if form == "main":
+        post = form in ("post", "post_bottleneck")
+        if form in ("plain_pre", "plain_post"):
+            m1 = self.mod(blk[1], c)
+            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=x, y=y, w=self.weight(m1, c, c, 27, 0, True), b=self.param("b", m1),
+                    flags=relu if form == "plain_pre" else hb)
+            if form == "plain_post":
+                self.op(self.fwd, OP_RELU, level, c, 0, x=y, y=y, flags=hb)
+            return (form, x, y, m1)
+        first = hb if (main or post) else relu              # main_path_relu / post-activation: no activation on the way in
+        t = self.buf(level, c) if post else y               # post-activation: the branch's result, kept for the backward mask
+        r = -1 if post else x
+        if form in ("main", "post"):
             _, c1, c2 = blk
             m1, m2 = self.mod(c1, c), self.mod(c2, c)
             y1 = self.buf(level, c)
             self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=x, y=y1, w=self.weight(m1, c, c, 27, 0, True), b=self.param("b", m1), flags=first)
-            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=y1, y=y, r=x, w=self.weight(m2, c, c, 27, 0, True), b=self.param("b", m2), flags=relu)
+            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=y1, y=t, r=r, w=self.weight(m2, c, c, 27, 0, True), b=self.param("b", m2), flags=relu)
             sv = (form, x, y, y1, m1, m2)
         else:
             _, n1, kk, n2 = blk
@@ -267,28 +285,49 @@ class Stage:
             a, b = self.buf(level, ci), self.buf(level, ci)
             self.op(self.fwd, OP_GEMM_IDENT, level, c, ci, x=x, y=a, w=self.param("w", m1), b=self.param("b", m1), flags=first)
             self.op(self.fwd, OP_CONV_SUBM, level, ci, ci, x=a, y=b, w=self.weight(mk, ci, ci, 27, 0, True), b=self.param("b", mk), flags=relu)
-            self.op(self.fwd, OP_GEMM_IDENT, level, ci, c, x=b, y=y, r=x, w=self.param("w", m2), b=self.param("b", m2), flags=relu)
+            self.op(self.fwd, OP_GEMM_IDENT, level, ci, c, x=b, y=t, r=r, w=self.param("w", m2), b=self.param("b", m2), flags=relu)
             sv = (form, x, y, a, b, ci, m1, mk, m2)
         if main:
             self.op(self.fwd, OP_RELU, level, c, 0, x=y, y=y, flags=hb)
+        if post:
+            self.op(self.fwd, OP_ADD_RELU, level, c, 0, x=x, x1=t, y=y, flags=hb)
+            sv = sv + (t,)
         return sv
 
     def _form_bwd(self, level, c, g, dx, sv):
         hb, relu = self.hb, L.F_RELU_IN | self.hb
         form, x, y = sv[:3]
+        if form in ("plain_pre", "plain_post"):
+            m1 = sv[3]
+            if form == "plain_post":
+                gs = self.buf(level, c, kind="b")
+                self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=y, x1=g, y=gs, flags=hb)
+                g = gs
+            pre = form == "plain_pre"
+            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dx, m=x if pre else -1, w=self.weight(m1, c, c, 27, BACK, True),
+                    flags=BACK | hb)
+            self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=x, y=g, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")),
+                    flags=relu if pre else hb)
+            return
         main = form in ("main", "both")
-        first = hb if main else relu
+        post = form in ("post", "post_bottleneck")
+        first = hb if (main or post) else relu
+        g_skip = g                                          # what the skip hands back to x
         if main:
             gs = self.buf(level, c, kind="b")
             self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=y, x1=g, y=gs, flags=hb)
-            g = gs
+            g = g_skip = gs
+        if post:                                            # only the branch passes the closing activation
+            gs = self.buf(level, c, kind="b")
+            self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=sv[-1], x1=g, y=gs, flags=hb)
+            g, sv = gs, sv[:-1]
         t = self.buf(level, c, kind="b")                    # the branch's gradient of x, before the skip's is added
-        if form == "main":
+        if form in ("main", "post"):
             y1, m1, m2 = sv[3:]
             dy1 = self.buf(level, c, kind="b")
             self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dy1, m=y1, w=self.weight(m2, c, c, 27, BACK, True), flags=BACK | hb)
             self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=dy1, y=t, w=self.weight(m1, c, c, 27, BACK, True), flags=BACK | hb)
-            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=hb)
+            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g_skip, y=dx, flags=hb)
             self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=y1, y=g, w=self.gregion((m2, "w")), b=self.gregion((m2, "b")), flags=relu)
             self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=x, y=dy1, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
             return
@@ -296,8 +335,8 @@ class Stage:
         db, da = self.buf(level, ci, kind="b"), self.buf(level, ci, kind="b")
         self.op(self.bwd, OP_GEMM_IDENT, level, c, ci, x=g, y=db, m=b, w=self.param("w", m2), flags=BACK | hb)
         self.op(self.bwd, OP_CONV_SUBM, level, ci, ci, x=db, y=da, m=a, w=self.weight(mk, ci, ci, 27, BACK, True), flags=BACK | hb)
-        self.op(self.bwd, OP_GEMM_IDENT, level, ci, c, x=da, y=t, m=-1 if main else x, w=self.param("w", m1), flags=BACK | hb)
-        self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=hb)
+        self.op(self.bwd, OP_GEMM_IDENT, level, ci, c, x=da, y=t, m=-1 if (main or post) else x, w=self.param("w", m1), flags=BACK | hb)
+        self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g_skip, y=dx, flags=hb)
         self.op(self.bwd, OP_WGRAD_IDENT, level, ci, c, x=b, y=g, w=self.gregion((m2, "w")), b=self.gregion((m2, "b")), flags=relu)
         self.op(self.bwd, OP_WGRAD_SUBM, level, ci, ci, x=a, y=db, w=self.gregion((mk, "w")), b=self.gregion((mk, "b")), flags=relu)
         self.op(self.bwd, OP_WGRAD_IDENT, level, c, ci, x=x, y=da, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
@@ -363,6 +402,18 @@ def _lean_slots(self):
 Stage._lean_slots = _lean_slots
 
 
+def run_add_relu(x_ptr, x1_ptr, y_ptr, rows, c, bf16, scratch):
+    """y = x + max(x1, 0) over [rows, c] slabs as a plan of ONE SCN_OP_ADD_RELU through scn_exec_run: the fused end of a
+    post-activation unit has no entry point of its own.  Raw addresses; scratch: a device tensor of at least 256 bytes (the
+    executor asks for one whatever the ops are).  For the kernel tests and tools/post_act_bench.py."""
+    lib = L.lib()
+    levels = (ExecLevel * 1)()
+    levels[0].n = int(rows)
+    ops = (ExecOp * 1)(ExecOp(OP_ADD_RELU, XF_BF16 if bf16 else 0, 0, int(c), 0, 0, 2, -1, -1, 1, -1, 0, -1, -1, 0, 0))
+    table = (vp * 3)(x_ptr, x1_ptr, y_ptr)
+    L.check(lib.scn_exec_run(ops, 1, levels, 1, table, None, None, scratch.data_ptr(), scratch.numel(), None, L.stream()))
+
+
 def _lean_layout(stage, ns):
     """-> (offset per forward workspace buffer, total bytes) of the forward-only plan."""
     base, tot = {}, 0
@@ -397,6 +448,19 @@ def _unit_blocks(unit_seq):
     ("bottleneck" | "both", N1, K, N2) and ("main", K1, K2) -- "both" and "main" close with a ReLU (main_path_relu).  None when
     a block is none of them (batch norm, a layer without bias, channel padding, groups)."""
     out = []
+    mods = list(unit_seq._modules.values()) if isinstance(unit_seq, torch.nn.Sequential) else list(unit_seq)
+    if mods and len(mods) % 2 == 0 and all(type(m) in (M.ReLU, M.SubmanifoldConvolution) for m in mods):
+        # use_residuals=False: a flat [ReLU, K] * n | [K, ReLU] * n (module_factory.py:186-218)
+        pre = type(mods[0]) is M.ReLU
+        convs, relus = (mods[1::2], mods[0::2]) if pre else (mods[0::2], mods[1::2])
+        if any(type(m) is not M.ReLU for m in relus):
+            return None
+        for m in convs:
+            if (type(m) is not M.SubmanifoldConvolution or m.filter_size != 3 or m.bias is None or m.groups != 1 or m.pad_out_to
+                    or m.nIn != m.nOut):
+                return None
+            out.append(("plain_pre" if pre else "plain_post", m))
+        return out
     for block in unit_seq:
         plain = _plain_blocks([block])
         if plain is not None:
@@ -412,10 +476,16 @@ def _unit_blocks(unit_seq):
         if type(a) is not M.Identity or type(inner) is not M.Sequential:
             return None
         mods = list(inner._modules.values())
-        if not main:                                         # relu_first: the branch opens with the activation
-            if not mods or type(mods[0]) is not M.ReLU:
+        post = False
+        if not main:                                         # relu_first: the branch opens with the activation ...
+            if not mods:
                 return None
-            mods = mods[1:]
+            if type(mods[0]) is M.ReLU:
+                mods = mods[1:]
+            elif type(mods[-1]) is M.ReLU:                   # ... without it the activation closes the branch (post-activation)
+                mods, post = mods[:-1], True
+            else:
+                return None
         if len(mods) not in (3, 5) or any(type(m) is not M.ReLU for m in mods[1::2]):
             return None
         convs = mods[0::2]
@@ -424,28 +494,49 @@ def _unit_blocks(unit_seq):
         sizes = tuple(m.filter_size for m in convs)
         c = convs[0].nIn
         if sizes == (3, 3):
-            if not main or any((m.nIn, m.nOut) != (c, c) for m in convs):
+            if not (main or post) or any((m.nIn, m.nOut) != (c, c) for m in convs):
                 return None
-            out.append(("main", *convs))
+            out.append(("post" if post else "main", *convs))
         elif sizes == (1, 3, 1):
             ci = convs[0].nOut
             if (convs[1].nIn, convs[1].nOut, convs[2].nIn, convs[2].nOut) != (ci, ci, ci, c):
                 return None
-            out.append(("both" if main else "bottleneck", *convs))
+            out.append(("both" if main else ("post_bottleneck" if post else "bottleneck"), *convs))
         else:
             return None
     return out
+
+
+def _block_width(blk):
+    """Channels a unit of `_unit_blocks` takes and gives."""
+    return (blk[1] if isinstance(blk[0], str) else blk[0]).nIn
 
 
 def _phys(m):
     return int(getattr(m, "pad_out_to", None) or m.nOut)
 
 
-def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False, cast_last=False, in_bf16=False):
+def _stage_relus(stage):
+    """(a ReLU leads the layer, a ReLU follows it) of an input stage (module_factory.py:438-486): the conv-type layer itself or a
+    Sequential of just it -- (False, False) --, Sequential(ReLU, layer), Sequential(layer, ReLU).  None: anything else."""
+    if isinstance(stage, M._ConvBase):
+        return (False, False)
+    if type(stage) is not M.Sequential:
+        return None
+    kinds = tuple("r" if type(m) is M.ReLU else ("c" if isinstance(m, M._ConvBase) else "?") for m in stage._modules.values())
+    return {("c",): (False, False), ("r", "c"): (True, False), ("c", "r"): (False, True)}.get(kinds)
+
+
+def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False, cast_last=False, in_bf16=False,
+                          relus=(False, False)):
     """Encoder level: head (SubM 1^3 at level 0 | Convolution 2^3/2 from level-1) + residual units.
     level 0 in bf16 storage: the head runs in fp32 on the fp32 input and its result is cast (SparseUNet), or -- cast_first,
     the mask branch's input stage -- the input is cast first and the head runs on bf16 rows, or -- in_bf16 -- the input
-    slab is bf16-stored already (a SubM 1^3 stage behind a bf16 network in a module tree); cast_last: fp32 output."""
+    slab is bf16-stored already (a SubM 1^3 stage behind a bf16 network in a module tree); cast_last: fp32 output.
+    relus (`_stage_relus`): a ReLU in front of the head is fused into its gather; one behind it is an in-place SCN_OP_RELU on the
+    head's result, whose backward masks by that slab."""
+    lead, trail = relus
+    lead_fl = L.F_RELU_IN if lead else 0
     st = Stage(bf16, 1)
     in_bf16 = bool(bf16 and in_bf16 and level == 0)
     es_in = (2 if in_bf16 else 4) if (level == 0) else st.es
@@ -458,6 +549,8 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
     st.out_id = OUT
     if level == 0:
         if bf16 and (cast_first or in_bf16):
+            if lead or trail:
+                raise NotImplementedError("executor: a level-0 head on bf16 rows takes no input-stage ReLU")
             xin = IN
             if not in_bf16:
                 xin = st.buf(0, cin_phys)
@@ -467,7 +560,9 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
             x, head_in, head_hb = h, xin, XF_BF16
         else:
             h = st.buf(0, c, 4)
-            st.op(st.fwd, OP_GEMM_IDENT, 0, cin_phys, c, x=IN, y=h, w=st.param("w", mh), b=st.param("b", mh), flags=0)
+            st.op(st.fwd, OP_GEMM_IDENT, 0, cin_phys, c, x=IN, y=h, w=st.param("w", mh), b=st.param("b", mh), flags=lead_fl)
+            if trail:
+                st.op(st.fwd, OP_RELU, 0, c, 0, x=h, y=h, flags=0)
             x, head_in, head_hb = h, IN, 0
             if bf16:
                 x = st.buf(0, c)
@@ -475,7 +570,10 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
     else:
         x = st.buf(level, c)
         st.op(st.fwd, OP_CONV_CHILD, level - 1, cin_phys, c, x=IN, y=x, w=st.weight(mh, cin_phys, c, 8, 0, True),
-              b=st.param("b", mh), flags=st.hb)
+              b=st.param("b", mh), flags=lead_fl | st.hb)
+        h = x
+        if trail:
+            st.op(st.fwd, OP_RELU, level, c, 0, x=x, y=x, flags=st.hb)
     if bf16 and cast_last:
         last, saved = st.units_fwd(level, c, x, blocks)
         st.op(st.fwd, OP_CAST, level, c, 0, x=last, y=OUT, flags=0)
@@ -504,18 +602,30 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
             if bf16:
                 gf = st.buf(0, c, 4, "b")
                 st.op(st.bwd, OP_CAST, 0, c, 0, x=g, y=gf, flags=0)
-            st.op(st.bwd, OP_GEMM_IDENT, 0, c, cin_phys, x=gf, y=DIN, w=st.param("w", mh), flags=BACK)
-            st.op(st.bwd, OP_WGRAD_IDENT, 0, cin_phys, c, x=IN, y=gf, w=gw, b=gb, flags=0)
+            if trail:
+                gm = st.buf(0, c, 4, "b")
+                st.op(st.bwd, OP_RELU_BWD, 0, c, 0, m=h, x1=gf, y=gm, flags=0)
+                gf = gm
+            st.op(st.bwd, OP_GEMM_IDENT, 0, c, cin_phys, x=gf, y=DIN, m=IN if lead else -1, w=st.param("w", mh), flags=BACK)
+            st.op(st.bwd, OP_WGRAD_IDENT, 0, cin_phys, c, x=IN, y=gf, w=gw, b=gb, flags=lead_fl)
     else:
-        st.op(st.bwd, OP_RULES_CHILD, level - 1, c, cin_phys, x=g, y=DIN, w=st.param("w", mh), flags=L.F_W_TRANSPOSED | st.hb)
-        st.op(st.bwd, OP_WGRAD_DOWN, level - 1, cin_phys, c, x=IN, y=g, w=gw, flags=st.hb)
+        if trail:
+            gm = st.buf(level, c, kind="b")
+            st.op(st.bwd, OP_RELU_BWD, level, c, 0, m=h, x1=g, y=gm, flags=st.hb)
+            g = gm
+        st.op(st.bwd, OP_RULES_CHILD, level - 1, c, cin_phys, x=g, y=DIN, m=IN if lead else -1, w=st.param("w", mh),
+              flags=L.F_W_TRANSPOSED | st.hb)
+        st.op(st.bwd, OP_WGRAD_DOWN, level - 1, cin_phys, c, x=IN, y=g, w=gw, flags=lead_fl | st.hb)
         st.op(st.bwd, OP_COLSUM, level, c, 0, x=g, b=gb, flags=st.hb)
     return st.freeze()
 
 
-def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16):
+def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, False)):
     """Decoder level: ReLU -> Deconvolution 2^3/2 (coarse level+1 -> level) -> JoinTable([up, skip]) -> NetworkInNetwork ->
-    residual units.  Inputs: (coarse slab, skip slab)."""
+    residual units.  Inputs: (coarse slab, skip slab).  relus (`_stage_relus`): (True, False) is that form; (False, True) the
+    relu_first=False one, Deconvolution -> ReLU, the ReLU in place on the deconvolution's result."""
+    lead, trail = relus
+    lead_fl = L.F_RELU_IN if lead else 0
     st = Stage(bf16, 2)
     c = _phys(up)
     IN0 = st.buf(level + 1, c_coarse, None, "x")
@@ -526,7 +636,9 @@ def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16):
     mu, mn = st.mod(up, c_coarse), st.mod(nin, 2 * c)
     upb = st.buf(level, c)
     st.op(st.fwd, OP_RULES_CHILD, level, c_coarse, c, x=IN0, y=upb, w=st.param("w", mu), b=st.param("b", mu),
-          flags=L.F_RELU_IN | st.hb)
+          flags=lead_fl | st.hb)
+    if trail:
+        st.op(st.fwd, OP_RELU, level, c, 0, x=upb, y=upb, flags=st.hb)
     h = st.buf(level, c)
     st.op(st.fwd, OP_ROWS2, level, c, c, x=upb, x1=IN1, c1=c, y=h, w=st.param("w", mn), b=st.param("b", mn), flags=st.hb)
     last, saved = st.units_fwd(level, c, h, blocks, out_id=OUT)
@@ -542,10 +654,14 @@ def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16):
     gwn, gbn = st.gregion((mn, "w")), st.gregion((mn, "b"))
     st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=upb, y=g, w=gwn, b=gbn, aux=0, flags=st.hb)
     st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=IN1, y=g, w=gwn, b=-1, aux=c * c, flags=st.hb)
-    st.op(st.bwd, OP_CONV_CHILD, level, c, c_coarse, x=dup, y=DIN0, m=IN0,
+    if trail:
+        dm = st.buf(level, c, kind="b")
+        st.op(st.bwd, OP_RELU_BWD, level, c, 0, m=upb, x1=dup, y=dm, flags=st.hb)
+        dup = dm
+    st.op(st.bwd, OP_CONV_CHILD, level, c, c_coarse, x=dup, y=DIN0, m=IN0 if lead else -1,
           w=st.weight(mu, c, c_coarse, 8, L.F_W_TRANSPOSED, True), flags=L.F_W_TRANSPOSED | st.hb)
     gwu, gbu = st.gregion((mu, "w")), st.gregion((mu, "b"))
-    st.op(st.bwd, OP_WGRAD_UP, level, c_coarse, c, x=IN0, y=dup, w=gwu, b=gbu, flags=L.F_RELU_IN | st.hb)
+    st.op(st.bwd, OP_WGRAD_UP, level, c_coarse, c, x=IN0, y=dup, w=gwu, b=gbu, flags=lead_fl | st.hb)
     return st.freeze()
 
 
@@ -848,6 +964,8 @@ def _record_relu_masks(stage, ns, ws, offs, inputs, out):
     for op in stage.fwd:
         if op.op == OP_RELU:                             # in place: the result has the sign mask of what the ReLU read
             src = op.y
+        elif op.op == OP_ADD_RELU:                       # the branch slab the closing activation read
+            src = op.x1
         elif op.flags & L.F_RELU_IN:
             src = op.x
         else:

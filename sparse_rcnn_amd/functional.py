@@ -1006,6 +1006,23 @@ class AddFunction(torch.autograd.Function):
         return dY, dY
 
 
+class AddStoredFunction(torch.autograd.Function):
+    """AddTable on two bf16-STORED slabs (modules.AddTable(stored=True)): scn_add_bf16, the result stays stored."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        A, B = _feat(a), _feat(b)
+        if A.shape != B.shape or not (_is_bf16(A) and _is_bf16(B)):
+            raise ValueError("AddTable(stored): two bf16 slabs of one shape required")
+        Y = torch.empty_like(A)
+        L.check(L.lib().scn_add_bf16(L.ptr(A), L.ptr(B), A.numel(), L.ptr(Y), L.stream()))
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        return dY, dY
+
+
 # ------------------------------------------------------------------------------------------------------
 # A8 BatchNorm(Leaky)ReLU (module_factory.py:92-102)
 # ------------------------------------------------------------------------------------------------------

@@ -73,6 +73,11 @@ def _conv_input(x, c_in, c_out, tile_kernel):
 # never sees (custom_container.py:70-83), so the first and the third return a DeferredTensor and the fourth -- a Sequential
 # of residual units that is handed a pending NetworkInNetwork -- runs the whole level.  Anything that does not fit computes
 # layer by layer as before; both ways launch the same kernels with the same arguments (bit-identical, tests/test_gpu_exec.py).
+# The factory's other shapes are recognised too (tests/test_gpu_post_act.py): an input stage with its ReLU in front of the layer
+# or behind it (relu_first, drop_input_relu), Deconvolution -> ReLU, post-activation units and plain convolution blocks
+# (`_tree_blocks`).  Those run as stages on fp32 slabs only: under bf16 feature storage the layer-by-layer path widens at a
+# stand-alone ReLU / AddTable, the stage would not.  The bottleneck / main-path-ReLU units with relu_first stay layer by layer in
+# a foreign tree, as they were.
 # ----------------------------------------------------------------------------------------------------------------------
 TREE_STAGES = __import__('os').environ.get("SCN_TREE_STAGES", "1") != "0"
 STAGE_STATS = {"enc": 0, "dec": 0, "layerwise_units": 0}       # how often a forward took which way (tests, bench.py)
@@ -91,6 +96,33 @@ def _head_of(m):
     if type(m) is SubmanifoldConvolution and m.filter_size == 1 and m.groups == 1:
         return m
     return m if (type(m) is Convolution and m.stride == (2, 2, 2)) else None
+
+
+def _stage_of(m):
+    """(head, (ReLU in front, ReLU behind)) of an encoder level's input stage (module_factory.py:438-486), or None."""
+    from . import executor as EX
+    relus = EX._stage_relus(m)
+    if relus is None:
+        return None
+    head = _head_of(m if isinstance(m, _ConvBase) else next(c for c in m._modules.values() if isinstance(c, _ConvBase)))
+    return None if head is None else (head, relus)
+
+
+_TREE_FORMS = ("post", "post_bottleneck", "plain_pre", "plain_post")
+
+
+def _tree_blocks(seq):
+    """executor._unit_blocks of a Sequential of units, limited to the forms a foreign tree's stages take."""
+    from . import executor as EX
+    blocks = EX._unit_blocks(seq)
+    if blocks and any(isinstance(b[0], str) and b[0] not in _TREE_FORMS for b in blocks):
+        return None
+    return blocks
+
+
+def _default_form(blocks, relus):
+    """The shapes the stages always took: plain pre-activation units behind a bare head / ReLU -> Deconvolution."""
+    return relus[1] is False and not any(isinstance(b[0], str) for b in blocks)
 
 
 # A cached shape (`_stage_kind`) / compiled plan (`_stages`) of a Sequential captures its WHOLE subtree: the head, the inner
@@ -134,7 +166,8 @@ def _validate_plan_caches(seq):
 
 
 def _kind(seq):
-    """'enc': (head, units) of an encoder level | 'units': residual units only | 'up': (ReLU, Deconvolution) | None."""
+    """'enc': (input stage, units) of an encoder level | 'units': units only | 'up': (ReLU, Deconvolution) | 'up_post':
+    (Deconvolution, ReLU) | None."""
     _validate_plan_caches(seq)
     kind = seq.__dict__.get("_stage_kind")
     if kind is not None:
@@ -145,12 +178,15 @@ def _kind(seq):
     if (len(mods) == 2 and type(mods[0]) is ReLU and type(mods[1]) is Deconvolution and mods[1].bias is not None
             and mods[1].stride == (2, 2, 2)):
         kind = "up"
-    elif len(mods) == 2 and _head_of(mods[0]) is not None and type(mods[1]) is Sequential:
-        head, blocks = _head_of(mods[0]), EX._plain_blocks(mods[1])
-        if (blocks and head.bias is not None and head.pad_out_to is None and all(c1.nIn == head.nOut for c1, _ in blocks)
+    elif (len(mods) == 2 and type(mods[0]) is Deconvolution and type(mods[1]) is ReLU and mods[0].bias is not None
+            and mods[0].stride == (2, 2, 2)):
+        kind = "up_post"
+    elif len(mods) == 2 and type(mods[1]) is Sequential and _stage_of(mods[0]) is not None:
+        (head, relus), blocks = _stage_of(mods[0]), _tree_blocks(mods[1])
+        if (blocks and head.bias is not None and head.pad_out_to is None and all(EX._block_width(b) == head.nOut for b in blocks)
                 and head.nOut % 8 == 0 and (type(head) is SubmanifoldConvolution or head.nIn % 8 == 0)):
             kind = "enc"
-    elif mods and EX._plain_blocks(seq):
+    elif mods and _tree_blocks(seq):
         kind = "units"
     object.__setattr__(seq, "_stage_kind", kind)
     return kind or None
@@ -163,7 +199,10 @@ def _enc_stage(seq, input):
     if not _usable(f):
         return NotImplemented
     mods = list(seq._modules.values())
-    head = _head_of(mods[0])
+    head, relus = _stage_of(mods[0])
+    blocks = _tree_blocks(mods[1])
+    if not _default_form(blocks, relus) and (f.dtype == torch.bfloat16 or FEATURE_STORAGE is torch.bfloat16):
+        return NotImplemented
     level = 0 if type(head) is SubmanifoldConvolution else 1
     if f.shape[1] != head.nIn:
         return NotImplemented
@@ -182,7 +221,7 @@ def _enc_stage(seq, input):
     cache = seq.__dict__.setdefault("_stages", {})
     st = cache.get(key)
     if st is None:
-        st = cache[key] = EX.compile_encoder_stage(level, head, EX._plain_blocks(mods[1]), head.nIn, bf16, in_bf16=in16)
+        st = cache[key] = EX.compile_encoder_stage(level, head, blocks, head.nIn, bf16, in_bf16=in16, relus=relus)
     md = input.metadata
     lv = EX.build_levels(md, input.spatial_size, level + 1)
     if lv is None:
@@ -203,13 +242,16 @@ def _dec_stage(seq, input):
     _, up_t, skip_t, nin = tag
     if not (isinstance(up_t, DeferredTensor) and up_t.pending and up_t.tag[0] == "up"):
         return NotImplemented
-    _, coarse_t, deconv = up_t.tag
+    _, coarse_t, deconv, *post = up_t.tag
+    relus = (False, True) if post else (True, False)
     xc, xs = coarse_t.features, skip_t.features
     c = deconv.nOut
-    blocks = EX._plain_blocks(seq)
+    blocks = _tree_blocks(seq)
+    if not _default_form(blocks, relus) and (xc.dtype == torch.bfloat16 or FEATURE_STORAGE is torch.bfloat16):
+        return NotImplemented
     if not (_usable(xc) and _usable(xs) and xc.dtype == xs.dtype and xs.shape[1] == c and nin.nIn == 2 * c and nin.nOut == c
             and nin.bias is not None and c % 8 == 0 and deconv.nIn % 8 == 0 and xc.shape[1] == deconv.nIn
-            and deconv.pad_out_to is None and nin.pad_out_to is None and all(c1.nIn == c for c1, _ in blocks)):
+            and deconv.pad_out_to is None and nin.pad_out_to is None and all(EX._block_width(b) == c for b in blocks)):
         return NotImplemented
     md = input.metadata
     fine = tuple(int(s) for s in input.spatial_size)
@@ -220,7 +262,7 @@ def _dec_stage(seq, input):
     key = (id(deconv), id(nin), bf16)
     st = cache.get(key)
     if st is None:
-        st = EX.compile_decoder_stage(0, deconv, nin, blocks, deconv.nIn, bf16)
+        st = EX.compile_decoder_stage(0, deconv, nin, blocks, deconv.nIn, bf16, relus=relus)
         cache[key] = st
         st._keep = (deconv, nin)                         # (the ids in the key stay valid while the plan lives)
     lv = EX.build_levels(md, fine, 2)
@@ -292,6 +334,11 @@ class Sequential(torch.nn.Sequential):
                 out_size = torch.as_tensor([int(s) * 2 for s in input.spatial_size], dtype=torch.long)
                 return DeferredTensor(lambda: deconv(input, relu_in=True).features, input.metadata, out_size,
                                       ("up", input, deconv))
+            elif kind == "up_post" and _usable(input.features):
+                deconv, relu = self._modules["0"], self._modules["1"]
+                out_size = torch.as_tensor([int(s) * 2 for s in input.spatial_size], dtype=torch.long)
+                return DeferredTensor(lambda: relu(deconv(input)).features, input.metadata, out_size,
+                                      ("up", input, deconv, "post"))
         mods = list(self._modules.values())
         i = 0
         while i < len(mods):
@@ -377,11 +424,24 @@ class ConcatTable(Sequential):
     """Applies every child to the same input -> list (module_factory.py:52-54)."""
 
     def forward(self, input):
+        if isinstance(input, DeferredTensor) and input.pending:
+            input.features          # whoever gets here computes layer by layer: no branch may take the tensor for a pending level
         return [m(input) for m in self._modules.values()]
 
 
 class AddTable(Module):
+    def __init__(self, stored=False):
+        """stored (not a reference argument; unet.residual_block sets it on its post-activation unit): bf16-stored operands are
+        added as they are -- widened exactly, one rounding, a bf16 result (scn_add_bf16) -- instead of leaving an fp32 slab."""
+        super().__init__()
+        self.stored = bool(stored)
+
     def forward(self, input):
+        if getattr(self, "stored", False) and all(t.features.dtype == torch.bfloat16 for t in input):   # (getattr: a module pickled before the flag existed)
+            feats = input[0].features
+            for t in input[1:]:
+                feats = F.AddStoredFunction.apply(feats, t.features)
+            return _out(input[0], feats)
         feats = _wide(input[0].features)
         for t in input[1:]:
             feats = F.AddFunction.apply(feats, _wide(t.features))
@@ -408,8 +468,14 @@ def _wide(x):
 
 
 class ReLU(Module):
+    def __init__(self, stored=False):
+        """stored (not a reference argument; unet.py sets it on a ReLU that no convolution follows): a bf16-stored slab stays
+        stored (scn_relu_fwd_bf16, exact) instead of being widened."""
+        super().__init__()
+        self.stored = bool(stored)
+
     def forward(self, input):
-        return _out(input, F.ReLUFunction.apply(_wide(input.features)))
+        return _out(input, F.ReLUFunction.apply(input.features if getattr(self, "stored", False) else _wide(input.features)))
 
 
 class _BatchNorm(Module):

@@ -92,10 +92,12 @@ class SparseStepModel(torch.nn.Module):
 
     def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False, with_class=False,
                  with_segmentation=False, upsample_heads=False, class_storage=None, simple_class=False, bottleneck_divisor=0,
-                 main_path_relu=False):
+                 main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True):
         """bottleneck_divisor, main_path_relu (0 / False: nothing changes): the form of the BACKBONE's residual units
         (unet.residual_block; the reference's switches of the same names, run.py:516-518).  The mask branch's own networks keep
         the plain unit: its level 0 runs on channel-padded slabs, which the other forms do not take.
+        relu_first, drop_input_relu, use_residuals (True: nothing changes): the backbone's post-activation units, the ReLU of
+        its input stages and its plain convolution blocks (unet.py header; run.py:519 and the defaults of model.py:262-269).
         simple_class (with_class="dense" only; False: nothing changes): the dense arm's head is the reference's class network
         WITHOUT pooling (classhead.ReshapeClassBranch; `simple_class`, run.py:706-710) on the same kept volume, fp32.
         class_storage (with_class="dense" on bf16 storage only; None: nothing changes): "bf16" builds the dense class branch
@@ -113,9 +115,11 @@ class SparseStepModel(torch.nn.Module):
         with_segmentation: the reference's segmentation head (classhead.SegmentationHead, 20 classes) on the backbone output.
         Both are constructed AFTER the other modules: under one seed the others start from the same values with or without."""
         super().__init__()
+        stage_kw = dict(relu_first=relu_first, drop_input_relu=drop_input_relu, use_residuals=use_residuals)
         self.backbone = Backbone(7, channels, batchnorm=batchnorm, bf16_blocks=storage,
                                  **(dict(bottleneck_divisor=bottleneck_divisor, main_path_relu=main_path_relu)
-                                    if (bottleneck_divisor or main_path_relu) else {}))
+                                    if (bottleneck_divisor or main_path_relu) else {}),
+                                 **({} if all(stage_kw.values()) else stage_kw))
         self.mask = MaskBranch(channels[0], 7, bf16_blocks=storage) if with_mask else None
         self.rpn = self.roi_selector = None
         self.rpn_levels = None                 # indices of the encoder levels the RPN reads
@@ -199,10 +203,13 @@ class SceneStep:
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
                  upsample_heads=False, class_storage=None, simple_class=False, multitask_loss=False, loss_weights=None,
-                 bottleneck_divisor=0, main_path_relu=False):
+                 bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True):
         """bottleneck_divisor, main_path_relu (0 / False: nothing changes): the backbone's residual units take the reference's
         bottleneck form (inner width C // bottleneck_divisor) and / or its main-path ReLU (unet.residual_block).  dtype="bf16"
         needs every inner width to be a multiple of 8 (ValueError otherwise).  The mask branch keeps the plain unit.
+        relu_first, drop_input_relu, use_residuals (True: nothing changes): the backbone's post-activation units
+        (relu_first=False), the ReLU of its encoder input stages kept (drop_input_relu=False), plain convolution blocks in place
+        of residual units (use_residuals=False; with a non-default bottleneck_divisor / main_path_relu: ValueError).
         loss_weights (None: nothing changes): a dict over `rpn_class`, `rpn_bbox`, `class`, `mask`, `segmentation` with the
         reference's `loss_*_weight` values (default 1 each; run.py keeps `loss_segmentation_weight=1/8` as an option).  A key of
         a loss that is off, an unknown key or a value that is not positive and finite: ValueError.
@@ -398,6 +405,8 @@ class SceneStep:
         if self.segmentation_loss and not self.n_boxes:
             raise ValueError("segmentation_loss=True needs boxes (n_boxes > 0)")
         self.bottleneck_divisor, self.main_path_relu = int(bottleneck_divisor or 0), bool(main_path_relu)
+        self.relu_first, self.drop_input_relu, self.use_residuals = bool(relu_first), bool(drop_input_relu), bool(use_residuals)
+        stage_kw = dict(relu_first=self.relu_first, drop_input_relu=self.drop_input_relu, use_residuals=self.use_residuals)
         self.model = SparseStepModel(self.channels, bool(self.n_boxes), storage, rpn_kind, self.n_boxes,
                                      batchnorm=workload.endswith("-bn"),
                                      with_class="dense" if self.dense_class else self.class_loss,
@@ -406,7 +415,8 @@ class SceneStep:
                                      **(dict(class_storage=class_storage) if class_storage else {}),
                                      **(dict(simple_class=True) if self.simple_class else {}),
                                      **(dict(bottleneck_divisor=self.bottleneck_divisor, main_path_relu=self.main_path_relu)
-                                        if (self.bottleneck_divisor or self.main_path_relu) else {})).to(self.device)
+                                        if (self.bottleneck_divisor or self.main_path_relu) else {}),
+                                     **({} if all(stage_kw.values()) else stage_kw)).to(self.device)
         self.combiner = self.loss_record = None
         if self._loss_weights is not None:
             from .loss import LossCombiner
@@ -953,6 +963,10 @@ class SceneStep:
                 ", 2 residual units/level (" + ", ".join(
                     ([f"bottleneck_divisor={self.bottleneck_divisor}"] if self.bottleneck_divisor else [])
                     + (["main_path_relu=True"] if self.main_path_relu else [])) + ")") + ", 2^3/2 conv+deconv"
+             + ("" if (self.relu_first and self.drop_input_relu and self.use_residuals) else " (" + ", ".join(
+                 ([] if self.relu_first else ["relu_first=False: post-activation units, layer -> ReLU input stages"])
+                 + ([] if self.drop_input_relu else ["drop_input_relu=False"])
+                 + ([] if self.use_residuals else ["use_residuals=False: plain convolution blocks"])) + ")")
              + (", BatchNormReLU in the residual units (training mode, fp64 statistics; layer-by-layer path)"
                 if self.workload.endswith("-bn") else ""))
         if self.n_boxes and self.with_rpn:

@@ -13,8 +13,21 @@ N = SubM 1^3, what the factory's get_channel_changer builds on the sparse side; 
   main_path_relu=True                                  :  y = act(x + K2(act(K1(x))))                no activation on the way in (:163-171)
   both                                                 :  y = act(x + N2(act(K(act(N1(x))))))
 
-Flags reproduced: relu_first=True, main_path_relu and bottleneck_divisor as given, drop_input_relu=True, num_units=2,
-use_residuals=True, concat=True, batchnorm=False (scannet_config/run.py:516-519,609-623).
+relu_first=False (the default of the reference's FeatureExtractor class, model.py:262-269; :163-171 takes the main_path_relu
+branch, so those two forms stay as above and only the first two change -- the activation closes the BRANCH):
+  bottleneck_divisor=0, main_path_relu=False           :  y = x + act(K2(act(K1(x))))
+  bottleneck_divisor=d, main_path_relu=False           :  y = x + act(N2(act(K(act(N1(x))))))
+
+Input stage of a level (get_input_stage, :438-486; layer = the SubM 1^3 / Convolution / Deconvolution above):
+  relu_first=True  : act -> layer        relu_first=False : layer -> act (in place)        ReLU dropped : layer alone
+An encoder level drops it with drop_input_relu; a decoder level (:533-578) never does.
+
+use_residuals=False (get_unit_stage :489-510, get_convolution_blocks :186-218): the units of a level are one flat Sequential,
+[act, K] * num_units with relu_first, [K, act] * num_units without -- no skip, no AddTable.
+
+Flags reproduced: relu_first, drop_input_relu, use_residuals, main_path_relu and bottleneck_divisor as given (defaults: the
+committed configuration's True, True, True, False, 0), num_units=2, concat=True, batchnorm=False
+(scannet_config/run.py:516-519,609-623).
 """
 from __future__ import annotations
 
@@ -34,8 +47,14 @@ def inner_width(c, bottleneck_divisor):
     return ci
 
 
-def residual_block(c, batchnorm=False, bottleneck_divisor=0, main_path_relu=False):
-    """module_factory.py:127-183 get_residual_block(relu_first=True) inside :51-57 sparse_residual(inner_block, Identity,
+def _act(ch, batchnorm, stored=False):
+    """The activation of module_factory.py:116-124.  stored: a ReLU no convolution follows (it cannot be fused into a gather)
+    runs on a bf16-stored slab as it is instead of widening it -- what the step executor's SCN_OP_RELU does."""
+    return M.BatchNormReLU(ch) if batchnorm else M.ReLU(stored=stored)
+
+
+def residual_block(c, batchnorm=False, bottleneck_divisor=0, main_path_relu=False, relu_first=True):
+    """module_factory.py:127-183 get_residual_block inside :51-57 sparse_residual(inner_block, Identity,
     activation): the forms of the header comment, in the reference's nesting."""
     def act(ch):
         return M.BatchNormReLU(ch) if batchnorm else M.ReLU()
@@ -48,43 +67,89 @@ def residual_block(c, batchnorm=False, bottleneck_divisor=0, main_path_relu=Fals
         body = [M.SubmanifoldConvolution(3, c, c, 3, not batchnorm), act(c), M.SubmanifoldConvolution(3, c, c, 3, not batchnorm)]
     if main_path_relu:                                       # the activation closes the unit instead of opening its branch
         return M.Sequential(M.ConcatTable(M.Identity(), M.Sequential(*body)), M.AddTable(), act(c))
+    if not relu_first:                                       # post-activation: the activation closes the branch (:170)
+        return M.Sequential(M.ConcatTable(M.Identity(), M.Sequential(*body, _act(c, batchnorm, True))), M.AddTable(stored=True))
     return M.Sequential(M.ConcatTable(M.Identity(), M.Sequential(act(c), *body)), M.AddTable())
 
 
-def units(c, num_units=2, batchnorm=False, bottleneck_divisor=0, main_path_relu=False):
-    return M.Sequential(*[residual_block(c, batchnorm, bottleneck_divisor, main_path_relu) for _ in range(num_units)])
+def plain_blocks(c, num_units=2, batchnorm=False, relu_first=True):
+    """module_factory.py:186-218 get_convolution_blocks at one width: [act, K] * num_units | [K, act] * num_units, flat."""
+    layers = []
+    for _ in range(num_units):
+        conv = M.SubmanifoldConvolution(3, c, c, 3, not batchnorm)
+        layers += [_act(c, batchnorm), conv] if relu_first else [conv, _act(c, batchnorm, True)]
+    return M.Sequential(*layers)
 
 
-def unit_conv_indices(bottleneck_divisor=0, main_path_relu=False):
+def check_unit_switches(use_residuals=True, bottleneck_divisor=0, main_path_relu=False):
+    if not use_residuals and (bottleneck_divisor or main_path_relu):
+        raise ValueError("use_residuals=False builds plain convolution blocks: the reference would ignore bottleneck_divisor "
+                         "and main_path_relu there (module_factory.py:505-507) -- leave them at their defaults")
+
+
+def units(c, num_units=2, batchnorm=False, bottleneck_divisor=0, main_path_relu=False, relu_first=True, use_residuals=True):
+    check_unit_switches(use_residuals, bottleneck_divisor, main_path_relu)
+    if not use_residuals:
+        return plain_blocks(c, num_units, batchnorm, relu_first)
+    kw = {} if relu_first else dict(relu_first=False)
+    return M.Sequential(*[residual_block(c, batchnorm, bottleneck_divisor, main_path_relu, **kw) for _ in range(num_units)])
+
+
+def input_stage(layer, batchnorm=False, relu_first=True, drop_relu=False):
+    """module_factory.py:438-486 get_input_stage around `layer`; with the ReLU dropped the stage is the layer itself."""
+    if drop_relu:
+        return layer
+    if relu_first:
+        return M.Sequential(_act(layer.nIn, batchnorm), layer)
+    return M.Sequential(layer, _act(layer.nOut, batchnorm, True))
+
+
+def stage_layer(stage):
+    """The conv-type layer of an input stage (`input_stage`)."""
+    if isinstance(stage, M._ConvBase):
+        return stage
+    return next(m for m in stage if isinstance(m, M._ConvBase))
+
+
+def unit_conv_indices(bottleneck_divisor=0, main_path_relu=False, relu_first=True):
     """Positions of a unit's convolutions inside its inner Sequential (ConcatTable[1]): the activations between them take
     the others, and relu_first without main_path_relu puts one in front."""
     n = 3 if bottleneck_divisor else 2
-    first = 0 if main_path_relu else 1
+    first = 0 if (main_path_relu or not relu_first) else 1
     return tuple(first + 2 * v for v in range(n))
 
 
-def reference_key_map(n_levels, num_units=2, bottleneck_divisor=0, main_path_relu=False):
+def reference_key_map(n_levels, num_units=2, bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True,
+                      use_residuals=True):
     """state_dict key of the reference's FeatureExtractor (sparse + U-Net: `main_network` = SequentialInterims of encoder
     levels, `unet.module_list` = SkipConnectionReuniter per decoder level; module_factory.py:438-578, model.py:364-391)
     -> this package's parameter name (`SparseUNet.named_oracle_params`).  Checked against the key list of a reference
     FeatureExtractor built on this package (tests/golden/dropin_feature_extractor.json; the bottleneck / main-path-ReLU
     forms: tests/golden/unit_forms_keys.json)."""
+    check_unit_switches(use_residuals, bottleneck_divisor, main_path_relu)
     out = {}
-    conv_at = unit_conv_indices(bottleneck_divisor, main_path_relu)
+    conv_at = unit_conv_indices(bottleneck_divisor, main_path_relu, relu_first)
+    head_at = 1 if (relu_first and not drop_input_relu) else 0   # a ReLU leads the encoder's input stage
+    up_at = 1 if relu_first else 0                               # the decoder never drops it: act -> Deconv | Deconv -> act
+
+    def unit_keys(ref, own, t):
+        for u in range(num_units):
+            if not use_residuals:                            # flat [act, K] * n | [K, act] * n
+                out[f"{ref}.{2 * u + (1 if relu_first else 0)}.{t}"] = f"{own}.res{u}.conv0.{t}"
+                continue
+            for v, idx in enumerate(conv_at):                # the unit's convolutions inside ConcatTable[1]
+                out[f"{ref}.{u}.0.1.{idx}.{t}"] = f"{own}.res{u}.conv{v}.{t}"
+
     for l in range(n_levels):
         for t in ("weight", "bias"):
-            out[f"main_network.{l}.0.0.{t}"] = f"enc{l}.in.{t}"
-            for u in range(num_units):
-                for v, idx in enumerate(conv_at):                # the unit's convolutions inside ConcatTable[1]
-                    out[f"main_network.{l}.1.{u}.0.1.{idx}.{t}"] = f"enc{l}.res{u}.conv{v}.{t}"
+            out[f"main_network.{l}.0.{head_at}.{t}"] = f"enc{l}.in.{t}"
+            unit_keys(f"main_network.{l}.1", f"enc{l}", t)
     for i in range(n_levels - 1):
         l = n_levels - 2 - i
         for t in ("weight", "bias"):
-            out[f"unet.module_list.{i}.input_stage.1.{t}"] = f"dec{l}.up.{t}"
+            out[f"unet.module_list.{i}.input_stage.{up_at}.{t}"] = f"dec{l}.up.{t}"
             out[f"unet.module_list.{i}.channel_changer.{t}"] = f"dec{l}.nin.{t}"
-            for u in range(num_units):
-                for v, idx in enumerate(conv_at):
-                    out[f"unet.module_list.{i}.output_stage.{u}.0.1.{idx}.{t}"] = f"dec{l}.res{u}.conv{v}.{t}"
+            unit_keys(f"unet.module_list.{i}.output_stage", f"dec{l}", t)
     return out
 
 
@@ -93,9 +158,10 @@ class SparseUNet(nn.Module):
     resolution; ``.interims`` holds the encoder outputs (the reference's SequentialInterims, custom_container.py:5-12)."""
 
     def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False,
-                 identity_first=False, min_channels=0, bottleneck_divisor=0, main_path_relu=False):
-        """bottleneck_divisor, main_path_relu: the form of every residual unit (header comment; the defaults build what this
-        class always built).  bf16_blocks="all" then also needs every unit's inner width C // bottleneck_divisor to be a
+                 identity_first=False, min_channels=0, bottleneck_divisor=0, main_path_relu=False, relu_first=True,
+                 drop_input_relu=True, use_residuals=True):
+        """bottleneck_divisor, main_path_relu, relu_first, use_residuals: the form of every unit; relu_first and drop_input_relu:
+        the ReLU of the input stages (header comment; the defaults build what this class always built).  bf16_blocks="all" then also needs every unit's inner width C // bottleneck_divisor to be a
         multiple of 8; bf16_blocks=True (the fused bf16 node of the plain unit) has no form for them: ValueError.
         identity_first: level 0 of the encoder is the reference's FLD('I') -- no layer at all, channels[0] == cin
         (the mask head's internal U-Net: scannet_config/run.py:756-775, I -> B32/2 -> B48/2 -> B64/2; the decoder's
@@ -124,20 +190,25 @@ class SparseUNet(nn.Module):
         self.bf16_blocks = bool(bf16_blocks) and not self.bf16_all
         if bf16_blocks and (batchnorm or any(c % 8 for c in self.channels[1 if identity_first else 0:])):
             raise ValueError("bf16_blocks needs channel counts that are multiples of 8 and no batch norm")
+        self.relu_first, self.drop_input_relu, self.use_residuals = bool(relu_first), bool(drop_input_relu), bool(use_residuals)
+        check_unit_switches(self.use_residuals, self.bottleneck_divisor, self.main_path_relu)
+        stage_form = not (self.relu_first and self.drop_input_relu and self.use_residuals)
         new_form = bool(self.bottleneck_divisor) or self.main_path_relu
-        if new_form and self.bf16_blocks:
-            raise ValueError("bf16_blocks=True runs the plain residual unit as one fused bf16 node: with bottleneck_divisor or "
-                             "main_path_relu use bf16_blocks='all'")
+        if (new_form or stage_form) and self.bf16_blocks:
+            raise ValueError("bf16_blocks=True runs the plain residual unit as one fused bf16 node: with bottleneck_divisor, "
+                             "main_path_relu, relu_first=False, drop_input_relu=False or use_residuals=False use bf16_blocks='all'")
         if self.bottleneck_divisor:
             widths = [w for l, w in enumerate(self.channels) if not (l == 0 and self.identity_first)] + list(self.dec_channels)
             inner = sorted({inner_width(w, self.bottleneck_divisor) for w in widths})
             if self.bf16_all and any(ci % 8 for ci in inner):
                 raise ValueError(f"bf16_blocks needs channel counts that are multiples of 8: bottleneck_divisor="
                                  f"{self.bottleneck_divisor} gives inner widths {inner}")
-        if new_form and self.identity_first and self.channels[0] % 8:
-            raise ValueError("bottleneck_divisor / main_path_relu are not combined with a channel-padded level 0 "
-                             f"(identity_first on {self.channels[0]} channels)")
+        if (new_form or stage_form) and self.identity_first and self.channels[0] % 8:
+            raise ValueError("bottleneck_divisor / main_path_relu / relu_first=False / drop_input_relu=False / use_residuals=False "
+                             f"are not combined with a channel-padded level 0 (identity_first on {self.channels[0]} channels)")
         unit_kw = dict(bottleneck_divisor=self.bottleneck_divisor, main_path_relu=self.main_path_relu) if new_form else {}
+        if not (self.relu_first and self.use_residuals):
+            unit_kw.update(relu_first=self.relu_first, use_residuals=self.use_residuals)
         enc = []
         for l, c in enumerate(self.channels):
             if l == 0 and self.identity_first:
@@ -145,14 +216,16 @@ class SparseUNet(nn.Module):
                 continue
             head = (M.SubmanifoldConvolution(3, cin, c, 1, True) if l == 0
                     else M.Convolution(3, self.channels[l - 1], c, (2, 2, 2), (2, 2, 2), True))
-            enc.append(M.Sequential(head, units(c, num_units, batchnorm, **unit_kw)))
+            enc.append(M.Sequential(input_stage(head, batchnorm, self.relu_first, self.drop_input_relu),
+                                    units(c, num_units, batchnorm, **unit_kw)))
         self.encoder = nn.ModuleList(enc)
         dec = []
         for l in range(len(self.channels) - 2, -1, -1):
             c, d = self.channels[l], self.dec_channels[l]
             cup = self.channels[l + 1] if l == len(self.channels) - 2 else self.dec_channels[l + 1]
             dec.append(nn.ModuleDict(dict(
-                up=M.Sequential(M.ReLU(), M.Deconvolution(3, cup, d, (2, 2, 2), (2, 2, 2), True)),
+                up=(M.Sequential(M.ReLU(), M.Deconvolution(3, cup, d, (2, 2, 2), (2, 2, 2), True)) if self.relu_first else
+                    input_stage(M.Deconvolution(3, cup, d, (2, 2, 2), (2, 2, 2), True), batchnorm, False)),
                 join=M.JoinTable(),
                 nin=M.NetworkInNetwork(d + c, d, True),
                 units=units(d, num_units, batchnorm, **unit_kw))))
@@ -170,7 +243,7 @@ class SparseUNet(nn.Module):
                     raise ValueError(f"batch norm on a level-0 width of {c0}: that level runs on slabs zero-padded to "
                                      f"{self.phys0} columns, and batch norm takes no padded slab")
                 self.out_phys = self.phys0
-                d0["up"][1].pad_out_to = self.phys0
+                stage_layer(d0["up"]).pad_out_to = self.phys0
                 d0["nin"].pad_out_to = self.phys0
                 d0["nin"].in_groups = (c0, c0)
                 for m in d0["units"].modules():
@@ -311,8 +384,10 @@ class SparseUNet(nn.Module):
         ok = ok and self.dec_channels == tuple(ch[:-1])      # (min_channels in effect: the layer-by-layer path)
         enc_blocks = [EX._unit_blocks(lvl[1]) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
         dec_blocks = [EX._unit_blocks(d["units"]) for d in self.decoder]
-        heads = [lvl[0] for l, lvl in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
-        ok = ok and EX._require_bias(*heads, *[d["up"][1] for d in self.decoder], *[d["nin"] for d in self.decoder])
+        heads = [stage_layer(lvl[0]) for l, lvl in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
+        ok = ok and EX._require_bias(*heads, *[stage_layer(d["up"]) for d in self.decoder], *[d["nin"] for d in self.decoder])
+        ok = ok and all(EX._stage_relus(lvl[0]) is not None for l, lvl in enumerate(self.encoder)
+                        if not (l == 0 and self.identity_first)) and all(EX._stage_relus(d["up"]) is not None for d in self.decoder)
         if ok and all(b is not None for b in enc_blocks + dec_blocks):
             bf16 = self.bf16_all
             phys = [self.phys0] + list(ch[1:])
@@ -321,13 +396,14 @@ class SparseUNet(nn.Module):
                 if l == 0 and self.identity_first:
                     enc.append(None)
                     continue
-                head = self.encoder[l][0]
+                head = stage_layer(self.encoder[l][0])
                 cin_phys = head.nIn if l == 0 else phys[l - 1]
-                enc.append(EX.compile_encoder_stage(l, head, enc_blocks[l], cin_phys, bf16))
+                enc.append(EX.compile_encoder_stage(l, head, enc_blocks[l], cin_phys, bf16, relus=EX._stage_relus(self.encoder[l][0])))
             dec = []
             for i, d in enumerate(self.decoder):
                 l = L - 2 - i
-                dec.append(EX.compile_decoder_stage(l, d["up"][1], d["nin"], dec_blocks[i], phys[l + 1], bf16))
+                dec.append(EX.compile_decoder_stage(l, stage_layer(d["up"]), d["nin"], dec_blocks[i], phys[l + 1], bf16,
+                                                    relus=EX._stage_relus(d["up"])))
             plan = dict(enc=enc, dec=dec)
         object.__setattr__(self, "_exec_plan_cache", plan)
         return plan
@@ -405,11 +481,11 @@ class SparseUNet(nn.Module):
         for l, level in enumerate(self.encoder):
             if l == 0 and self.identity_first:
                 continue
-            out[f"enc{l}.in.weight"], out[f"enc{l}.in.bias"] = level[0].weight, level[0].bias
+            out[f"enc{l}.in.weight"], out[f"enc{l}.in.bias"] = stage_layer(level[0]).weight, stage_layer(level[0]).bias
             self._res(out, f"enc{l}", level[1])
         for i, d in enumerate(self.decoder):
             l = len(self.channels) - 2 - i
-            out[f"dec{l}.up.weight"], out[f"dec{l}.up.bias"] = d["up"][1].weight, d["up"][1].bias
+            out[f"dec{l}.up.weight"], out[f"dec{l}.up.bias"] = stage_layer(d["up"]).weight, stage_layer(d["up"]).bias
             out[f"dec{l}.nin.weight"], out[f"dec{l}.nin.bias"] = d["nin"].weight, d["nin"].bias
             self._res(out, f"dec{l}", d["units"])
         return out
@@ -421,6 +497,10 @@ class SparseUNet(nn.Module):
         units_of = [(f"enc{l}", level[1]) for l, level in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
         units_of += [(f"dec{len(self.channels) - 2 - i}", d["units"]) for i, d in enumerate(self.decoder)]
         for prefix, unit_seq in units_of:
+            if len(unit_seq) and not isinstance(unit_seq[0], M.Sequential):    # use_residuals=False: one batch norm per pair
+                for u, bn in enumerate(m for m in unit_seq if isinstance(m, M._BatchNorm)):
+                    out[f"{prefix}.res{u}.bn0.running_mean"], out[f"{prefix}.res{u}.bn0.running_var"] = bn.running_mean, bn.running_var
+                continue
             for u, block in enumerate(unit_seq):
                 bns = [m for m in block[0][1] if isinstance(m, M._BatchNorm)]
                 bns += [m for m in list(block)[2:] if isinstance(m, M._BatchNorm)]     # main_path_relu: the closing activation
@@ -431,6 +511,14 @@ class SparseUNet(nn.Module):
 
     @staticmethod
     def _res(out, prefix, unit_seq):
+        if len(unit_seq) and not isinstance(unit_seq[0], M.Sequential):        # use_residuals=False: flat (act, K) | (K, act) pairs
+            for u, cv in enumerate(m for m in unit_seq if isinstance(m, M.SubmanifoldConvolution)):
+                out[f"{prefix}.res{u}.conv0.weight"] = cv.weight
+                if cv.bias is not None:
+                    out[f"{prefix}.res{u}.conv0.bias"] = cv.bias
+            for u, bn in enumerate(m for m in unit_seq if isinstance(m, M._BatchNorm)):
+                out[f"{prefix}.res{u}.bn0.weight"], out[f"{prefix}.res{u}.bn0.bias"] = bn.weight, bn.bias
+            return
         for u, block in enumerate(unit_seq):
             inner = block[0][1]
             for v, bn in enumerate(m for m in inner if isinstance(m, M._BatchNorm)):
@@ -451,12 +539,16 @@ class SparseUNet(nn.Module):
         from the first key that ends in 'main_network.0.0.0.weight'.  -> (missing reference keys, unused checkpoint keys)."""
         if self.identity_first:
             raise NotImplementedError("the mask head's internal U-Net is not a FeatureExtractor checkpoint")
+        head_at = 1 if (self.relu_first and not self.drop_input_relu) else 0
         if prefix is None:
-            tail = "main_network.0.0.0.weight"
+            tail = f"main_network.0.0.{head_at}.weight"
             prefix = next((k[:-len(tail)] for k in state_dict if k.endswith(tail)), "")
         own = self.named_oracle_params()
         num_units = len(self.decoder[0]["units"]) if len(self.decoder) else len(self.encoder[0][1])
-        kmap = reference_key_map(len(self.channels), num_units, self.bottleneck_divisor, self.main_path_relu)
+        if not self.use_residuals:
+            num_units //= 2                                   # (a flat Sequential of pairs)
+        kmap = reference_key_map(len(self.channels), num_units, self.bottleneck_divisor, self.main_path_relu, self.relu_first,
+                                 self.drop_input_relu, self.use_residuals)
         missing, used = [], set()
         with torch.no_grad():
             for rk, name in kmap.items():
@@ -487,10 +579,11 @@ class Backbone(nn.Module):
     """InputLayer(mode 4) + SparseUNet: what model.py:414-431 runs for sparse + include_unet."""
 
     def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False,
-                 bottleneck_divisor=0, main_path_relu=False):
+                 bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True):
         super().__init__()
         self.unet = SparseUNet(cin, channels, num_units, batchnorm, bf16_blocks, bottleneck_divisor=bottleneck_divisor,
-                               main_path_relu=main_path_relu)
+                               main_path_relu=main_path_relu, relu_first=relu_first, drop_input_relu=drop_input_relu,
+                               use_residuals=use_residuals)
 
     # How a forward without prepared metadata builds its index structures: False = step by step from Python (row-count
     # waits overlapped with kernel queueing: faster when nothing else can run meanwhile), True = one scn_pyramid_build
