@@ -82,7 +82,9 @@ extern "C" {
  *      additive within 5: + scn_roialign_pool_fwd / _bwd, their _bf16 forms, scn_box_flatten_fwd / _bwd (175 entry points);
  *      additive within 5: + scn_loss_combine / scn_loss_combine_bwd (177 entry points);
  *      additive within 5: + scn_conv_tiles_plan_describe (178 entry points);
- *      additive within 5: + the executor op SCN_OP_ADD_RELU, no new entry point (178 entry points) */
+ *      additive within 5: + the executor op SCN_OP_ADD_RELU, no new entry point (178 entry points);
+ *      additive within 5: + the executor ops SCN_OP_BN_STATS / _BN_FWD / _BN_BWD and the op flag SCN_XF_BN_TRAINING;
+ *                           SCN_OP_WGRAD_SUBM with b < 0 is scn_wgrad_rules(_bf16); no new entry point (178 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -754,7 +756,7 @@ enum {
     SCN_OP_CONV_CHILD = 3,   /* scn_conv_tiles(_bf16) over the level's child tiles: Convolution fwd / Deconvolution bwd-data */
     SCN_OP_RULES_CHILD = 4,  /* scn_gemm_rules(_bf16) coarse -> fine: Deconvolution fwd / Convolution bwd-data              */
     SCN_OP_ROWS2 = 5,        /* scn_gemm_rows2: NiN over two joined parts (fwd), or its two-destination bwd-data             */
-    SCN_OP_WGRAD_SUBM = 6,   /* scn_wgrad_bias_rules(_bf16) on the level's 3^3 rules                                          */
+    SCN_OP_WGRAD_SUBM = 6,   /* scn_wgrad_bias_rules(_bf16) on the level's 3^3 rules; b < 0 (no bias): scn_wgrad_rules(_bf16)    */
     SCN_OP_WGRAD2_SUBM = 7,  /* scn_wgrad_bias_rules2(_bf16): both convolutions of a residual unit                             */
     SCN_OP_WGRAD_DOWN = 8,   /* Convolution: scn_wgrad_rules(_bf16) on the child rules (X fine, dY coarse)                     */
     SCN_OP_WGRAD_UP = 9,     /* Deconvolution: scn_wgrad_bias_rules(_bf16), roles swapped (X coarse, dY fine), db over all 8  */
@@ -764,12 +766,21 @@ enum {
     SCN_OP_CAST = 13,        /* storage cast: SCN_XF_BF16 set = fp32 -> bf16, else bf16 -> fp32                               */
     SCN_OP_RELU = 14,        /* y = max(x, 0) (scn_relu_fwd / _bf16), y may be x: the closing ReLU of a main-path residual unit */
     SCN_OP_RELU_BWD = 15,    /* y = x1 where m > 0, else 0 (scn_relu_bwd / _bf16): m = the slab the ReLU read OR wrote         */
-    SCN_OP_ADD_RELU = 16     /* y = x + max(x1, 0) over rows * cin elements in ONE pass, x1 left as it is, y may be x: the end of a
+    SCN_OP_ADD_RELU = 16,    /* y = x + max(x1, 0) over rows * cin elements in ONE pass, x1 left as it is, y may be x: the end of a
                               * post-activation residual unit (module_factory.py:163-171, relu_first=False).  The only op that is not
                               * an entry point of its own; scn_relu_fwd's expression, scn_add's operand order and (bf16) one
                               * rounding: bit-equal to SCN_OP_RELU (x1 -> r) followed by SCN_OP_ADD (x, r -> y)                    */
+    /* BatchNorm(Leaky)ReLU over the fp32 slab x ([rows][cin]); none of them takes SCN_XF_BF16.  w = params[] id of gamma, beta =
+     * params[w + 1].  mean | var: the 2 * cin floats of bufs[x1] (batch statistics), or with x1 < 0 the layer's running buffers
+     * params[w + 2], params[w + 3].  aux / c1 = the bits of eps / leakiness as fp32.  Scratch: scn_bn_scratch_bytes(cin) of the
+     * pass's shared region (scn_exec_requirements counts it). */
+    SCN_OP_BN_STATS = 17,    /* scn_bn_stats: x -> bufs[y] = mean[cin] | biased var[cin]                                       */
+    SCN_OP_BN_FWD = 18,      /* scn_bn_fwd: x -> y                                                                             */
+    SCN_OP_BN_BWD = 19       /* scn_bn_bwd: x, m = dY -> y = dX, grads[b] = dgamma[cin] | dbeta[cin]; SCN_XF_BN_TRAINING: the
+                              * statistics were the batch's (the gradient passes through them), else constants                 */
 };
 #define SCN_XF_BF16 (1 << 16)        /* op flag: the op's feature slabs are bf16-stored                                      */
+#define SCN_XF_BN_TRAINING (1 << 18) /* op flag (BN_BWD; BN_FWD carries it too): batch statistics, see SCN_OP_BN_BWD                    */
 #define SCN_XF_COARSE_ROWS (1 << 17) /* op flag (GEMM_IDENT / WGRAD_IDENT / COLSUM / ADD / CAST / RELU / RELU_BWD): rows = n_coarse of `level` */
 
 typedef struct scn_exec_level {
@@ -800,10 +811,12 @@ typedef struct scn_exec_op {
     int32_t cin, cout;               /* of the CALL (backward-data calls swap the layer's) */
     int32_t x, y;                    /* buffer ids: source slab, destination slab (wgrad ops: X operand, dY operand) */
     int32_t r, m;                    /* residual operand, relu-mask operand; -1: none */
-    int32_t x1, y1;                  /* ROWS2: second source / second destination; WGRAD2: second operand pair; ADD: x1; RELU_BWD: x1 = dY */
-    int32_t c1;                      /* ROWS2: channels of the second source (fwd) / second destination (bwd) */
-    int32_t w, b;                    /* params[] ids (weight or bf16 image, bias) -- wgrad / colsum ops: grads[] ids; -1: none */
-    int32_t aux;                     /* WGRAD_IDENT: element offset into grads[w]; WGRAD_*: unused */
+    int32_t x1, y1;                  /* ROWS2: second source / second destination; WGRAD2: second operand pair; ADD: x1; RELU_BWD: x1 = dY;
+                                      * BN_FWD / BN_BWD: x1 = the mean | var vector, -1: the running buffers */
+    int32_t c1;                      /* ROWS2: channels of the second source (fwd) / second destination (bwd); BN_*: leakiness bits */
+    int32_t w, b;                    /* params[] ids (weight or bf16 image, bias) -- wgrad / colsum ops: grads[] ids; -1: none;
+                                      * BN_*: w = params[] id of gamma (see SCN_OP_BN_STATS), BN_BWD: b = grads[] id */
+    int32_t aux;                     /* WGRAD_IDENT: element offset into grads[w]; WGRAD_*: unused; BN_*: eps bits */
     int32_t reserved;
 } scn_exec_op;
 

@@ -7,6 +7,7 @@
 // node per layer.  Every op IS one of the library's own entry points with the arguments the layer-by-layer path passes, so
 // the two paths produce the same bits (tests/test_gpu_exec.py).
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 #include <atomic>
@@ -55,6 +56,8 @@ inline int call_flags(const scn_exec_op& o) { return o.flags & 0xffff; }
 inline int64_t rows_of(const scn_exec_op& o, const scn_exec_level& L) {
     return (o.flags & SCN_XF_COARSE_ROWS) ? L.n_coarse : L.n;
 }
+
+inline float bits_f32(int32_t v) { float f; memcpy(&f, &v, sizeof f); return f; }
 
 template <typename T>
 inline T* B(const Ctx& c, int id) { return id < 0 ? nullptr : (T*)c.bufs[id]; }
@@ -117,6 +120,12 @@ int run_op(const Ctx& c0, const scn_exec_op& o, void* own_scratch = nullptr) {
                               nullptr, B<void>(c, o.y), o.cout, nullptr, 0, fl, h ? 1 : 0, st);
     }
     case SCN_OP_WGRAD_SUBM: {
+        if (o.b < 0) {               // a layer without bias (the convolutions of a batch-norm unit): the call its own backward makes
+            if (h) return scn_wgrad_rules_bf16(B<u16>(c, o.x), o.cin, B<u16>(c, o.y), o.cout, L.in_rows, L.out_rows, L.prefix_host,
+                                               27, G<float>(c, o.w), c.scratch, fl, st);
+            return scn_wgrad_rules(B<float>(c, o.x), o.cin, B<float>(c, o.y), o.cout, L.in_rows, L.out_rows, L.prefix_host, 27,
+                                   G<float>(c, o.w), c.scratch, fl, st);
+        }
         const uint32_t dbm = o.b >= 0 ? (1u << 13) : 0u;
         if (h) return scn_wgrad_bias_rules_bf16(B<u16>(c, o.x), o.cin, B<u16>(c, o.y), o.cout, L.in_rows, L.out_rows, L.prefix_host,
                                                 27, G<float>(c, o.w), G<float>(c, o.b), dbm, c.scratch, fl, st);
@@ -196,6 +205,29 @@ int run_op(const Ctx& c0, const scn_exec_op& o, void* own_scratch = nullptr) {
         if (h) return scn::add_relu_bf16(B<u16>(c, o.x), B<u16>(c, o.x1), count, B<u16>(c, o.y), st);
         return scn::add_relu(B<float>(c, o.x), B<float>(c, o.x1), count, B<float>(c, o.y), st);
     }
+    // BatchNorm(Leaky)ReLU on fp32 slabs.  params[w], params[w + 1] = gamma, beta; mean | var: the 2 * cin floats of bufs[x1]
+    // (batch statistics, SCN_OP_BN_STATS wrote them) or, x1 < 0, the running buffers params[w + 2], params[w + 3].
+    case SCN_OP_BN_STATS: {
+        SCN_REQUIRE(!h && o.cin >= 1 && o.y >= 0);
+        float* mv = B<float>(c, o.y);
+        SCN_REQUIRE(mv != nullptr);
+        return scn_bn_stats(B<float>(c, o.x), rows_of(o, L), o.cin, mv, mv + o.cin, c.scratch, st);
+    }
+    case SCN_OP_BN_FWD:
+    case SCN_OP_BN_BWD: {
+        SCN_REQUIRE(!h && o.cin >= 1 && o.w >= 0 && c.params != nullptr);
+        const float* mean = o.x1 >= 0 ? B<float>(c, o.x1) : P<float>(c, o.w + 2);
+        const float* var = o.x1 >= 0 ? (mean ? mean + o.cin : nullptr) : P<float>(c, o.w + 3);
+        const float eps = bits_f32(o.aux), leak = bits_f32(o.c1);
+        if (o.op == SCN_OP_BN_FWD)
+            return scn_bn_fwd(B<float>(c, o.x), rows_of(o, L), o.cin, mean, var, eps, P<float>(c, o.w), P<float>(c, o.w + 1), leak,
+                              B<float>(c, o.y), st);
+        float* dgamma = G<float>(c, o.b);
+        SCN_REQUIRE(dgamma != nullptr);
+        return scn_bn_bwd(B<float>(c, o.x), B<float>(c, o.m), rows_of(o, L), o.cin, mean, var, eps, P<float>(c, o.w),
+                          P<float>(c, o.w + 1), leak, (o.flags & SCN_XF_BN_TRAINING) ? 1 : 0, B<float>(c, o.y), dgamma,
+                          dgamma + o.cin, c.scratch, st);
+    }
     default:
         return scn::fail(SCN_EINVAL, "scn_exec_run: unknown op %s%lld", "", o.op);
     }
@@ -233,6 +265,8 @@ int pass_needs(const scn_exec_op* ops, int n_ops, const scn_exec_level* levels, 
             break;
         }
         case SCN_OP_COLSUM: s = (int64_t)SCN_COLSUM_BLOCKS * o.cin * (int64_t)sizeof(float); break;
+        case SCN_OP_BN_STATS:
+        case SCN_OP_BN_BWD: s = o.cin >= 1 ? scn_bn_scratch_bytes(o.cin) : -1; break;
         default: {
             const int64_t w = wgrad_scratch_of(o, L);
             if (w < 0) return scn::fail(SCN_EINVAL, "scn_exec: op %s%lld has bad arguments", "", i);

@@ -14,17 +14,25 @@ autograd edges, and the encoder outputs (`SparseUNet.interims`, the RPN's inputs
 
 Units: the plain pre-activation residual unit, the reference's bottleneck / main-path-ReLU forms, its post-activation units
 (relu_first=False) and its plain convolution blocks (use_residuals=False) (`_unit_blocks`); input stages with the ReLU in front
-of the layer, behind it, or dropped (`_stage_relus`).
+of the layer, behind it, or dropped (`_stage_relus`).  Batch-norm networks (`SparseUNet(batchnorm=True, bn_stages=True)`, or
+SCN_EXEC_BN=1): every one of those units and input stages with BatchNorm(Leaky)ReLU where the ReLU stood (`_bn_blocks`).  A
+batch-norm activation is never folded into the consuming convolution: it is SCN_OP_BN_STATS + SCN_OP_BN_FWD writing a slab
+of its own, SCN_OP_BN_BWD on the way back; its batch mean / variance live in the stage workspace and the host applies the
+running-statistics update after the forward call (`run_stage`), with the statements functional.BatchNormReLUFunction uses.
 
-Not covered (the layer-by-layer path runs instead): batch norm, `bf16_blocks=True` (casts around every run of units),
-channel plans the two-source NetworkInNetwork kernel does not take, empty levels, and any step in which
-`profiling.TIMER` brackets single launches with events.
+Not covered (the layer-by-layer path runs instead): batch norm without `bn_stages`, `bf16_blocks=True` (casts around every
+run of units), channel plans the two-source NetworkInNetwork kernel does not take, empty levels, and any step in which
+`profiling.TIMER` brackets single launches with events.  A batch-norm network also steps aside while `modules._BatchNorm.SYNC`
+is on with an initialised process group (the all-reduce sits between two kernels of a layer), while
+`functional.RELU_RECORD` records activation masks, and when its batch-norm layers are not all in the network's own
+training / evaluation mode.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
 import os
+import struct
 import threading
 
 import torch
@@ -36,6 +44,8 @@ from . import modules as M
 ENABLED = os.environ.get("SCN_EXEC", "1") != "0"
 # parameter-gradient ops of a backward pass on a second stream beside the backward-data chain (scn_exec_run_streams)
 SIDE_LEAVES = os.environ.get("SCN_EXEC_SIDE", "0") != "0"
+# developer switch: batch-norm networks built WITHOUT `bn_stages=True` compile stage plans too (A/B of an unmodified bench.py)
+BN_STAGES = os.environ.get("SCN_EXEC_BN", "0") != "0"
 _side_streams, _side_scratch = {}, {}
 
 i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
@@ -43,7 +53,9 @@ i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
 OP_GEMM_IDENT, OP_CONV_SUBM, OP_CONV_CHILD, OP_RULES_CHILD, OP_ROWS2 = 1, 2, 3, 4, 5
 OP_WGRAD_SUBM, OP_WGRAD2_SUBM, OP_WGRAD_DOWN, OP_WGRAD_UP, OP_WGRAD_IDENT, OP_COLSUM, OP_ADD, OP_CAST = 6, 7, 8, 9, 10, 11, 12, 13
 OP_RELU, OP_RELU_BWD, OP_ADD_RELU = 14, 15, 16
-XF_BF16, XF_COARSE_ROWS = 1 << 16, 1 << 17
+OP_BN_STATS, OP_BN_FWD, OP_BN_BWD = 17, 18, 19
+XF_BF16, XF_COARSE_ROWS, XF_BN_TRAINING = 1 << 16, 1 << 17, 1 << 18
+VEC = -1                                # `level` of a buffer that is one row whatever the level sizes are (batch mean | variance)
 BACK = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
 
 
@@ -61,6 +73,16 @@ class ExecLevel(C.Structure):
 
 def _addr(prefix_host):
     return C.cast(prefix_host, vp).value
+
+
+def _f32_bits(v):
+    """The int32 that holds float(v) rounded to fp32 -- how eps / leakiness travel in an ExecOp (ctypes rounds the same way when
+    the layer-by-layer path hands them to a `float` argument)."""
+    return struct.unpack("<i", struct.pack("<f", float(v)))[0]
+
+
+def _rows(ns, lv):
+    return 1 if lv < 0 else ns[lv]
 
 
 def build_levels(md, size, n_levels):
@@ -161,7 +183,9 @@ def _levels_from_native(md, nat, n_levels):
 class Stage:
     """The launch plan of one autograd node: forward and backward op lists over symbolic buffer / parameter / gradient ids."""
 
-    def __init__(self, bf16, n_inputs):
+    def __init__(self, bf16, n_inputs, bn_training=True):
+        self.bn_training = bool(bn_training)     # batch-norm layers of the plan: batch statistics | the running buffers
+        self.bn_layers = []             # training: (mod idx, buffer id of [mean | var], level) per batch-norm layer, module order
         self.bf16 = bool(bf16)
         self.hb = XF_BF16 if bf16 else 0
         self.es = 2 if bf16 else 4
@@ -170,6 +194,7 @@ class Stage:
         self.bufs = []                  # id -> (level, channels, elem bytes, kind)   kind: "f" fwd ws | "b" bwd ws | "x" external
         self.mods = []                  # modules whose (W, b) the node takes: (module, cin_phys)
         self.params = []                # params-table descriptors: ("w", mod idx) | ("b", mod idx) | ("img", mod idx, cin, cout, n_off, flags)
+                                        # | ("rm", mod idx) | ("rv", mod idx): a batch-norm layer's running buffers (evaluation)
         self.gregions = []              # gradient regions: list of [(mod idx, "w"|"b"), ...] laid out back to back
         self.in_ids, self.din_ids = [], []
         self.out_id = self.dout_id = None
@@ -212,7 +237,7 @@ class Stage:
         for k, blk in enumerate(blocks):
             if isinstance(blk[0], str):                      # a bottleneck / main-path-ReLU unit (_unit_blocks)
                 y = out_id if (out_id is not None and k == len(blocks) - 1) else self.buf(level, c)
-                saved.append(self._form_fwd(level, c, x, y, blk))
+                saved.append((self._bn_fwd if blk[0] == "bn" else self._form_fwd)(level, c, x, y, blk))
                 x = y
                 continue
             c1, c2 = blk
@@ -231,7 +256,7 @@ class Stage:
         for k, sv in enumerate(reversed(saved)):
             if isinstance(sv[0], str):
                 dx = din_id if (din_id is not None and k == len(saved) - 1) else self.buf(level, c, kind="b")
-                self._form_bwd(level, c, g, dx, sv)
+                (self._bn_bwd if sv[0] == "bn" else self._form_bwd)(level, c, g, dx, sv)
                 g = dx
                 continue
             x, y1, m1, m2 = sv
@@ -341,6 +366,97 @@ class Stage:
         self.op(self.bwd, OP_WGRAD_SUBM, level, ci, ci, x=a, y=db, w=self.gregion((mk, "w")), b=self.gregion((mk, "b")), flags=relu)
         self.op(self.bwd, OP_WGRAD_IDENT, level, c, ci, x=x, y=da, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
 
+    # ---- batch-norm activations and units (bn_stages) ---------------------------------------------------------------------
+    # A BatchNorm(Leaky)ReLU layer is SCN_OP_BN_STATS (training mode: batch mean | biased variance -> ONE 2c-float vector of the
+    # stage workspace) + SCN_OP_BN_FWD reading slab x and writing a slab y of its own -- never a flag of the consuming
+    # convolution --, and SCN_OP_BN_BWD (x, dy -> dx and dgamma | dbeta in ONE gradient region) on the way back: scn_bn_stats /
+    # scn_bn_fwd / scn_bn_bwd with the arguments functional.BatchNormReLUFunction passes.  gamma and beta sit next to each other
+    # in the params table (`w` names gamma); evaluation mode: the running buffers follow them, no statistics op is planned.
+    def bn_layer(self, level, m, x, y):
+        c = int(m.nPlanes)
+        mi = self.mod(m, c)
+        if ("w", mi) in self.params:
+            raise RuntimeError("executor plan: a batch-norm layer stands twice in one stage")
+        gp = self.param("w", mi)
+        self.param("b", mi)
+        mv, fl = -1, 0
+        if self.bn_training:
+            mv, fl = self.buf(VEC, 2 * c, 4), XF_BN_TRAINING
+            self.op(self.fwd, OP_BN_STATS, level, c, 0, x=x, y=mv)
+            self.bn_layers.append((mi, mv, level))
+        else:
+            self.param("rm", mi)
+            self.param("rv", mi)
+        eps, leak = _f32_bits(m.eps), _f32_bits(m.leakiness)
+        self.op(self.fwd, OP_BN_FWD, level, c, 0, x=x, y=y, x1=mv, w=gp, aux=eps, c1=leak, flags=fl)
+        return (level, c, mi, x, mv, gp, eps, leak, fl)
+
+    def bn_layer_bwd(self, rec, g, dx):
+        level, c, mi, x, mv, gp, eps, leak, fl = rec
+        self.op(self.bwd, OP_BN_BWD, level, c, 0, x=x, m=g, y=dx, x1=mv, w=gp, b=self.gregion((mi, "w"), (mi, "b")), aux=eps,
+                c1=leak, flags=fl)
+
+    def _chain_conv(self, level, m, cin, x, y, r=-1):
+        """A SubM 3^3 / 1^3 layer of a batch-norm unit: no activation in its gather, its bias (None beside batch norm) as it is."""
+        mi, cout = self.mod(m, cin), int(m.nOut)
+        b = self.param("b", mi) if m.bias is not None else -1
+        if m.filter_size == 3:
+            self.op(self.fwd, OP_CONV_SUBM, level, cin, cout, x=x, y=y, r=r, w=self.weight(mi, cin, cout, 27, 0, True), b=b, flags=self.hb)
+        else:
+            self.op(self.fwd, OP_GEMM_IDENT, level, cin, cout, x=x, y=y, r=r, w=self.param("w", mi), b=b, flags=self.hb)
+        return (mi, m.filter_size, cin, cout, x, m.bias is not None)
+
+    def _chain_conv_bwd(self, level, rec, g, dx):
+        mi, k, cin, cout, x, has_b = rec
+        if k == 3:
+            self.op(self.bwd, OP_CONV_SUBM, level, cout, cin, x=g, y=dx, w=self.weight(mi, cout, cin, 27, BACK, True), flags=BACK | self.hb)
+        else:
+            self.op(self.bwd, OP_GEMM_IDENT, level, cout, cin, x=g, y=dx, w=self.param("w", mi), flags=BACK | self.hb)
+        gw = self.gregion((mi, "w"))
+        gb = self.gregion((mi, "b")) if has_b else -1      # (no bias: scn_wgrad_rules, as the layer's own backward)
+        self.op(self.bwd, OP_WGRAD_SUBM if k == 3 else OP_WGRAD_IDENT, level, cin, cout, x=x, y=g, w=gw, b=gb, flags=self.hb)
+
+    def _bn_fwd(self, level, c, x, y, blk):
+        """A unit of `_bn_blocks`: the branch layer by layer, every layer writing a slab of its own.  skip "res": x joins in the
+        last convolution's epilogue (modules.Sequential hands it the residual); "add": one SCN_OP_ADD behind a branch that ends
+        in its activation (post-activation); None: a flat run of plain blocks.  closing: the activation of a main-path unit."""
+        _, _, skip, mods, closing = blk
+        end = y if closing is None else self.buf(level, c)
+        t, w, tape = x, c, []
+        for i, m in enumerate(mods):
+            last = i == len(mods) - 1
+            bn = isinstance(m, M._BatchNorm)
+            cout = int(m.nPlanes) if bn else int(m.nOut)
+            dst = end if (last and skip != "add") else self.buf(level, cout)
+            if bn:
+                tape.append(("a", self.bn_layer(level, m, t, dst)))
+            else:
+                tape.append(("k", self._chain_conv(level, m, w, t, dst, r=x if (last and skip == "res") else -1)))
+            t, w = dst, cout
+        if skip == "add":
+            self.op(self.fwd, OP_ADD, level, c, 0, x=x, x1=t, y=end, flags=self.hb)
+        crec = self.bn_layer(level, closing, end, y) if closing is not None else None
+        return ("bn", skip, tape, crec)
+
+    def _bn_bwd(self, level, c, g, dx, sv):
+        _, skip, tape, crec = sv
+        if crec is not None:
+            gs = self.buf(level, c, kind="b")
+            self.bn_layer_bwd(crec, g, gs)
+            g = gs
+        t = g
+        for i in range(len(tape) - 1, -1, -1):
+            kind, rec = tape[i]
+            cin = rec[1] if kind == "a" else rec[2]
+            dst = dx if (i == 0 and skip is None) else self.buf(level, cin, kind="b")
+            if kind == "a":
+                self.bn_layer_bwd(rec, t, dst)
+            else:
+                self._chain_conv_bwd(level, rec, t, dst)
+            t = dst
+        if skip is not None:                                # the two gradient paths of x: layer by layer autograd adds them
+            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=self.hb)
+
     # ---- finish -----------------------------------------------------------------------------------------------------
     def freeze(self):
         self.fwd_arr = (ExecOp * len(self.fwd))(*self.fwd)
@@ -352,13 +468,18 @@ class Stage:
         self.bwd_specs = [(self.bufs[i][0], self.bufs[i][1] * self.bufs[i][2]) for i in self.bwd_ws]
         self.w_entries = [(k, 2 * d[1]) for k, d in enumerate(self.params) if d[0] == "w"]
         self.b_entries = [(k, 2 * d[1] + 1) for k, d in enumerate(self.params) if d[0] == "b"]
-        self.img_entries = [(k, 2 * d[1]) + tuple(d[2:]) for k, d in enumerate(self.params) if d[0] not in ("w", "b")]
+        self.img_entries = [(k, 2 * d[1]) + tuple(d[2:]) for k, d in enumerate(self.params) if d[0] == "img"]
+        # batch norm: the running buffers an evaluation-mode plan reads, the positions of gamma / beta among the node's parameters
+        self.stat_entries = [(k, d[1], "running_mean" if d[0] == "rm" else "running_var") for k, d in enumerate(self.params)
+                             if d[0] in ("rm", "rv")]
+        self.bn_phys = frozenset(2 * i + j for i, (m, _) in enumerate(self.mods) if isinstance(m, M._BatchNorm) for j in (0, 1))
         self.grad_views = {}                              # tuple of parameter shapes -> (region offsets, total, views)
         # a main-path unit that ends the stage: its backward masks by the stage's OUTPUT slab, which then is saved for backward
         self.bwd_reads_out = any(getattr(op, f) == self.out_id for op in self.bwd for f in ("x", "y", "r", "m", "x1", "y1"))
         self._lean_slots()
         covered = sorted(m for reg in self.gregions for m in reg)
-        want = sorted((i, k) for i in range(len(self.mods)) for k in ("w", "b"))
+        want = sorted((i, k) for i, (m, _) in enumerate(self.mods) for k in ("w", "b")
+                      if k == "w" or getattr(m, "bias", None) is not None or not self.bn_phys)
         if covered != want:
             raise RuntimeError("executor plan: every parameter must sit in exactly one gradient region")
         return self
@@ -386,7 +507,7 @@ def _lean_slots(self):
                     slot_of[v] = (cls, n_slots.get(cls, 0))
                     n_slots[cls] = n_slots.get(cls, 0) + 1
         for v in (op.x, op.r, op.m, op.x1, op.y, op.y1):
-            if v in slot_of and last[v] == t and slot_of[v] is not None:
+            if v in slot_of and last[v] == t and slot_of[v] is not None and self.bufs[v][0] != VEC:   # (VEC: the host reads it after the pass)
                 cls, k = slot_of[v]
                 if k not in free.setdefault(cls, []):
                     free[cls].append(k)
@@ -418,7 +539,7 @@ def _lean_layout(stage, ns):
     """-> (offset per forward workspace buffer, total bytes) of the forward-only plan."""
     base, tot = {}, 0
     for (lv, row_bytes), k in stage.lean_classes:
-        size = (ns[lv] * row_bytes + 255) & ~255
+        size = (_rows(ns, lv) * row_bytes + 255) & ~255
         base[(lv, row_bytes)] = (tot, size)
         tot += size * k
     return [base[cls][0] + k * base[cls][1] for cls, k in stage.lean_slot_of], tot
@@ -443,10 +564,59 @@ def _plain_blocks(unit_seq):
     return out
 
 
-def _unit_blocks(unit_seq):
+def _bn_chain(mods, c):
+    """Channels behind a run of BatchNorm(Leaky)ReLU / SubM 3^3 / SubM 1^3 layers that starts at c channels; None: not such a run."""
+    for m in mods:
+        if isinstance(m, M._BatchNorm):
+            if int(m.nPlanes) != c:
+                return None
+        elif (type(m) is M.SubmanifoldConvolution and m.filter_size in (1, 3) and m.groups == 1 and not m.pad_out_to
+                and m.nIn == c):
+            c = m.nOut
+        else:
+            return None
+    return c
+
+
+def _bn_blocks(unit_seq):
+    """`_unit_blocks` of a batch-norm network: every unit form of unet.residual_block / plain_blocks with BatchNorm(Leaky)ReLU where
+    the ReLU stands, as ("bn", channels, skip, branch layers, closing activation | None) -- skip "res": the branch ends in a
+    convolution that adds x in its epilogue (pre-activation, bottleneck, main-path units); "add": the branch ends in its
+    activation and an AddTable follows (post-activation); None: one flat run [act, K] * n | [K, act] * n.  A ReLU that batch
+    norm replaced never appears: a unit that still holds one is none of these (None)."""
+    mods = list(unit_seq._modules.values()) if isinstance(unit_seq, torch.nn.Sequential) else list(unit_seq)
+    if mods and all(isinstance(m, (M._BatchNorm, M.SubmanifoldConvolution)) for m in mods):
+        c = int(mods[0].nPlanes) if isinstance(mods[0], M._BatchNorm) else mods[0].nIn
+        kinds = [isinstance(m, M._BatchNorm) for m in mods]
+        if len(mods) % 2 or kinds != [kinds[0], not kinds[0]] * (len(mods) // 2) or _bn_chain(mods, c) != c:
+            return None
+        return [("bn", c, None, mods, None)]
+    out = []
+    for block in mods:
+        if not (type(block) is M.Sequential and len(block) in (2, 3) and type(block[0]) is M.ConcatTable
+                and type(block[1]) is M.AddTable and len(block[0]._modules) == 2):
+            return None
+        closing = block[2] if len(block) == 3 else None
+        a, inner = list(block[0]._modules.values())
+        if type(a) is not M.Identity or type(inner) is not M.Sequential or not len(inner):
+            return None
+        branch = list(inner._modules.values())
+        c = int(branch[0].nPlanes) if isinstance(branch[0], M._BatchNorm) else getattr(branch[0], "nIn", None)
+        if c is None or _bn_chain(branch, c) != c or not any(isinstance(m, M._BatchNorm) for m in branch):
+            return None
+        if closing is not None and not (isinstance(closing, M._BatchNorm) and int(closing.nPlanes) == c):
+            return None
+        out.append(("bn", c, "add" if isinstance(branch[-1], M._BatchNorm) else "res", branch, closing))
+    return out
+
+
+def _unit_blocks(unit_seq, bn=False):
     """_plain_blocks with the reference's other unit forms: a plain unit stays (conv1, conv2); the others come as
     ("bottleneck" | "both", N1, K, N2) and ("main", K1, K2) -- "both" and "main" close with a ReLU (main_path_relu).  None when
-    a block is none of them (batch norm, a layer without bias, channel padding, groups)."""
+    a block is none of them (batch norm, a layer without bias, channel padding, groups).
+    bn: a batch-norm layer may stand wherever a ReLU may (`_bn_blocks`)."""
+    if bn and any(isinstance(m, M._BatchNorm) for m in (unit_seq.modules() if isinstance(unit_seq, torch.nn.Module) else unit_seq)):
+        return _bn_blocks(unit_seq)
     out = []
     mods = list(unit_seq._modules.values()) if isinstance(unit_seq, torch.nn.Sequential) else list(unit_seq)
     if mods and len(mods) % 2 == 0 and all(type(m) in (M.ReLU, M.SubmanifoldConvolution) for m in mods):
@@ -509,6 +679,8 @@ def _unit_blocks(unit_seq):
 
 def _block_width(blk):
     """Channels a unit of `_unit_blocks` takes and gives."""
+    if blk[0] == "bn":
+        return blk[1]
     return (blk[1] if isinstance(blk[0], str) else blk[0]).nIn
 
 
@@ -516,28 +688,48 @@ def _phys(m):
     return int(getattr(m, "pad_out_to", None) or m.nOut)
 
 
-def _stage_relus(stage):
+def _stage_relus(stage, bn=False):
     """(a ReLU leads the layer, a ReLU follows it) of an input stage (module_factory.py:438-486): the conv-type layer itself or a
-    Sequential of just it -- (False, False) --, Sequential(ReLU, layer), Sequential(layer, ReLU).  None: anything else."""
+    Sequential of just it -- (False, False) --, Sequential(ReLU, layer), Sequential(layer, ReLU).  None: anything else.
+    bn: a batch-norm layer may stand where the ReLU does; the pair then holds that MODULE in place of True."""
     if isinstance(stage, M._ConvBase):
         return (False, False)
     if type(stage) is not M.Sequential:
         return None
-    kinds = tuple("r" if type(m) is M.ReLU else ("c" if isinstance(m, M._ConvBase) else "?") for m in stage._modules.values())
-    return {("c",): (False, False), ("r", "c"): (True, False), ("c", "r"): (False, True)}.get(kinds)
+    mods = list(stage._modules.values())
+    kinds = tuple("r" if (type(m) is M.ReLU or (bn and isinstance(m, M._BatchNorm))) else ("c" if isinstance(m, M._ConvBase) else "?")
+                  for m in mods)
+    out = {("c",): (False, False), ("r", "c"): (True, False), ("c", "r"): (False, True)}.get(kinds)
+    if out is None or not bn:
+        return out
+    act = mods[0] if out[0] else (mods[1] if out[1] else None)
+    if isinstance(act, M._BatchNorm):
+        return (act, False) if out[0] else (False, act)
+    return out
+
+
+def _bn_of(flag):
+    """The batch-norm layer a `_stage_relus` entry names, or None (no activation there, or a ReLU)."""
+    return flag if isinstance(flag, M._BatchNorm) else None
 
 
 def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False, cast_last=False, in_bf16=False,
-                          relus=(False, False)):
+                          relus=(False, False), bn_training=True):
     """Encoder level: head (SubM 1^3 at level 0 | Convolution 2^3/2 from level-1) + residual units.
     level 0 in bf16 storage: the head runs in fp32 on the fp32 input and its result is cast (SparseUNet), or -- cast_first,
     the mask branch's input stage -- the input is cast first and the head runs on bf16 rows, or -- in_bf16 -- the input
     slab is bf16-stored already (a SubM 1^3 stage behind a bf16 network in a module tree); cast_last: fp32 output.
     relus (`_stage_relus`): a ReLU in front of the head is fused into its gather; one behind it is an in-place SCN_OP_RELU on the
-    head's result, whose backward masks by that slab."""
+    head's result, whose backward masks by that slab.  A batch-norm layer in either place (`_stage_relus(bn=True)`; fp32 slabs
+    only) reads one slab and writes another: in front, the head gathers the normalised slab; behind, the units start from it.
+    bn_training: the batch-norm layers of the stage take batch statistics (False: their running buffers)."""
     lead, trail = relus
+    lead_bn, trail_bn = _bn_of(lead), _bn_of(trail)
+    if bf16 and (lead_bn or trail_bn or any(b[0] == "bn" for b in blocks)):
+        raise NotImplementedError("executor: batch norm runs on fp32 slabs")
+    lead, trail = bool(lead) and lead_bn is None, bool(trail) and trail_bn is None
     lead_fl = L.F_RELU_IN if lead else 0
-    st = Stage(bf16, 1)
+    st = Stage(bf16, 1, bn_training)
     in_bf16 = bool(bf16 and in_bf16 and level == 0)
     es_in = (2 if in_bf16 else 4) if (level == 0) else st.es
     c = _phys(head)
@@ -560,20 +752,34 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
             x, head_in, head_hb = h, xin, XF_BF16
         else:
             h = st.buf(0, c, 4)
-            st.op(st.fwd, OP_GEMM_IDENT, 0, cin_phys, c, x=IN, y=h, w=st.param("w", mh), b=st.param("b", mh), flags=lead_fl)
+            head_in = IN
+            if lead_bn is not None:
+                head_in = st.buf(0, cin_phys, 4)
+                lead_rec = st.bn_layer(0, lead_bn, IN, head_in)
+            st.op(st.fwd, OP_GEMM_IDENT, 0, cin_phys, c, x=head_in, y=h, w=st.param("w", mh), b=st.param("b", mh), flags=lead_fl)
             if trail:
                 st.op(st.fwd, OP_RELU, 0, c, 0, x=h, y=h, flags=0)
-            x, head_in, head_hb = h, IN, 0
+            x, head_hb = h, 0
+            if trail_bn is not None:
+                x = st.buf(0, c, 4)
+                trail_rec = st.bn_layer(0, trail_bn, h, x)
             if bf16:
                 x = st.buf(0, c)
                 st.op(st.fwd, OP_CAST, 0, c, 0, x=h, y=x, flags=XF_BF16)
     else:
         x = st.buf(level, c)
-        st.op(st.fwd, OP_CONV_CHILD, level - 1, cin_phys, c, x=IN, y=x, w=st.weight(mh, cin_phys, c, 8, 0, True),
+        head_in = IN
+        if lead_bn is not None:
+            head_in = st.buf(level - 1, cin_phys)
+            lead_rec = st.bn_layer(level - 1, lead_bn, IN, head_in)
+        st.op(st.fwd, OP_CONV_CHILD, level - 1, cin_phys, c, x=head_in, y=x, w=st.weight(mh, cin_phys, c, 8, 0, True),
               b=st.param("b", mh), flags=lead_fl | st.hb)
         h = x
         if trail:
             st.op(st.fwd, OP_RELU, level, c, 0, x=x, y=x, flags=st.hb)
+        if trail_bn is not None:
+            x = st.buf(level, c)
+            trail_rec = st.bn_layer(level, trail_bn, h, x)
     if bf16 and cast_last:
         last, saved = st.units_fwd(level, c, x, blocks)
         st.op(st.fwd, OP_CAST, level, c, 0, x=last, y=OUT, flags=0)
@@ -606,27 +812,47 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
                 gm = st.buf(0, c, 4, "b")
                 st.op(st.bwd, OP_RELU_BWD, 0, c, 0, m=h, x1=gf, y=gm, flags=0)
                 gf = gm
-            st.op(st.bwd, OP_GEMM_IDENT, 0, c, cin_phys, x=gf, y=DIN, m=IN if lead else -1, w=st.param("w", mh), flags=BACK)
-            st.op(st.bwd, OP_WGRAD_IDENT, 0, cin_phys, c, x=IN, y=gf, w=gw, b=gb, flags=lead_fl)
+            if trail_bn is not None:
+                gm = st.buf(0, c, 4, "b")
+                st.bn_layer_bwd(trail_rec, gf, gm)
+                gf = gm
+            dhead = DIN if lead_bn is None else st.buf(0, cin_phys, 4, "b")
+            st.op(st.bwd, OP_GEMM_IDENT, 0, c, cin_phys, x=gf, y=dhead, m=IN if lead else -1, w=st.param("w", mh), flags=BACK)
+            st.op(st.bwd, OP_WGRAD_IDENT, 0, cin_phys, c, x=head_in, y=gf, w=gw, b=gb, flags=lead_fl)
+            if lead_bn is not None:
+                st.bn_layer_bwd(lead_rec, dhead, DIN)
     else:
         if trail:
             gm = st.buf(level, c, kind="b")
             st.op(st.bwd, OP_RELU_BWD, level, c, 0, m=h, x1=g, y=gm, flags=st.hb)
             g = gm
-        st.op(st.bwd, OP_RULES_CHILD, level - 1, c, cin_phys, x=g, y=DIN, m=IN if lead else -1, w=st.param("w", mh),
+        if trail_bn is not None:
+            gm = st.buf(level, c, kind="b")
+            st.bn_layer_bwd(trail_rec, g, gm)
+            g = gm
+        dhead = DIN if lead_bn is None else st.buf(level - 1, cin_phys, kind="b")
+        st.op(st.bwd, OP_RULES_CHILD, level - 1, c, cin_phys, x=g, y=dhead, m=IN if lead else -1, w=st.param("w", mh),
               flags=L.F_W_TRANSPOSED | st.hb)
-        st.op(st.bwd, OP_WGRAD_DOWN, level - 1, cin_phys, c, x=IN, y=g, w=gw, flags=lead_fl | st.hb)
+        st.op(st.bwd, OP_WGRAD_DOWN, level - 1, cin_phys, c, x=head_in, y=g, w=gw, flags=lead_fl | st.hb)
         st.op(st.bwd, OP_COLSUM, level, c, 0, x=g, b=gb, flags=st.hb)
+        if lead_bn is not None:
+            st.bn_layer_bwd(lead_rec, dhead, DIN)
     return st.freeze()
 
 
-def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, False)):
+def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, False), bn_training=True):
     """Decoder level: ReLU -> Deconvolution 2^3/2 (coarse level+1 -> level) -> JoinTable([up, skip]) -> NetworkInNetwork ->
     residual units.  Inputs: (coarse slab, skip slab).  relus (`_stage_relus`): (True, False) is that form; (False, True) the
-    relu_first=False one, Deconvolution -> ReLU, the ReLU in place on the deconvolution's result."""
+    relu_first=False one, Deconvolution -> ReLU, the ReLU in place on the deconvolution's result.  A batch-norm layer behind
+    the deconvolution (fp32 slabs only) writes the slab the NetworkInNetwork reads; in front of it: not a form the network
+    builder makes (NotImplementedError)."""
     lead, trail = relus
+    trail_bn = _bn_of(trail)
+    if _bn_of(lead) is not None or (bf16 and (trail_bn is not None or any(b[0] == "bn" for b in blocks))):
+        raise NotImplementedError("executor: a decoder level takes batch norm behind its deconvolution, on fp32 slabs")
+    trail = bool(trail) and trail_bn is None
     lead_fl = L.F_RELU_IN if lead else 0
-    st = Stage(bf16, 2)
+    st = Stage(bf16, 2, bn_training)
     c = _phys(up)
     IN0 = st.buf(level + 1, c_coarse, None, "x")
     IN1 = st.buf(level, c, None, "x")
@@ -639,8 +865,12 @@ def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, F
           flags=lead_fl | st.hb)
     if trail:
         st.op(st.fwd, OP_RELU, level, c, 0, x=upb, y=upb, flags=st.hb)
+    upa = upb                                              # what the NetworkInNetwork reads
+    if trail_bn is not None:
+        upa = st.buf(level, c)
+        trail_rec = st.bn_layer(level, trail_bn, upb, upa)
     h = st.buf(level, c)
-    st.op(st.fwd, OP_ROWS2, level, c, c, x=upb, x1=IN1, c1=c, y=h, w=st.param("w", mn), b=st.param("b", mn), flags=st.hb)
+    st.op(st.fwd, OP_ROWS2, level, c, c, x=upa, x1=IN1, c1=c, y=h, w=st.param("w", mn), b=st.param("b", mn), flags=st.hb)
     last, saved = st.units_fwd(level, c, h, blocks, out_id=OUT)
     # ---- backward
     DOUT = st.buf(level, c, None, "x")
@@ -652,11 +882,15 @@ def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, F
     dup = st.buf(level, c, kind="b")
     st.op(st.bwd, OP_ROWS2, level, c, c, x=g, y=dup, y1=DIN1, c1=c, w=st.param("w", mn), flags=L.F_W_TRANSPOSED | st.hb)
     gwn, gbn = st.gregion((mn, "w")), st.gregion((mn, "b"))
-    st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=upb, y=g, w=gwn, b=gbn, aux=0, flags=st.hb)
+    st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=upa, y=g, w=gwn, b=gbn, aux=0, flags=st.hb)
     st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=IN1, y=g, w=gwn, b=-1, aux=c * c, flags=st.hb)
     if trail:
         dm = st.buf(level, c, kind="b")
         st.op(st.bwd, OP_RELU_BWD, level, c, 0, m=upb, x1=dup, y=dm, flags=st.hb)
+        dup = dm
+    if trail_bn is not None:
+        dm = st.buf(level, c, kind="b")
+        st.bn_layer_bwd(trail_rec, dup, dm)
         dup = dm
     st.op(st.bwd, OP_CONV_CHILD, level, c, c_coarse, x=dup, y=DIN0, m=IN0 if lead else -1,
           w=st.weight(mu, c, c_coarse, 8, L.F_W_TRANSPOSED, True), flags=L.F_W_TRANSPOSED | st.hb)
@@ -672,7 +906,7 @@ def _layout(specs, ns):
     offs, tot = [], 0
     for lv, row_bytes in specs:
         offs.append(tot)
-        tot += (ns[lv] * row_bytes + 255) & ~255
+        tot += (_rows(ns, lv) * row_bytes + 255) & ~255
     return offs, tot
 
 
@@ -798,11 +1032,13 @@ def _step_eligible(stage, kept, needs, pending=()):
         for which, p in ((0, m.weight), (1, m.bias)):
             j = 2 * mi + which
             if p is None:                       # (phys[j] was None as well: save_for_backward skipped it)
+                if stage.bn_phys:               # a batch-norm stage: its units' convolutions have no bias, nothing to deliver
+                    continue
                 return None
             if kept[k] is not p or not p.is_leaf:
                 return None
             k += 1
-            if not needs[j]:
+            if not needs[j] or j in stage.bn_phys:      # (gamma / beta: scn_bn_bwd writes them inside the pass -- never held back)
                 continue
             if p.grad is not None or id(p) in pending or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
                 return None
@@ -854,6 +1090,11 @@ class StageFunction(torch.autograd.Function):
         for k, j in stage.b_entries:
             t = phys[j]
             ptab[k] = 0 if t is None else (t if (t.dtype is f32 and t.is_contiguous()) else F._f32(t)).data_ptr()
+        stats = [getattr(stage.mods[mi][0], name) for _, mi, name in stage.stat_entries]
+        for (k, _, _), t in zip(stage.stat_entries, stats):
+            if t.dtype is not f32 or not t.is_contiguous() or t.device != dev:
+                raise L.ScnError("executor: the running statistics of a batch-norm layer must be contiguous fp32 on the slabs' device")
+            ptab[k] = t.data_ptr()
         for k, j, cin, cout, n_off, fl in stage.img_entries:
             if lean and fl:                      # a backward-data image: only a backward pass reads it
                 continue
@@ -868,9 +1109,18 @@ class StageFunction(torch.autograd.Function):
         _run(stage, stage.fwd_arr, levels, table, ptab, None, dev)
         if F.RELU_RECORD is not None:
             _record_relu_masks(stage, ns, ws, offs, inputs, out)
+        if stage.bn_layers:                      # batch mean / variance of every batch-norm layer, for `run_stage`
+            where = dict(zip(stage.fwd_ws, offs))
+            handed = []
+            for mi, mv, blv in stage.bn_layers:
+                c = stage.bufs[mv][1] // 2
+                both = ws[where[mv]:where[mv] + 8 * c].view(f32)
+                handed.append((stage.mods[mi][0], both[:c], both[c:], ns[blv]))
+            _bn_handed.stats = handed
         if lean:
             return out
         ctx.stage, ctx.levels, ctx.table, ctx.ptab = stage, levels, table, ptab
+        ctx.stats = stats                        # (evaluation-mode batch norm: the backward reads the running buffers through ptab)
         ctx.phys_shapes = tuple(None if t is None else tuple(t.shape) for t in phys)
         # Everything the pointer tables name travels through save_for_backward: the parameter tensors, the forward workspace,
         # the packed weight images and the input slabs.  They stay alive exactly as long as autograd keeps the graph
@@ -946,7 +1196,8 @@ class StageFunction(torch.autograd.Function):
                 scope.deliver.append((p, flat[v[0]:v[0] + v[1]].view(v[2])))
                 scope.pending.add(id(p))
             scope.passes += 1
-            return (None, None, None, *dins, *([None] * len(views)))
+            return (None, None, None, *dins,
+                    *[flat[v[0]:v[0] + v[1]].view(v[2]) if (j in stage.bn_phys and v is not None) else None for j, v in enumerate(views)])
         _run(stage, stage.bwd_arr, levels, table, ptab, gtab, dev, side=True)
         grads = [None if v is None else flat[v[0]:v[0] + v[1]].view(v[2]) for v in views]
         del kept
@@ -979,6 +1230,21 @@ def _record_relu_masks(stage, ns, ws, offs, inputs, out):
         F._rec_relu(t)
 
 
+_bn_handed = threading.local()
+
+
+def _update_running_stats():
+    """The running-statistics update of every batch-norm layer of the stage that just ran, in module order: the statements of
+    functional.BatchNormReLUFunction.forward on the batch mean / biased variance the stage computed (views of its workspace)
+    and the level's row count -- same operands, same torch kernels, same bits."""
+    handed, _bn_handed.stats = getattr(_bn_handed, "stats", None) or (), None
+    with torch.no_grad():
+        for m, mean, var, n in handed:
+            momentum = float(m.momentum)
+            m.running_mean.mul_(momentum).add_(mean, alpha=1 - momentum)
+            m.running_var.mul_(momentum).add_(var, alpha=(1 - momentum) * (n / (n - 1) if n > 1 else 1.0))
+
+
 def _require_bias(*mods):
     """Plans write a bias gradient for every conv-type layer they cover (COLSUM / the b region of the WGRAD ops): a layer
     built with bias=False keeps the layer-by-layer path."""
@@ -992,8 +1258,12 @@ def run_stage(stage, levels, inputs, pack=False):
     stage's weight images are packed by ONE launch of its own instead of one per image."""
     phys = []
     for m, cin_phys in stage.mods:
-        W, b = m._wb(cin_phys)
+        W, b = (m.weight, m.bias) if isinstance(m, M._BatchNorm) else m._wb(cin_phys)
         phys += [W, b]
+    if stage.bn_layers:
+        y = StageFunction.apply(stage, levels, _lean(inputs, phys), *inputs, *phys)
+        _update_running_stats()
+        return y
     if pack and stage.bf16:
         lean = _lean(inputs, phys)
         attr = "_pack_plan_fwd" if lean else "_pack_plan"

@@ -43,7 +43,7 @@ REF_PLAN = (32, 48, 64, 80, 96, 112)      # the reference's own sparse U-Net pla
 WORKLOADS = {      # name -> (channels, grid, active voxels per sample, boxes per scene, BASELINE.json entry, samples per rank)
     "cfg2": ((32, 64, 128, 256), (512, 512, 256), 150_000, 0, "configs[1]", 1),
     # cfg2 with BatchNormReLU in place of every ReLU of the residual units (north_star names the operator; the reference ships it
-    # off, run.py:612 `batchnorm=False`): the layer-by-layer path (the step executor does not cover batch norm), two more passes
+    # off, run.py:612 `batchnorm=False`): the layer-by-layer path by default (step-executor stages: `bn_stages=True`), two more passes
     # over every slab and direction; under DP each rank normalises with its own scene unless modules._BatchNorm.SYNC is set
     "cfg2-bn": ((32, 64, 128, 256), (512, 512, 256), 150_000, 0, "configs[1] with BatchNormReLU units (batchnorm=True)", 1),
     "cfg3": ((32, 64, 128, 256), (512, 512, 256), 150_000, 64, "configs[2]", 1),
@@ -92,8 +92,10 @@ class SparseStepModel(torch.nn.Module):
 
     def __init__(self, channels, with_mask, storage, with_rpn=False, n_boxes=64, batchnorm=False, with_class=False,
                  with_segmentation=False, upsample_heads=False, class_storage=None, simple_class=False, bottleneck_divisor=0,
-                 main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True):
-        """bottleneck_divisor, main_path_relu (0 / False: nothing changes): the form of the BACKBONE's residual units
+                 main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True, bn_stages=False):
+        """bn_stages (with batchnorm; False: nothing changes): the batch-norm backbone runs as step-executor stages
+        (unet.SparseUNet).
+        bottleneck_divisor, main_path_relu (0 / False: nothing changes): the form of the BACKBONE's residual units
         (unet.residual_block; the reference's switches of the same names, run.py:516-518).  The mask branch's own networks keep
         the plain unit: its level 0 runs on channel-padded slabs, which the other forms do not take.
         relu_first, drop_input_relu, use_residuals (True: nothing changes): the backbone's post-activation units, the ReLU of
@@ -119,7 +121,8 @@ class SparseStepModel(torch.nn.Module):
         self.backbone = Backbone(7, channels, batchnorm=batchnorm, bf16_blocks=storage,
                                  **(dict(bottleneck_divisor=bottleneck_divisor, main_path_relu=main_path_relu)
                                     if (bottleneck_divisor or main_path_relu) else {}),
-                                 **({} if all(stage_kw.values()) else stage_kw))
+                                 **({} if all(stage_kw.values()) else stage_kw),
+                                 **(dict(bn_stages=True) if bn_stages else {}))
         self.mask = MaskBranch(channels[0], 7, bf16_blocks=storage) if with_mask else None
         self.rpn = self.roi_selector = None
         self.rpn_levels = None                 # indices of the encoder levels the RPN reads
@@ -203,8 +206,12 @@ class SceneStep:
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rpn_loss=False, mask_loss=False, n_gt=None,
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
                  upsample_heads=False, class_storage=None, simple_class=False, multitask_loss=False, loss_weights=None,
-                 bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True):
-        """bottleneck_divisor, main_path_relu (0 / False: nothing changes): the backbone's residual units take the reference's
+                 bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True,
+                 bn_stages=False):
+        """bn_stages (a "-bn" workload; False: nothing changes): the batch-norm backbone runs as step-executor stages, one
+        autograd node per level (unet.SparseUNet; the developer switch SCN_EXEC_BN=1 does the same for a step built without
+        the keyword).  Same kernels, arguments and bits as the layer-by-layer path, which stays the default.
+        bottleneck_divisor, main_path_relu (0 / False: nothing changes): the backbone's residual units take the reference's
         bottleneck form (inner width C // bottleneck_divisor) and / or its main-path ReLU (unet.residual_block).  dtype="bf16"
         needs every inner width to be a multiple of 8 (ValueError otherwise).  The mask branch keeps the plain unit.
         relu_first, drop_input_relu, use_residuals (True: nothing changes): the backbone's post-activation units
@@ -407,6 +414,7 @@ class SceneStep:
         self.bottleneck_divisor, self.main_path_relu = int(bottleneck_divisor or 0), bool(main_path_relu)
         self.relu_first, self.drop_input_relu, self.use_residuals = bool(relu_first), bool(drop_input_relu), bool(use_residuals)
         stage_kw = dict(relu_first=self.relu_first, drop_input_relu=self.drop_input_relu, use_residuals=self.use_residuals)
+        self.bn_stages = bool(bn_stages)
         self.model = SparseStepModel(self.channels, bool(self.n_boxes), storage, rpn_kind, self.n_boxes,
                                      batchnorm=workload.endswith("-bn"),
                                      with_class="dense" if self.dense_class else self.class_loss,
@@ -416,7 +424,8 @@ class SceneStep:
                                      **(dict(simple_class=True) if self.simple_class else {}),
                                      **(dict(bottleneck_divisor=self.bottleneck_divisor, main_path_relu=self.main_path_relu)
                                         if (self.bottleneck_divisor or self.main_path_relu) else {}),
-                                     **({} if all(stage_kw.values()) else stage_kw)).to(self.device)
+                                     **({} if all(stage_kw.values()) else stage_kw),
+                                     **(dict(bn_stages=True) if self.bn_stages else {})).to(self.device)
         self.combiner = self.loss_record = None
         if self._loss_weights is not None:
             from .loss import LossCombiner
@@ -967,7 +976,8 @@ class SceneStep:
                  ([] if self.relu_first else ["relu_first=False: post-activation units, layer -> ReLU input stages"])
                  + ([] if self.drop_input_relu else ["drop_input_relu=False"])
                  + ([] if self.use_residuals else ["use_residuals=False: plain convolution blocks"])) + ")")
-             + (", BatchNormReLU in the residual units (training mode, fp64 statistics; layer-by-layer path)"
+             + ((", BatchNormReLU in the residual units (training mode, fp64 statistics; "
+                 + ("step-executor stages, one node per level)" if self.model.backbone.unet._bn_staged() else "layer-by-layer path)"))
                 if self.workload.endswith("-bn") else ""))
         if self.n_boxes and self.with_rpn:
             r = self.model.rpn

@@ -159,9 +159,12 @@ class SparseUNet(nn.Module):
 
     def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False,
                  identity_first=False, min_channels=0, bottleneck_divisor=0, main_path_relu=False, relu_first=True,
-                 drop_input_relu=True, use_residuals=True):
+                 drop_input_relu=True, use_residuals=True, bn_stages=False):
         """bottleneck_divisor, main_path_relu, relu_first, use_residuals: the form of every unit; relu_first and drop_input_relu:
-        the ReLU of the input stages (header comment; the defaults build what this class always built).  bf16_blocks="all" then also needs every unit's inner width C // bottleneck_divisor to be a
+        the ReLU of the input stages (header comment; the defaults build what this class always built).
+        bn_stages (with batchnorm=True; otherwise it changes nothing): the batch-norm network runs through the step executor, one
+        autograd node per level, as the ReLU networks do (executor.py; same kernels, same arguments, same bits as the
+        layer-by-layer path, which stays the default).  With bf16_blocks or on a channel-padded plan: ValueError.  bf16_blocks="all" then also needs every unit's inner width C // bottleneck_divisor to be a
         multiple of 8; bf16_blocks=True (the fused bf16 node of the plain unit) has no form for them: ValueError.
         identity_first: level 0 of the encoder is the reference's FLD('I') -- no layer at all, channels[0] == cin
         (the mask head's internal U-Net: scannet_config/run.py:756-775, I -> B32/2 -> B48/2 -> B64/2; the decoder's
@@ -172,6 +175,9 @@ class SparseUNet(nn.Module):
         16 channels: the mask network cut from the raw point features alone (7 channels in, 16 out)."""
         super().__init__()
         self.channels = tuple(channels)
+        self.batchnorm, self.bn_stages = bool(batchnorm), bool(bn_stages)
+        if self.bn_stages and self.batchnorm and bf16_blocks:
+            raise ValueError("bn_stages=True runs batch norm on fp32 slabs (batch norm widens bf16 rows): not with bf16_blocks")
         self.bottleneck_divisor, self.main_path_relu = int(bottleneck_divisor or 0), bool(main_path_relu)
         if self.bottleneck_divisor < 0:
             raise ValueError("bottleneck_divisor >= 0 required")
@@ -250,6 +256,9 @@ class SparseUNet(nn.Module):
                     if isinstance(m, M.SubmanifoldConvolution):
                         m.pad_out_to = self.phys0
             else:                                            # min_channels widened the decoder: only the skip slab is padded
+                if self.batchnorm and self.bn_stages:
+                    raise ValueError(f"bn_stages=True on a channel-padded plan (a level-0 width of {c0} runs on slabs zero-padded "
+                                     f"to {self.phys0} columns): batch-norm stages take no padded slab")
                 self.out_phys = self.out_channels
                 d0["nin"].in_groups = (self.out_channels, c0)
                 d0["nin"].in_phys = (self.out_channels, self.phys0)
@@ -316,7 +325,7 @@ class SparseUNet(nn.Module):
         return jobs
 
     _PLAN_ATTRS = ("_pack_aliases", "_pack_aliases_fwd", "_pad_plan", "_pad_requests", "_pack_plan", "_pack_plan_fwd",
-                   "_exec_plan_cache")
+                   "_exec_plan_cache", "_exec_plan_cache_bn")
 
     def __getstate__(self):
         """copy.deepcopy (EMA copies) / torch.save after a forward: the compiled launch plans hold ctypes pointer arrays and
@@ -370,24 +379,45 @@ class SparseUNet(nn.Module):
     # ---- step executor (executor.py): one autograd node and two C calls per LEVEL instead of one per layer -------------
     EXEC = True                 # class-wide switch (tests compare the two ways of driving the same kernels)
 
-    def _exec_plan(self):
-        """Launch plans of the levels, compiled once from the module tree; False when this network is not covered (batch
-        norm, bf16_blocks=True, a block that is none of the residual-unit forms, channel counts the two-source
-        NetworkInNetwork kernel does not take)."""
-        plan = self.__dict__.get("_exec_plan_cache")
-        if plan is not None:
-            return plan
+    def _bn_staged(self):
+        """Does this batch-norm network compile stage plans (`bn_stages=True`, or the developer switch SCN_EXEC_BN=1)?"""
         from . import executor as EX
+        d = self.__dict__                                    # (a network pickled before the switch existed has neither attribute)
+        return bool(d.get("batchnorm")) and (bool(d.get("bn_stages")) or EX.BN_STAGES)
+
+    def _exec_plan(self, training=None):
+        """Launch plans of the levels, compiled once from the module tree; False when this network is not covered (batch
+        norm without `bn_stages`, bf16_blocks=True, a block that is none of the residual-unit forms, channel counts the
+        two-source NetworkInNetwork kernel does not take).  A batch-norm network has one set of plans per mode -- training
+        (None: this module's): batch statistics and a statistics op per layer, or the running buffers and none."""
+        from . import executor as EX
+        bn = self._bn_staged()
+        if bn:
+            training = self.training if training is None else bool(training)
+            cache = self.__dict__.get("_exec_plan_cache_bn")
+            if cache is None:
+                cache = {}
+                object.__setattr__(self, "_exec_plan_cache_bn", cache)
+            if training in cache:
+                return cache[training]
+        else:
+            plan = self.__dict__.get("_exec_plan_cache")
+            if plan is not None:
+                return plan
         plan = False
         ch, L = self.channels, len(self.channels)
         ok = not self.bf16_blocks and all(c % 8 == 0 for c in ch[1:]) and (self.phys0 % 8 == 0)
         ok = ok and self.dec_channels == tuple(ch[:-1])      # (min_channels in effect: the layer-by-layer path)
-        enc_blocks = [EX._unit_blocks(lvl[1]) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
-        dec_blocks = [EX._unit_blocks(d["units"]) for d in self.decoder]
+        enc_blocks = [EX._unit_blocks(lvl[1], bn) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
+        dec_blocks = [EX._unit_blocks(d["units"], bn) for d in self.decoder]
         heads = [stage_layer(lvl[0]) for l, lvl in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
         ok = ok and EX._require_bias(*heads, *[stage_layer(d["up"]) for d in self.decoder], *[d["nin"] for d in self.decoder])
-        ok = ok and all(EX._stage_relus(lvl[0]) is not None for l, lvl in enumerate(self.encoder)
-                        if not (l == 0 and self.identity_first)) and all(EX._stage_relus(d["up"]) is not None for d in self.decoder)
+        ok = ok and all(EX._stage_relus(lvl[0], bn) is not None for l, lvl in enumerate(self.encoder)
+                        if not (l == 0 and self.identity_first)) and all(EX._stage_relus(d["up"], bn) is not None for d in self.decoder)
+        # batch norm: fp32 slabs exactly as wide as the layers; in a decoder level only behind the deconvolution
+        ok = ok and not (bn and (self.phys0 != ch[0] or self.bf16_all
+                                 or any(EX._bn_of(EX._stage_relus(d["up"], bn)[0]) is not None for d in self.decoder)))
+        mode = dict(bn_training=training) if bn else {}
         if ok and all(b is not None for b in enc_blocks + dec_blocks):
             bf16 = self.bf16_all
             phys = [self.phys0] + list(ch[1:])
@@ -398,15 +428,32 @@ class SparseUNet(nn.Module):
                     continue
                 head = stage_layer(self.encoder[l][0])
                 cin_phys = head.nIn if l == 0 else phys[l - 1]
-                enc.append(EX.compile_encoder_stage(l, head, enc_blocks[l], cin_phys, bf16, relus=EX._stage_relus(self.encoder[l][0])))
+                enc.append(EX.compile_encoder_stage(l, head, enc_blocks[l], cin_phys, bf16, relus=EX._stage_relus(self.encoder[l][0], bn),
+                                                    **mode))
             dec = []
             for i, d in enumerate(self.decoder):
                 l = L - 2 - i
                 dec.append(EX.compile_decoder_stage(l, stage_layer(d["up"]), d["nin"], dec_blocks[i], phys[l + 1], bf16,
-                                                    relus=EX._stage_relus(d["up"])))
+                                                    relus=EX._stage_relus(d["up"], bn), **mode))
             plan = dict(enc=enc, dec=dec)
-        object.__setattr__(self, "_exec_plan_cache", plan)
+        if bn:
+            cache[training] = plan
+        else:
+            object.__setattr__(self, "_exec_plan_cache", plan)
         return plan
+
+    def _bn_steps_aside(self):
+        """A staged batch-norm network takes the layer-by-layer path for this call: SyncBN with an initialised process group
+        (the all-reduce sits between the two kernels of a layer), activation masks being recorded (functional.RELU_RECORD), or
+        batch-norm layers that are not all in this module's own training / evaluation mode."""
+        from . import functional as F
+        if F.RELU_RECORD is not None:
+            return True
+        if M._BatchNorm.SYNC:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                return True
+        return any(m.training != self.training for m in self.modules() if isinstance(m, M._BatchNorm))
 
     def _forward_exec(self, x):
         """The forward through the step executor, or None when it does not apply to this call."""
@@ -416,6 +463,8 @@ class SparseUNet(nn.Module):
             return None
         f = x.features
         if not (f.is_cuda and f.dtype == torch.float32 and f.dim() == 2 and f.shape[0] > 0):
+            return None
+        if self.__dict__.get("batchnorm") and (not self._bn_staged() or self._bn_steps_aside()):
             return None
         plan = self._exec_plan()
         if not plan:
@@ -579,11 +628,12 @@ class Backbone(nn.Module):
     """InputLayer(mode 4) + SparseUNet: what model.py:414-431 runs for sparse + include_unet."""
 
     def __init__(self, cin=7, channels=(32, 64, 128, 256), num_units=2, batchnorm=False, bf16_blocks=False,
-                 bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True):
+                 bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True,
+                 bn_stages=False):
         super().__init__()
         self.unet = SparseUNet(cin, channels, num_units, batchnorm, bf16_blocks, bottleneck_divisor=bottleneck_divisor,
                                main_path_relu=main_path_relu, relu_first=relu_first, drop_input_relu=drop_input_relu,
-                               use_residuals=use_residuals)
+                               use_residuals=use_residuals, bn_stages=bn_stages)
 
     # How a forward without prepared metadata builds its index structures: False = step by step from Python (row-count
     # waits overlapped with kernel queueing: faster when nothing else can run meanwhile), True = one scn_pyramid_build
