@@ -12,13 +12,17 @@ One node per LEVEL rather than per network: the parameter gradients of a level l
 ends, so the bucketed gradient all-reduce of dp.py still overlaps with the rest of backward, skip connections stay ordinary
 autograd edges, and the encoder outputs (`SparseUNet.interims`, the RPN's inputs in the reference) stay differentiable.
 
-Units: the plain pre-activation residual unit, the reference's bottleneck / main-path-ReLU forms, its post-activation units
-(relu_first=False) and its plain convolution blocks (use_residuals=False) (`_unit_blocks`); input stages with the ReLU in front
-of the layer, behind it, or dropped (`_stage_relus`).  Batch-norm networks (`SparseUNet(batchnorm=True, bn_stages=True)`, or
-SCN_EXEC_BN=1): every one of those units and input stages with BatchNorm(Leaky)ReLU where the ReLU stood (`_bn_blocks`).  A
-batch-norm activation is never folded into the consuming convolution: it is SCN_OP_BN_STATS + SCN_OP_BN_FWD writing a slab
-of its own, SCN_OP_BN_BWD on the way back; its batch mean / variance live in the stage workspace and the host applies the
-running-statistics update after the forward call (`run_stage`), with the statements functional.BatchNormReLUFunction uses.
+Units: every unit of a level is ONE description (`Unit`: a skip around a short branch of activations and SubM convolutions,
+optionally closed by an activation), read off the module tree by ONE recogniser (`_units`) and compiled by ONE emitter pair
+(`Stage.units_fwd` / `units_bwd`, a walk over the branch's layers).  That covers the plain pre-activation residual unit, the
+reference's bottleneck / main-path-ReLU forms, its post-activation units (relu_first=False) and its plain convolution blocks
+(use_residuals=False); which of them a ReLU network may compile is `Unit.accepted`.  Input stages come with the activation in
+front of the layer, behind it, or dropped (`_stage_relus`; `Stage.act` / `act_bwd`).  Batch-norm networks
+(`SparseUNet(batchnorm=True, bn_stages=True)`, or SCN_EXEC_BN=1): the same units and input stages with BatchNorm(Leaky)ReLU
+where the ReLU stood.  A batch-norm activation is never folded into the consuming convolution: it is SCN_OP_BN_STATS +
+SCN_OP_BN_FWD writing a slab of its own, SCN_OP_BN_BWD on the way back; its batch mean / variance live in the stage workspace
+and the host applies the running-statistics update after the forward call (`run_stage`), with the statements
+functional.BatchNormReLUFunction uses.
 
 Not covered (the layer-by-layer path runs instead): batch norm without `bn_stages`, `bf16_blocks=True` (casts around every
 run of units), channel plans the two-source NetworkInNetwork kernel does not take, empty levels, and any step in which
@@ -34,6 +38,7 @@ import ctypes as C
 import os
 import struct
 import threading
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -180,6 +185,170 @@ def _levels_from_native(md, nat, n_levels):
 # ----------------------------------------------------------------------------------------------------------------------
 # plan compiler
 # ----------------------------------------------------------------------------------------------------------------------
+def _is_relu(m):
+    return type(m) is M.ReLU
+
+
+def _is_bn(m):
+    return isinstance(m, M._BatchNorm)
+
+
+def _is_subm(m):
+    return type(m) is M.SubmanifoldConvolution
+
+
+class Unit(NamedTuple):
+    """One unit of a level (unet.py header; module_factory.py:127-218): a skip around a short branch, optionally closed by an
+    activation.  Everything the plan compiler and its callers know about a unit is read from these fields."""
+    c: int                      # channels the unit takes and gives
+    skip: Optional[str]         # None: no skip (a plain block) | "res": x joins in the last convolution's epilogue |
+                                # "add": x joins after a branch that ends in its activation (post-activation)
+    layers: tuple               # the branch in order: ReLU, BatchNorm(Leaky)ReLU, SubmanifoldConvolution 1^3 | 3^3
+    closing: object = None      # the activation behind the join (a plain block: behind its convolution), or None
+
+    @property
+    def convs(self):
+        return [m for m in self.layers if _is_subm(m)]
+
+    @property
+    def has_bn(self):
+        return any(_is_bn(m) for m in (*self.layers, self.closing))
+
+    @property
+    def is_default(self):
+        """x + K2(ReLU(K1(ReLU(x)))), K 3^3: the pre-activation unit every network had before the other forms existed."""
+        return (self.skip == "res" and self.closing is None and len(self.layers) == 4 and _is_relu(self.layers[0])
+                and _is_relu(self.layers[2]) and len(self.convs) == 2 and all(m.filter_size == 3 for m in self.convs))
+
+    @property
+    def tree_form(self):
+        """A form the stages of a module tree somebody else built take (modules.py): the default unit, the post-activation
+        units and the plain blocks.  The bottleneck / main-path-ReLU units stay layer by layer there."""
+        return self.is_default or self.skip != "res"
+
+    def _width_behind(self):
+        """Channels behind the branch when c go in; None when a layer does not take what the one before it gives."""
+        w = self.c
+        for m in self.layers:
+            if _is_bn(m) and int(m.nPlanes) != w:
+                return None
+            if _is_subm(m):
+                if m.nIn != w:
+                    return None
+                w = m.nOut
+        return w
+
+    def accepted(self):
+        """May a plan be compiled for this unit?  The rules, one place each; a unit that fails one keeps the layer-by-layer path."""
+        convs, closing = self.convs, self.closing
+        if self._width_behind() != self.c or any(m.filter_size not in (1, 3) or m.groups != 1 for m in convs):
+            return False
+        if not (closing is None or _is_relu(closing) or (_is_bn(closing) and int(closing.nPlanes) == self.c)):
+            return False
+        if self.has_bn:
+            # batch norm wherever an activation stands (no ReLU left over), at least once inside the branch; any 1^3 / 3^3 chain
+            # that returns to c, its convolutions with or without bias, none of them channel-padded
+            return (all(_is_bn(m) or _is_subm(m) for m in self.layers) and any(map(_is_bn, self.layers)) and not _is_relu(closing)
+                    and not any(m.pad_out_to for m in convs))
+        # ReLU networks: the branch is K (ReLU K)* with exactly ONE more ReLU -- in front of it, behind it ("add") or closing the unit
+        lead, tail = _is_relu(self.layers[0]), _is_relu(self.layers[-1])
+        inner = self.layers[lead:len(self.layers) - tail]
+        if not (all(_is_relu(m) or _is_subm(m) for m in self.layers) and len(inner) == 2 * len(convs) - 1
+                and all(map(_is_subm, inner[0::2])) and lead + tail + (closing is not None) == 1 and tail == (self.skip == "add")):
+            return False
+        # branch shapes (3, 3) and (1, 3, 1), a plain block one 3^3 layer; a 3^3 layer keeps its width; every layer with bias
+        sizes = tuple(m.filter_size for m in convs)
+        if sizes not in (((3,),) if self.skip is None else ((3, 3), (1, 3, 1))):
+            return False
+        if any(m.bias is None or (m.filter_size == 3 and m.nIn != m.nOut) for m in convs):
+            return False
+        # channel padding: only the default unit (the mask head's level 0 runs it on zero-padded slabs)
+        return self.is_default or not any(m.pad_out_to for m in convs)
+
+
+def _width_in(layers):
+    """Channels the first layer of a branch takes (a ReLU takes any); None: it holds no batch-norm or SubM layer to say so."""
+    m = next((m for m in layers if not _is_relu(m)), None)
+    return int(m.nPlanes) if _is_bn(m) else (m.nIn if _is_subm(m) else None)
+
+
+def _units(unit_seq, bn=False):
+    """The units of a level as [Unit], or None when one of them is no form a plan is compiled for (`Unit.accepted`).
+    unit_seq: a Sequential (or list) of residual units  Sequential(ConcatTable(Identity, Sequential(branch)), AddTable [, act]),
+    or use_residuals=False's flat run  [act, K] * n | [K, act] * n  (module_factory.py:186-218).  A flat ReLU run is cut into
+    one plain block per convolution; a flat batch-norm run stays one unit (its widths need only return to c at its end).
+    bn: batch norm may stand wherever a ReLU may -- then in every unit; without it a batch-norm layer is no form at all."""
+    mods = list(unit_seq._modules.values()) if isinstance(unit_seq, torch.nn.Sequential) else list(unit_seq)
+    units = []
+    if mods and all(_is_relu(m) or _is_bn(m) or _is_subm(m) for m in mods):
+        is_act = [not _is_subm(m) for m in mods]
+        if len(mods) % 2 or is_act != [is_act[0], not is_act[0]] * (len(mods) // 2):
+            return None
+        if any(map(_is_bn, mods)):
+            units.append(Unit(_width_in(mods), None, tuple(mods)))
+        elif is_act[0]:
+            units += [Unit(k.nIn, None, (a, k)) for a, k in zip(mods[0::2], mods[1::2])]
+        else:
+            units += [Unit(k.nIn, None, (k,), a) for k, a in zip(mods[0::2], mods[1::2])]
+        mods = []
+    for block in mods:
+        if not (type(block) is M.Sequential and len(block) in (2, 3) and type(block[0]) is M.ConcatTable
+                and type(block[1]) is M.AddTable and len(block[0]._modules) == 2):
+            return None
+        a, inner = block[0]._modules.values()
+        if type(a) is not M.Identity or type(inner) is not M.Sequential:
+            return None
+        branch = tuple(inner._modules.values())
+        if _width_in(branch) is None:
+            return None
+        units.append(Unit(_width_in(branch), "res" if _is_subm(branch[-1]) else "add", branch, block[2] if len(block) == 3 else None))
+    with_bn = [u.has_bn for u in units]
+    if (any(with_bn) and not (bn and all(with_bn))) or not all(u.accepted() for u in units):
+        return None
+    return units
+
+
+class _Conv(NamedTuple):
+    """What the backward walk needs of a branch convolution: its module index, filter size, widths, input slab, whether a ReLU
+    sits in its gather, whether it has a bias."""
+    mi: int
+    k: int
+    cin: int
+    cout: int
+    x: int
+    relu_in: bool
+    has_b: bool
+
+
+class _Relu(NamedTuple):
+    """A ReLU with an op of its own: slab x holds the mask of its backward (hb: XF_BF16 when that slab is bf16-stored)."""
+    level: int
+    c: int
+    x: int
+    hb: int
+
+
+class _BN(NamedTuple):
+    """A batch-norm layer: input slab x, [mean | var] vector mv (training), gamma's params id gp, eps / leakiness as ExecOp bits."""
+    level: int
+    c: int
+    mi: int
+    x: int
+    mv: int
+    gp: int
+    eps: int
+    leak: int
+    fl: int
+
+
+class _UnitRec(NamedTuple):
+    """A compiled unit: its description, its input slab, one record per branch layer that has an op, the closing activation's."""
+    unit: Unit
+    x: int
+    tape: list
+    closing: object
+
+
 class Stage:
     """The launch plan of one autograd node: forward and backward op lists over symbolic buffer / parameter / gradient ids."""
 
@@ -229,149 +398,14 @@ class Stage:
     def op(self, lst, op, level, cin, cout, x=-1, y=-1, r=-1, m=-1, x1=-1, y1=-1, c1=0, w=-1, b=-1, aux=0, flags=0):
         lst.append(ExecOp(op, flags, level, cin, cout, x, y, r, m, x1, y1, c1, w, b, aux, 0))
 
-    # ---- residual units ----------------------------------------------------------------------------------------------
-    def units_fwd(self, level, c, x, blocks, out_id=None):
-        """blocks (`_unit_blocks`): (conv1, conv2) of x + SubM3(ReLU(SubM3(ReLU(x)))) at `c` physical channels, or a tagged tuple of
-        one of the other unit forms (`_form_fwd`).  -> (output id, saved)"""
-        saved = []
-        for k, blk in enumerate(blocks):
-            if isinstance(blk[0], str):                      # a bottleneck / main-path-ReLU unit (_unit_blocks)
-                y = out_id if (out_id is not None and k == len(blocks) - 1) else self.buf(level, c)
-                saved.append((self._bn_fwd if blk[0] == "bn" else self._form_fwd)(level, c, x, y, blk))
-                x = y
-                continue
-            c1, c2 = blk
-            m1, m2 = self.mod(c1, c), self.mod(c2, c)
-            y1 = self.buf(level, c)
-            y = out_id if (out_id is not None and k == len(blocks) - 1) else self.buf(level, c)
-            fl = L.F_RELU_IN | self.hb
-            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=x, y=y1, w=self.weight(m1, c, c, 27, 0, True), b=self.param("b", m1), flags=fl)
-            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=y1, y=y, r=x, w=self.weight(m2, c, c, 27, 0, True), b=self.param("b", m2), flags=fl)
-            saved.append((x, y1, m1, m2))
-            x = y
-        return x, saved
-
-    def units_bwd(self, level, c, g, saved, din_id=None):
-        """Backward of units_fwd: g = gradient of the last block's output -> id of the gradient of the first block's input."""
-        for k, sv in enumerate(reversed(saved)):
-            if isinstance(sv[0], str):
-                dx = din_id if (din_id is not None and k == len(saved) - 1) else self.buf(level, c, kind="b")
-                (self._bn_bwd if sv[0] == "bn" else self._form_bwd)(level, c, g, dx, sv)
-                g = dx
-                continue
-            x, y1, m1, m2 = sv
-            dy1 = self.buf(level, c, kind="b")
-            dx = din_id if (din_id is not None and k == len(saved) - 1) else self.buf(level, c, kind="b")
-            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dy1, m=y1, w=self.weight(m2, c, c, 27, BACK, True), flags=BACK | self.hb)
-            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=dy1, y=dx, m=x, r=g, w=self.weight(m1, c, c, 27, BACK, True),
-                    flags=BACK | L.F_RESIDUAL_LAST | self.hb)
-            gw, gb = self.gregion((m1, "w"), (m2, "w")), self.gregion((m1, "b"), (m2, "b"))
-            self.op(self.bwd, OP_WGRAD2_SUBM, level, c, c, x=x, y=dy1, x1=y1, y1=g, w=gw, b=gb, flags=L.F_RELU_IN | self.hb)
-            g = dx
-        return g
-
-    # ---- the reference's other unit forms (unet.py header; module_factory.py:127-183) ----------------------------------------
-    # Each op is the call the layer-by-layer path makes for that layer (modules.Sequential: ReLU fused into the next
-    # convolution's gather, the AddTable into the last convolution's epilogue).  Backward, the two gradient paths of x meet in
-    # an SCN_OP_ADD -- layer by layer autograd adds them -- because the row GEMM has no "residual after the mask" epilogue and
-    # a bf16 slab must be rounded before the add to give autograd's bits.  The closing ReLU of a main-path unit is one
-    # SCN_OP_RELU in place on the unit's result; its backward masks by that result (y > 0 exactly where the sum was).
-    #
-    # Post-activation units (relu_first=False, "post" / "post_bottleneck"): y = x + act(t), t the branch's last convolution.  No
-    # activation on the way in, no residual in the last convolution's epilogue; ONE SCN_OP_ADD_RELU ends the unit and leaves t
-    # as it is, which is the mask of the backward's SCN_OP_RELU_BWD.  The skip's gradient is dy itself, the branch's is masked.
-    # Plain blocks (use_residuals=False): "plain_pre" = K(ReLU(x)), the ReLU in the gather; "plain_post" = ReLU(K(x)), the ReLU
-    # one in-place SCN_OP_RELU on the block's result, its backward masked by that result.
-    def _form_fwd(self, level, c, x, y, blk):
-        hb, relu = self.hb, L.F_RELU_IN | self.hb
-        form, main = blk[0], blk[0] in ("main", "both")
-        post = form in ("post", "post_bottleneck")
-        if form in ("plain_pre", "plain_post"):
-            m1 = self.mod(blk[1], c)
-            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=x, y=y, w=self.weight(m1, c, c, 27, 0, True), b=self.param("b", m1),
-                    flags=relu if form == "plain_pre" else hb)
-            if form == "plain_post":
-                self.op(self.fwd, OP_RELU, level, c, 0, x=y, y=y, flags=hb)
-            return (form, x, y, m1)
-        first = hb if (main or post) else relu              # main_path_relu / post-activation: no activation on the way in
-        t = self.buf(level, c) if post else y               # post-activation: the branch's result, kept for the backward mask
-        r = -1 if post else x
-        if form in ("main", "post"):
-            _, c1, c2 = blk
-            m1, m2 = self.mod(c1, c), self.mod(c2, c)
-            y1 = self.buf(level, c)
-            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=x, y=y1, w=self.weight(m1, c, c, 27, 0, True), b=self.param("b", m1), flags=first)
-            self.op(self.fwd, OP_CONV_SUBM, level, c, c, x=y1, y=t, r=r, w=self.weight(m2, c, c, 27, 0, True), b=self.param("b", m2), flags=relu)
-            sv = (form, x, y, y1, m1, m2)
-        else:
-            _, n1, kk, n2 = blk
-            ci = n1.nOut
-            m1, mk, m2 = self.mod(n1, c), self.mod(kk, ci), self.mod(n2, ci)
-            a, b = self.buf(level, ci), self.buf(level, ci)
-            self.op(self.fwd, OP_GEMM_IDENT, level, c, ci, x=x, y=a, w=self.param("w", m1), b=self.param("b", m1), flags=first)
-            self.op(self.fwd, OP_CONV_SUBM, level, ci, ci, x=a, y=b, w=self.weight(mk, ci, ci, 27, 0, True), b=self.param("b", mk), flags=relu)
-            self.op(self.fwd, OP_GEMM_IDENT, level, ci, c, x=b, y=t, r=r, w=self.param("w", m2), b=self.param("b", m2), flags=relu)
-            sv = (form, x, y, a, b, ci, m1, mk, m2)
-        if main:
-            self.op(self.fwd, OP_RELU, level, c, 0, x=y, y=y, flags=hb)
-        if post:
-            self.op(self.fwd, OP_ADD_RELU, level, c, 0, x=x, x1=t, y=y, flags=hb)
-            sv = sv + (t,)
-        return sv
-
-    def _form_bwd(self, level, c, g, dx, sv):
-        hb, relu = self.hb, L.F_RELU_IN | self.hb
-        form, x, y = sv[:3]
-        if form in ("plain_pre", "plain_post"):
-            m1 = sv[3]
-            if form == "plain_post":
-                gs = self.buf(level, c, kind="b")
-                self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=y, x1=g, y=gs, flags=hb)
-                g = gs
-            pre = form == "plain_pre"
-            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dx, m=x if pre else -1, w=self.weight(m1, c, c, 27, BACK, True),
-                    flags=BACK | hb)
-            self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=x, y=g, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")),
-                    flags=relu if pre else hb)
-            return
-        main = form in ("main", "both")
-        post = form in ("post", "post_bottleneck")
-        first = hb if (main or post) else relu
-        g_skip = g                                          # what the skip hands back to x
-        if main:
-            gs = self.buf(level, c, kind="b")
-            self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=y, x1=g, y=gs, flags=hb)
-            g = g_skip = gs
-        if post:                                            # only the branch passes the closing activation
-            gs = self.buf(level, c, kind="b")
-            self.op(self.bwd, OP_RELU_BWD, level, c, 0, m=sv[-1], x1=g, y=gs, flags=hb)
-            g, sv = gs, sv[:-1]
-        t = self.buf(level, c, kind="b")                    # the branch's gradient of x, before the skip's is added
-        if form in ("main", "post"):
-            y1, m1, m2 = sv[3:]
-            dy1 = self.buf(level, c, kind="b")
-            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dy1, m=y1, w=self.weight(m2, c, c, 27, BACK, True), flags=BACK | hb)
-            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=dy1, y=t, w=self.weight(m1, c, c, 27, BACK, True), flags=BACK | hb)
-            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g_skip, y=dx, flags=hb)
-            self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=y1, y=g, w=self.gregion((m2, "w")), b=self.gregion((m2, "b")), flags=relu)
-            self.op(self.bwd, OP_WGRAD_SUBM, level, c, c, x=x, y=dy1, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
-            return
-        a, b, ci, m1, mk, m2 = sv[3:]
-        db, da = self.buf(level, ci, kind="b"), self.buf(level, ci, kind="b")
-        self.op(self.bwd, OP_GEMM_IDENT, level, c, ci, x=g, y=db, m=b, w=self.param("w", m2), flags=BACK | hb)
-        self.op(self.bwd, OP_CONV_SUBM, level, ci, ci, x=db, y=da, m=a, w=self.weight(mk, ci, ci, 27, BACK, True), flags=BACK | hb)
-        self.op(self.bwd, OP_GEMM_IDENT, level, ci, c, x=da, y=t, m=-1 if (main or post) else x, w=self.param("w", m1), flags=BACK | hb)
-        self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g_skip, y=dx, flags=hb)
-        self.op(self.bwd, OP_WGRAD_IDENT, level, ci, c, x=b, y=g, w=self.gregion((m2, "w")), b=self.gregion((m2, "b")), flags=relu)
-        self.op(self.bwd, OP_WGRAD_SUBM, level, ci, ci, x=a, y=db, w=self.gregion((mk, "w")), b=self.gregion((mk, "b")), flags=relu)
-        self.op(self.bwd, OP_WGRAD_IDENT, level, c, ci, x=x, y=da, w=self.gregion((m1, "w")), b=self.gregion((m1, "b")), flags=first)
-
-    # ---- batch-norm activations and units (bn_stages) ---------------------------------------------------------------------
-    # A BatchNorm(Leaky)ReLU layer is SCN_OP_BN_STATS (training mode: batch mean | biased variance -> ONE 2c-float vector of the
-    # stage workspace) + SCN_OP_BN_FWD reading slab x and writing a slab y of its own -- never a flag of the consuming
-    # convolution --, and SCN_OP_BN_BWD (x, dy -> dx and dgamma | dbeta in ONE gradient region) on the way back: scn_bn_stats /
-    # scn_bn_fwd / scn_bn_bwd with the arguments functional.BatchNormReLUFunction passes.  gamma and beta sit next to each other
-    # in the params table (`w` names gamma); evaluation mode: the running buffers follow them, no statistics op is planned.
+    # ---- free-standing activations ---------------------------------------------------------------------------------------
+    # An activation no convolution's gather absorbs: behind the head of a level, closing a unit or a plain block.  A ReLU is one
+    # SCN_OP_RELU in place; its backward (SCN_OP_RELU_BWD) masks by that slab -- y > 0 exactly where the ReLU's input was.  A
+    # BatchNorm(Leaky)ReLU layer is SCN_OP_BN_STATS (training mode: batch mean | biased variance -> ONE 2c-float vector of the
+    # stage workspace) + SCN_OP_BN_FWD reading slab x and writing a slab of its own, and SCN_OP_BN_BWD (x, dy -> dx and
+    # dgamma | dbeta in ONE gradient region) on the way back: scn_bn_stats / scn_bn_fwd / scn_bn_bwd with the arguments
+    # functional.BatchNormReLUFunction passes.  gamma and beta sit next to each other in the params table (`w` names gamma);
+    # evaluation mode: the running buffers follow them, no statistics op is planned.
     def bn_layer(self, level, m, x, y):
         c = int(m.nPlanes)
         mi = self.mod(m, c)
@@ -389,73 +423,145 @@ class Stage:
             self.param("rv", mi)
         eps, leak = _f32_bits(m.eps), _f32_bits(m.leakiness)
         self.op(self.fwd, OP_BN_FWD, level, c, 0, x=x, y=y, x1=mv, w=gp, aux=eps, c1=leak, flags=fl)
-        return (level, c, mi, x, mv, gp, eps, leak, fl)
+        return _BN(level, c, mi, x, mv, gp, eps, leak, fl)
 
-    def bn_layer_bwd(self, rec, g, dx):
-        level, c, mi, x, mv, gp, eps, leak, fl = rec
-        self.op(self.bwd, OP_BN_BWD, level, c, 0, x=x, m=g, y=dx, x1=mv, w=gp, b=self.gregion((mi, "w"), (mi, "b")), aux=eps,
-                c1=leak, flags=fl)
+    def act(self, level, c, m, x, out=None, fp32=False):
+        """The free-standing activation m on slab x -> (slab that holds the result, record for `act_bwd`).  A ReLU works in place
+        (x must be `out` where one is asked for); batch norm writes `out`, or a slab of its own.
+        fp32: x is an fp32 slab whatever the plan's storage is (the level-0 head of a bf16 network runs in fp32)."""
+        if _is_bn(m):
+            y = self.buf(level, c, 4) if out is None else out
+            return y, self.bn_layer(level, m, x, y)
+        hb = 0 if fp32 else self.hb
+        self.op(self.fwd, OP_RELU, level, c, 0, x=x, y=x, flags=hb)
+        return x, _Relu(level, c, x, hb)
 
-    def _chain_conv(self, level, m, cin, x, y, r=-1):
-        """A SubM 3^3 / 1^3 layer of a batch-norm unit: no activation in its gather, its bias (None beside batch norm) as it is."""
-        mi, cout = self.mod(m, cin), int(m.nOut)
-        b = self.param("b", mi) if m.bias is not None else -1
-        if m.filter_size == 3:
-            self.op(self.fwd, OP_CONV_SUBM, level, cin, cout, x=x, y=y, r=r, w=self.weight(mi, cin, cout, 27, 0, True), b=b, flags=self.hb)
+    def act_bwd(self, rec, g, dx=None):
+        """Backward of `act` (and of the ReLU that ends a post-activation branch): gradient slab g -> dx, or a slab of its own."""
+        hb = 0 if isinstance(rec, _BN) else rec.hb
+        if dx is None:
+            dx = self.buf(rec.level, rec.c, 2 if hb else 4, "b")
+        if isinstance(rec, _BN):
+            self.op(self.bwd, OP_BN_BWD, rec.level, rec.c, 0, x=rec.x, m=g, y=dx, x1=rec.mv, w=rec.gp,
+                    b=self.gregion((rec.mi, "w"), (rec.mi, "b")), aux=rec.eps, c1=rec.leak, flags=rec.fl)
         else:
-            self.op(self.fwd, OP_GEMM_IDENT, level, cin, cout, x=x, y=y, r=r, w=self.param("w", mi), b=b, flags=self.hb)
-        return (mi, m.filter_size, cin, cout, x, m.bias is not None)
+            self.op(self.bwd, OP_RELU_BWD, rec.level, rec.c, 0, m=rec.x, x1=g, y=dx, flags=hb)
+        return dx
 
-    def _chain_conv_bwd(self, level, rec, g, dx):
-        mi, k, cin, cout, x, has_b = rec
-        if k == 3:
-            self.op(self.bwd, OP_CONV_SUBM, level, cout, cin, x=g, y=dx, w=self.weight(mi, cout, cin, 27, BACK, True), flags=BACK | self.hb)
-        else:
-            self.op(self.bwd, OP_GEMM_IDENT, level, cout, cin, x=g, y=dx, w=self.param("w", mi), flags=BACK | self.hb)
-        gw = self.gregion((mi, "w"))
-        gb = self.gregion((mi, "b")) if has_b else -1      # (no bias: scn_wgrad_rules, as the layer's own backward)
-        self.op(self.bwd, OP_WGRAD_SUBM if k == 3 else OP_WGRAD_IDENT, level, cin, cout, x=x, y=g, w=gw, b=gb, flags=self.hb)
+    # ---- units -----------------------------------------------------------------------------------------------------------
+    # A unit (`Unit`) compiles by one walk over its branch, forward, and one over the records of that walk, in reverse.  Each op
+    # is the call the layer-by-layer path makes for that layer (modules.Sequential), so both paths give the same bits:
+    #   ReLU directly in front of a convolution   F_RELU_IN on that convolution -- no slab, no op.  The backward-data op masks by
+    #                                             the convolution's input slab (m=), the weight gradient carries F_RELU_IN.
+    #   BatchNorm(Leaky)ReLU                      `bn_layer`, a slab of its own, never a flag of the consuming convolution.
+    #   last convolution, skip "res"              x joins in its epilogue (r=x).
+    #   activation that ends a branch, skip "add" y = x + act(t): a ReLU is ONE SCN_OP_ADD_RELU that leaves the branch slab t as
+    #                                             it is -- the mask of the backward; batch norm writes a slab, SCN_OP_ADD joins.
+    #   closing activation                        `act` on the unit's result.
+    # Backward, the two gradient paths of x meet in an SCN_OP_ADD -- layer by layer autograd adds them -- because the row GEMM has
+    # no "residual after the mask" epilogue and a bf16 slab must be rounded before the add to give autograd's bits.  The default
+    # pre-activation unit alone does without it (`_unit_bwd`).
+    def units_fwd(self, level, c, x, units, out_id=None):
+        """units (`_units`) at `c` physical channels on slab x; the last one writes `out_id` when given.  -> (output id, records)"""
+        saved = []
+        for k, u in enumerate(units):
+            x, rec = self._unit_fwd(level, c, x, out_id if k == len(units) - 1 else None, u)
+            saved.append(rec)
+        return x, saved
 
-    def _bn_fwd(self, level, c, x, y, blk):
-        """A unit of `_bn_blocks`: the branch layer by layer, every layer writing a slab of its own.  skip "res": x joins in the
-        last convolution's epilogue (modules.Sequential hands it the residual); "add": one SCN_OP_ADD behind a branch that ends
-        in its activation (post-activation); None: a flat run of plain blocks.  closing: the activation of a main-path unit."""
-        _, _, skip, mods, closing = blk
-        end = y if closing is None else self.buf(level, c)
-        t, w, tape = x, c, []
-        for i, m in enumerate(mods):
-            last = i == len(mods) - 1
-            bn = isinstance(m, M._BatchNorm)
-            cout = int(m.nPlanes) if bn else int(m.nOut)
-            dst = end if (last and skip != "add") else self.buf(level, cout)
-            if bn:
-                tape.append(("a", self.bn_layer(level, m, t, dst)))
+    def units_bwd(self, level, c, g, saved, din_id=None):
+        """Backward of units_fwd: g = gradient of the last unit's output -> id of the gradient of the first unit's input."""
+        for k, rec in enumerate(reversed(saved)):
+            g = self._unit_bwd(level, c, g, din_id if k == len(saved) - 1 else None, rec)
+        return g
+
+    # (out / dx = None: a slab of the unit's own, asked for where the walk first writes it -- the symbol order plans always had)
+    def _unit_fwd(self, level, c, x, out, u):
+        def joined():                   # what the join writes: the unit's result, or what a closing batch norm reads
+            return self.buf(level, c) if (out is None or _is_bn(u.closing)) else out
+
+        t, w, relu_in, tape = x, c, False, []
+        for i, m in enumerate(u.layers):
+            last = i == len(u.layers) - 1
+            if _is_relu(m) and not last:
+                relu_in = True
+                continue
+            if _is_relu(m):
+                end = joined()
+                self.op(self.fwd, OP_ADD_RELU, level, c, 0, x=x, x1=t, y=end, flags=self.hb)
+                tape.append(_Relu(level, c, t, self.hb))
+                t = end
+                break
+            cout = w if _is_bn(m) else _phys(m)
+            dst = joined() if (last and u.skip != "add") else self.buf(level, cout)
+            if _is_bn(m):
+                tape.append(self.bn_layer(level, m, t, dst))
             else:
-                tape.append(("k", self._chain_conv(level, m, w, t, dst, r=x if (last and skip == "res") else -1)))
-            t, w = dst, cout
-        if skip == "add":
+                mi = self.mod(m, w)
+                wp = self.weight(mi, w, cout, 27, 0, True) if m.filter_size == 3 else self.param("w", mi)
+                b = self.param("b", mi) if m.bias is not None else -1       # (None beside batch norm)
+                self.op(self.fwd, OP_CONV_SUBM if m.filter_size == 3 else OP_GEMM_IDENT, level, w, cout, x=t, y=dst,
+                        r=x if (last and u.skip == "res") else -1, w=wp, b=b, flags=(L.F_RELU_IN if relu_in else 0) | self.hb)
+                tape.append(_Conv(mi, m.filter_size, w, cout, t, relu_in, m.bias is not None))
+            t, w, relu_in = dst, cout, False
+        if u.skip == "add" and _is_bn(u.layers[-1]):
+            end = joined()
             self.op(self.fwd, OP_ADD, level, c, 0, x=x, x1=t, y=end, flags=self.hb)
-        crec = self.bn_layer(level, closing, end, y) if closing is not None else None
-        return ("bn", skip, tape, crec)
+            t = end
+        closing = None
+        if u.closing is not None:
+            t, closing = self.act(level, c, u.closing, t, out=out)
+        return t, _UnitRec(u, x, tape, closing)
 
-    def _bn_bwd(self, level, c, g, dx, sv):
-        _, skip, tape, crec = sv
-        if crec is not None:
-            gs = self.buf(level, c, kind="b")
-            self.bn_layer_bwd(crec, g, gs)
-            g = gs
-        t = g
+    def _unit_bwd(self, level, c, g, dx, rec):
+        u, x, tape, hb = rec.unit, rec.x, rec.tape, self.hb
+        if u.is_default:
+            # The benchmarked unit keeps two fusions the general walk has no place for: the skip's gradient enters through the
+            # first convolution's backward-data epilogue (F_RESIDUAL_LAST: fp32 accumulators, one rounding -- no SCN_OP_ADD), and
+            # both weight gradients leave as ONE SCN_OP_WGRAD2_SUBM whose weight and bias regions hold the pair.
+            k1, k2 = tape
+            dy1 = self.buf(level, c, kind="b")
+            dx = self.buf(level, c, kind="b") if dx is None else dx
+            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=g, y=dy1, m=k2.x, w=self.weight(k2.mi, c, c, 27, BACK, True), flags=BACK | hb)
+            self.op(self.bwd, OP_CONV_SUBM, level, c, c, x=dy1, y=dx, m=x, r=g, w=self.weight(k1.mi, c, c, 27, BACK, True),
+                    flags=BACK | L.F_RESIDUAL_LAST | hb)
+            gw, gb = self.gregion((k1.mi, "w"), (k2.mi, "w")), self.gregion((k1.mi, "b"), (k2.mi, "b"))
+            self.op(self.bwd, OP_WGRAD2_SUBM, level, c, c, x=x, y=dy1, x1=k2.x, y1=g, w=gw, b=gb, flags=L.F_RELU_IN | hb)
+            return dx
+        if rec.closing is not None:
+            g = self.act_bwd(rec.closing, g)
+        # parameter-gradient ops: a batch-norm unit queues each right behind its backward-data op, a ReLU unit behind the unit's
+        # data chain and add (the orders the two kinds of unit always had; the grouped weight-gradient launch sees them as queued)
+        t, leaves = g, []
         for i in range(len(tape) - 1, -1, -1):
-            kind, rec = tape[i]
-            cin = rec[1] if kind == "a" else rec[2]
-            dst = dx if (i == 0 and skip is None) else self.buf(level, cin, kind="b")
-            if kind == "a":
-                self.bn_layer_bwd(rec, t, dst)
+            r = tape[i]
+            dst = dx if (i == 0 and u.skip is None) else None      # (None: a slab of the op's own)
+            if not isinstance(r, _Conv):
+                t = self.act_bwd(r, t, dst)
+                continue
+            if dst is None:
+                dst = self.buf(level, r.cin, kind="b")
+            wp = self.weight(r.mi, r.cout, r.cin, 27, BACK, True) if r.k == 3 else self.param("w", r.mi)
+            self.op(self.bwd, OP_CONV_SUBM if r.k == 3 else OP_GEMM_IDENT, level, r.cout, r.cin, x=t, y=dst,
+                    m=r.x if r.relu_in else -1, w=wp, flags=BACK | hb)
+            if u.has_bn:
+                self._conv_wgrad(level, r, t)
             else:
-                self._chain_conv_bwd(level, rec, t, dst)
+                leaves.append((r, t))
             t = dst
-        if skip is not None:                                # the two gradient paths of x: layer by layer autograd adds them
-            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=self.hb)
+        if u.skip is not None:                              # the two gradient paths of x
+            dx = self.buf(level, c, kind="b") if dx is None else dx
+            self.op(self.bwd, OP_ADD, level, c, 0, x=t, x1=g, y=dx, flags=hb)
+            t = dx
+        for leaf in leaves:
+            self._conv_wgrad(level, *leaf)
+        return t
+
+    def _conv_wgrad(self, level, r, g):
+        gw = self.gregion((r.mi, "w"))
+        gb = self.gregion((r.mi, "b")) if r.has_b else -1    # (no bias: scn_wgrad_rules, as the layer's own backward)
+        self.op(self.bwd, OP_WGRAD_SUBM if r.k == 3 else OP_WGRAD_IDENT, level, r.cin, r.cout, x=r.x, y=g, w=gw, b=gb,
+                flags=(L.F_RELU_IN if r.relu_in else 0) | self.hb)
 
     # ---- finish -----------------------------------------------------------------------------------------------------
     def freeze(self):
@@ -545,190 +651,43 @@ def _lean_layout(stage, ns):
     return [base[cls][0] + k * base[cls][1] for cls, k in stage.lean_slot_of], tot
 
 
-def _plain_blocks(unit_seq):
-    """[(conv1, conv2)] of a `units(...)` Sequential, or None when a block is not the plain pre-activation unit."""
-    out = []
-    for block in unit_seq:
-        if not (type(block) is M.Sequential and len(block) == 2 and type(block[0]) is M.ConcatTable and type(block[1]) is M.AddTable):
-            return None
-        a, inner = list(block[0]._modules.values()) if len(block[0]._modules) == 2 else (None, None)
-        if type(a) is not M.Identity or type(inner) is not M.Sequential or len(inner) != 4:
-            return None
-        r0, c1, r1, c2 = list(inner._modules.values())
-        if not (type(r0) is M.ReLU and type(r1) is M.ReLU and type(c1) is M.SubmanifoldConvolution
-                and type(c2) is M.SubmanifoldConvolution and c1.filter_size == 3 and c2.filter_size == 3
-                and c1.bias is not None and c2.bias is not None and c1.nIn == c2.nOut and c1.nOut == c2.nIn == c1.nIn
-                and c1.groups == 1 and c2.groups == 1):
-            return None
-        out.append((c1, c2))
-    return out
-
-
-def _bn_chain(mods, c):
-    """Channels behind a run of BatchNorm(Leaky)ReLU / SubM 3^3 / SubM 1^3 layers that starts at c channels; None: not such a run."""
-    for m in mods:
-        if isinstance(m, M._BatchNorm):
-            if int(m.nPlanes) != c:
-                return None
-        elif (type(m) is M.SubmanifoldConvolution and m.filter_size in (1, 3) and m.groups == 1 and not m.pad_out_to
-                and m.nIn == c):
-            c = m.nOut
-        else:
-            return None
-    return c
-
-
-def _bn_blocks(unit_seq):
-    """`_unit_blocks` of a batch-norm network: every unit form of unet.residual_block / plain_blocks with BatchNorm(Leaky)ReLU where
-    the ReLU stands, as ("bn", channels, skip, branch layers, closing activation | None) -- skip "res": the branch ends in a
-    convolution that adds x in its epilogue (pre-activation, bottleneck, main-path units); "add": the branch ends in its
-    activation and an AddTable follows (post-activation); None: one flat run [act, K] * n | [K, act] * n.  A ReLU that batch
-    norm replaced never appears: a unit that still holds one is none of these (None)."""
-    mods = list(unit_seq._modules.values()) if isinstance(unit_seq, torch.nn.Sequential) else list(unit_seq)
-    if mods and all(isinstance(m, (M._BatchNorm, M.SubmanifoldConvolution)) for m in mods):
-        c = int(mods[0].nPlanes) if isinstance(mods[0], M._BatchNorm) else mods[0].nIn
-        kinds = [isinstance(m, M._BatchNorm) for m in mods]
-        if len(mods) % 2 or kinds != [kinds[0], not kinds[0]] * (len(mods) // 2) or _bn_chain(mods, c) != c:
-            return None
-        return [("bn", c, None, mods, None)]
-    out = []
-    for block in mods:
-        if not (type(block) is M.Sequential and len(block) in (2, 3) and type(block[0]) is M.ConcatTable
-                and type(block[1]) is M.AddTable and len(block[0]._modules) == 2):
-            return None
-        closing = block[2] if len(block) == 3 else None
-        a, inner = list(block[0]._modules.values())
-        if type(a) is not M.Identity or type(inner) is not M.Sequential or not len(inner):
-            return None
-        branch = list(inner._modules.values())
-        c = int(branch[0].nPlanes) if isinstance(branch[0], M._BatchNorm) else getattr(branch[0], "nIn", None)
-        if c is None or _bn_chain(branch, c) != c or not any(isinstance(m, M._BatchNorm) for m in branch):
-            return None
-        if closing is not None and not (isinstance(closing, M._BatchNorm) and int(closing.nPlanes) == c):
-            return None
-        out.append(("bn", c, "add" if isinstance(branch[-1], M._BatchNorm) else "res", branch, closing))
-    return out
-
-
-def _unit_blocks(unit_seq, bn=False):
-    """_plain_blocks with the reference's other unit forms: a plain unit stays (conv1, conv2); the others come as
-    ("bottleneck" | "both", N1, K, N2) and ("main", K1, K2) -- "both" and "main" close with a ReLU (main_path_relu).  None when
-    a block is none of them (batch norm, a layer without bias, channel padding, groups).
-    bn: a batch-norm layer may stand wherever a ReLU may (`_bn_blocks`)."""
-    if bn and any(isinstance(m, M._BatchNorm) for m in (unit_seq.modules() if isinstance(unit_seq, torch.nn.Module) else unit_seq)):
-        return _bn_blocks(unit_seq)
-    out = []
-    mods = list(unit_seq._modules.values()) if isinstance(unit_seq, torch.nn.Sequential) else list(unit_seq)
-    if mods and len(mods) % 2 == 0 and all(type(m) in (M.ReLU, M.SubmanifoldConvolution) for m in mods):
-        # use_residuals=False: a flat [ReLU, K] * n | [K, ReLU] * n (module_factory.py:186-218)
-        pre = type(mods[0]) is M.ReLU
-        convs, relus = (mods[1::2], mods[0::2]) if pre else (mods[0::2], mods[1::2])
-        if any(type(m) is not M.ReLU for m in relus):
-            return None
-        for m in convs:
-            if (type(m) is not M.SubmanifoldConvolution or m.filter_size != 3 or m.bias is None or m.groups != 1 or m.pad_out_to
-                    or m.nIn != m.nOut):
-                return None
-            out.append(("plain_pre" if pre else "plain_post", m))
-        return out
-    for block in unit_seq:
-        plain = _plain_blocks([block])
-        if plain is not None:
-            out += plain
-            continue
-        if not (type(block) is M.Sequential and len(block) in (2, 3) and type(block[0]) is M.ConcatTable
-                and type(block[1]) is M.AddTable and len(block[0]._modules) == 2):
-            return None
-        main = len(block) == 3
-        if main and type(block[2]) is not M.ReLU:
-            return None
-        a, inner = list(block[0]._modules.values())
-        if type(a) is not M.Identity or type(inner) is not M.Sequential:
-            return None
-        mods = list(inner._modules.values())
-        post = False
-        if not main:                                         # relu_first: the branch opens with the activation ...
-            if not mods:
-                return None
-            if type(mods[0]) is M.ReLU:
-                mods = mods[1:]
-            elif type(mods[-1]) is M.ReLU:                   # ... without it the activation closes the branch (post-activation)
-                mods, post = mods[:-1], True
-            else:
-                return None
-        if len(mods) not in (3, 5) or any(type(m) is not M.ReLU for m in mods[1::2]):
-            return None
-        convs = mods[0::2]
-        if any(type(m) is not M.SubmanifoldConvolution or m.bias is None or m.groups != 1 or m.pad_out_to for m in convs):
-            return None
-        sizes = tuple(m.filter_size for m in convs)
-        c = convs[0].nIn
-        if sizes == (3, 3):
-            if not (main or post) or any((m.nIn, m.nOut) != (c, c) for m in convs):
-                return None
-            out.append(("post" if post else "main", *convs))
-        elif sizes == (1, 3, 1):
-            ci = convs[0].nOut
-            if (convs[1].nIn, convs[1].nOut, convs[2].nIn, convs[2].nOut) != (ci, ci, ci, c):
-                return None
-            out.append(("both" if main else ("post_bottleneck" if post else "bottleneck"), *convs))
-        else:
-            return None
-    return out
-
-
-def _block_width(blk):
-    """Channels a unit of `_unit_blocks` takes and gives."""
-    if blk[0] == "bn":
-        return blk[1]
-    return (blk[1] if isinstance(blk[0], str) else blk[0]).nIn
-
-
 def _phys(m):
     return int(getattr(m, "pad_out_to", None) or m.nOut)
 
 
 def _stage_relus(stage, bn=False):
-    """(a ReLU leads the layer, a ReLU follows it) of an input stage (module_factory.py:438-486): the conv-type layer itself or a
-    Sequential of just it -- (False, False) --, Sequential(ReLU, layer), Sequential(layer, ReLU).  None: anything else.
-    bn: a batch-norm layer may stand where the ReLU does; the pair then holds that MODULE in place of True."""
+    """(lead, trail): the activation MODULE in front of and behind the layer of an input stage (module_factory.py:438-486), each
+    None, a ReLU or -- bn -- a batch-norm layer: the conv-type layer itself or a Sequential of just it -- (None, None) --,
+    Sequential(act, layer), Sequential(layer, act).  None: anything else."""
     if isinstance(stage, M._ConvBase):
-        return (False, False)
+        return (None, None)
     if type(stage) is not M.Sequential:
         return None
     mods = list(stage._modules.values())
-    kinds = tuple("r" if (type(m) is M.ReLU or (bn and isinstance(m, M._BatchNorm))) else ("c" if isinstance(m, M._ConvBase) else "?")
-                  for m in mods)
-    out = {("c",): (False, False), ("r", "c"): (True, False), ("c", "r"): (False, True)}.get(kinds)
-    if out is None or not bn:
-        return out
-    act = mods[0] if out[0] else (mods[1] if out[1] else None)
-    if isinstance(act, M._BatchNorm):
-        return (act, False) if out[0] else (False, act)
-    return out
-
-
-def _bn_of(flag):
-    """The batch-norm layer a `_stage_relus` entry names, or None (no activation there, or a ReLU)."""
-    return flag if isinstance(flag, M._BatchNorm) else None
+    is_layer = [isinstance(m, M._ConvBase) for m in mods]
+    if is_layer == [True]:
+        return (None, None)
+    act = mods[is_layer.index(False)] if sorted(is_layer) == [False, True] else None
+    if not (_is_relu(act) or (bn and _is_bn(act))):
+        return None
+    return (None, act) if is_layer[0] else (act, None)
 
 
 def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False, cast_last=False, in_bf16=False,
-                          relus=(False, False), bn_training=True):
+                          relus=(None, None), bn_training=True):
     """Encoder level: head (SubM 1^3 at level 0 | Convolution 2^3/2 from level-1) + residual units.
     level 0 in bf16 storage: the head runs in fp32 on the fp32 input and its result is cast (SparseUNet), or -- cast_first,
     the mask branch's input stage -- the input is cast first and the head runs on bf16 rows, or -- in_bf16 -- the input
     slab is bf16-stored already (a SubM 1^3 stage behind a bf16 network in a module tree); cast_last: fp32 output.
-    relus (`_stage_relus`): a ReLU in front of the head is fused into its gather; one behind it is an in-place SCN_OP_RELU on the
-    head's result, whose backward masks by that slab.  A batch-norm layer in either place (`_stage_relus(bn=True)`; fp32 slabs
-    only) reads one slab and writes another: in front, the head gathers the normalised slab; behind, the units start from it.
+    blocks: the level's units (`_units`).  relus (`_stage_relus`): a ReLU in front of the head is a flag of its gather; every
+    other activation is free-standing (`Stage.act`) -- a ReLU behind the head works in place on its result, a batch-norm layer
+    (fp32 slabs only) reads one slab and writes another: in front, the head gathers the normalised slab; behind, the units
+    start from it.
     bn_training: the batch-norm layers of the stage take batch statistics (False: their running buffers)."""
     lead, trail = relus
-    lead_bn, trail_bn = _bn_of(lead), _bn_of(trail)
-    if bf16 and (lead_bn or trail_bn or any(b[0] == "bn" for b in blocks)):
+    if bf16 and (_is_bn(lead) or _is_bn(trail) or any(u.has_bn for u in blocks)):
         raise NotImplementedError("executor: batch norm runs on fp32 slabs")
-    lead, trail = bool(lead) and lead_bn is None, bool(trail) and trail_bn is None
-    lead_fl = L.F_RELU_IN if lead else 0
+    lead_fl = L.F_RELU_IN if _is_relu(lead) else 0
     st = Stage(bf16, 1, bn_training)
     in_bf16 = bool(bf16 and in_bf16 and level == 0)
     es_in = (2 if in_bf16 else 4) if (level == 0) else st.es
@@ -741,7 +700,7 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
     st.out_id = OUT
     if level == 0:
         if bf16 and (cast_first or in_bf16):
-            if lead or trail:
+            if lead is not None or trail is not None:
                 raise NotImplementedError("executor: a level-0 head on bf16 rows takes no input-stage ReLU")
             xin = IN
             if not in_bf16:
@@ -753,33 +712,24 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
         else:
             h = st.buf(0, c, 4)
             head_in = IN
-            if lead_bn is not None:
-                head_in = st.buf(0, cin_phys, 4)
-                lead_rec = st.bn_layer(0, lead_bn, IN, head_in)
+            if _is_bn(lead):
+                head_in, lead_rec = st.act(0, cin_phys, lead, IN, fp32=True)
             st.op(st.fwd, OP_GEMM_IDENT, 0, cin_phys, c, x=head_in, y=h, w=st.param("w", mh), b=st.param("b", mh), flags=lead_fl)
-            if trail:
-                st.op(st.fwd, OP_RELU, 0, c, 0, x=h, y=h, flags=0)
             x, head_hb = h, 0
-            if trail_bn is not None:
-                x = st.buf(0, c, 4)
-                trail_rec = st.bn_layer(0, trail_bn, h, x)
+            if trail is not None:
+                x, trail_rec = st.act(0, c, trail, h, fp32=True)
             if bf16:
                 x = st.buf(0, c)
                 st.op(st.fwd, OP_CAST, 0, c, 0, x=h, y=x, flags=XF_BF16)
     else:
         x = st.buf(level, c)
         head_in = IN
-        if lead_bn is not None:
-            head_in = st.buf(level - 1, cin_phys)
-            lead_rec = st.bn_layer(level - 1, lead_bn, IN, head_in)
+        if _is_bn(lead):
+            head_in, lead_rec = st.act(level - 1, cin_phys, lead, IN)
         st.op(st.fwd, OP_CONV_CHILD, level - 1, cin_phys, c, x=head_in, y=x, w=st.weight(mh, cin_phys, c, 8, 0, True),
               b=st.param("b", mh), flags=lead_fl | st.hb)
-        h = x
-        if trail:
-            st.op(st.fwd, OP_RELU, level, c, 0, x=x, y=x, flags=st.hb)
-        if trail_bn is not None:
-            x = st.buf(level, c)
-            trail_rec = st.bn_layer(level, trail_bn, h, x)
+        if trail is not None:
+            x, trail_rec = st.act(level, c, trail, x)
     if bf16 and cast_last:
         last, saved = st.units_fwd(level, c, x, blocks)
         st.op(st.fwd, OP_CAST, level, c, 0, x=last, y=OUT, flags=0)
@@ -808,50 +758,36 @@ def compile_encoder_stage(level, head, blocks, cin_phys, bf16, cast_first=False,
             if bf16:
                 gf = st.buf(0, c, 4, "b")
                 st.op(st.bwd, OP_CAST, 0, c, 0, x=g, y=gf, flags=0)
-            if trail:
-                gm = st.buf(0, c, 4, "b")
-                st.op(st.bwd, OP_RELU_BWD, 0, c, 0, m=h, x1=gf, y=gm, flags=0)
-                gf = gm
-            if trail_bn is not None:
-                gm = st.buf(0, c, 4, "b")
-                st.bn_layer_bwd(trail_rec, gf, gm)
-                gf = gm
-            dhead = DIN if lead_bn is None else st.buf(0, cin_phys, 4, "b")
-            st.op(st.bwd, OP_GEMM_IDENT, 0, c, cin_phys, x=gf, y=dhead, m=IN if lead else -1, w=st.param("w", mh), flags=BACK)
+            if trail is not None:
+                gf = st.act_bwd(trail_rec, gf)
+            dhead = st.buf(0, cin_phys, 4, "b") if _is_bn(lead) else DIN
+            st.op(st.bwd, OP_GEMM_IDENT, 0, c, cin_phys, x=gf, y=dhead, m=IN if lead_fl else -1, w=st.param("w", mh), flags=BACK)
             st.op(st.bwd, OP_WGRAD_IDENT, 0, cin_phys, c, x=head_in, y=gf, w=gw, b=gb, flags=lead_fl)
-            if lead_bn is not None:
-                st.bn_layer_bwd(lead_rec, dhead, DIN)
+            if _is_bn(lead):
+                st.act_bwd(lead_rec, dhead, DIN)
     else:
-        if trail:
-            gm = st.buf(level, c, kind="b")
-            st.op(st.bwd, OP_RELU_BWD, level, c, 0, m=h, x1=g, y=gm, flags=st.hb)
-            g = gm
-        if trail_bn is not None:
-            gm = st.buf(level, c, kind="b")
-            st.bn_layer_bwd(trail_rec, g, gm)
-            g = gm
-        dhead = DIN if lead_bn is None else st.buf(level - 1, cin_phys, kind="b")
-        st.op(st.bwd, OP_RULES_CHILD, level - 1, c, cin_phys, x=g, y=dhead, m=IN if lead else -1, w=st.param("w", mh),
+        if trail is not None:
+            g = st.act_bwd(trail_rec, g)
+        dhead = st.buf(level - 1, cin_phys, kind="b") if _is_bn(lead) else DIN
+        st.op(st.bwd, OP_RULES_CHILD, level - 1, c, cin_phys, x=g, y=dhead, m=IN if lead_fl else -1, w=st.param("w", mh),
               flags=L.F_W_TRANSPOSED | st.hb)
         st.op(st.bwd, OP_WGRAD_DOWN, level - 1, cin_phys, c, x=head_in, y=g, w=gw, flags=lead_fl | st.hb)
         st.op(st.bwd, OP_COLSUM, level, c, 0, x=g, b=gb, flags=st.hb)
-        if lead_bn is not None:
-            st.bn_layer_bwd(lead_rec, dhead, DIN)
+        if _is_bn(lead):
+            st.act_bwd(lead_rec, dhead, DIN)
     return st.freeze()
 
 
-def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, False), bn_training=True):
+def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, *, relus, bn_training=True):
     """Decoder level: ReLU -> Deconvolution 2^3/2 (coarse level+1 -> level) -> JoinTable([up, skip]) -> NetworkInNetwork ->
-    residual units.  Inputs: (coarse slab, skip slab).  relus (`_stage_relus`): (True, False) is that form; (False, True) the
-    relu_first=False one, Deconvolution -> ReLU, the ReLU in place on the deconvolution's result.  A batch-norm layer behind
-    the deconvolution (fp32 slabs only) writes the slab the NetworkInNetwork reads; in front of it: not a form the network
-    builder makes (NotImplementedError)."""
+    units (`_units`).  Inputs: (coarse slab, skip slab).  relus (`_stage_relus`): (ReLU, None) is that form, the ReLU a flag of
+    the deconvolution's gather; (None, act) the relu_first=False one, Deconvolution -> act, free-standing (`Stage.act`): a ReLU in
+    place on the deconvolution's result, a batch-norm layer (fp32 slabs only) writing the slab the NetworkInNetwork reads.
+    Batch norm in front of the deconvolution: not a form the network builder makes (NotImplementedError)."""
     lead, trail = relus
-    trail_bn = _bn_of(trail)
-    if _bn_of(lead) is not None or (bf16 and (trail_bn is not None or any(b[0] == "bn" for b in blocks))):
+    if _is_bn(lead) or (bf16 and (_is_bn(trail) or any(u.has_bn for u in blocks))):
         raise NotImplementedError("executor: a decoder level takes batch norm behind its deconvolution, on fp32 slabs")
-    trail = bool(trail) and trail_bn is None
-    lead_fl = L.F_RELU_IN if lead else 0
+    lead_fl = L.F_RELU_IN if lead is not None else 0
     st = Stage(bf16, 2, bn_training)
     c = _phys(up)
     IN0 = st.buf(level + 1, c_coarse, None, "x")
@@ -863,12 +799,9 @@ def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, F
     upb = st.buf(level, c)
     st.op(st.fwd, OP_RULES_CHILD, level, c_coarse, c, x=IN0, y=upb, w=st.param("w", mu), b=st.param("b", mu),
           flags=lead_fl | st.hb)
-    if trail:
-        st.op(st.fwd, OP_RELU, level, c, 0, x=upb, y=upb, flags=st.hb)
     upa = upb                                              # what the NetworkInNetwork reads
-    if trail_bn is not None:
-        upa = st.buf(level, c)
-        trail_rec = st.bn_layer(level, trail_bn, upb, upa)
+    if trail is not None:
+        upa, trail_rec = st.act(level, c, trail, upb)
     h = st.buf(level, c)
     st.op(st.fwd, OP_ROWS2, level, c, c, x=upa, x1=IN1, c1=c, y=h, w=st.param("w", mn), b=st.param("b", mn), flags=st.hb)
     last, saved = st.units_fwd(level, c, h, blocks, out_id=OUT)
@@ -884,15 +817,9 @@ def compile_decoder_stage(level, up, nin, blocks, c_coarse, bf16, relus=(True, F
     gwn, gbn = st.gregion((mn, "w")), st.gregion((mn, "b"))
     st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=upa, y=g, w=gwn, b=gbn, aux=0, flags=st.hb)
     st.op(st.bwd, OP_WGRAD_IDENT, level, c, c, x=IN1, y=g, w=gwn, b=-1, aux=c * c, flags=st.hb)
-    if trail:
-        dm = st.buf(level, c, kind="b")
-        st.op(st.bwd, OP_RELU_BWD, level, c, 0, m=upb, x1=dup, y=dm, flags=st.hb)
-        dup = dm
-    if trail_bn is not None:
-        dm = st.buf(level, c, kind="b")
-        st.bn_layer_bwd(trail_rec, dup, dm)
-        dup = dm
-    st.op(st.bwd, OP_CONV_CHILD, level, c, c_coarse, x=dup, y=DIN0, m=IN0 if lead else -1,
+    if trail is not None:
+        dup = st.act_bwd(trail_rec, dup)
+    st.op(st.bwd, OP_CONV_CHILD, level, c, c_coarse, x=dup, y=DIN0, m=IN0 if lead_fl else -1,
           w=st.weight(mu, c, c_coarse, 8, L.F_W_TRANSPOSED, True), flags=L.F_W_TRANSPOSED | st.hb)
     gwu, gbu = st.gregion((mu, "w")), st.gregion((mu, "b"))
     st.op(st.bwd, OP_WGRAD_UP, level, c_coarse, c, x=IN0, y=dup, w=gwu, b=gbu, flags=lead_fl | st.hb)

@@ -186,10 +186,11 @@ class MaskBranch(nn.Module):
             return None
         st = self.__dict__.get("_input_stage")
         if st is None:
-            blocks = EX._plain_blocks(self.input_conv_layer[1])
+            blocks = EX._units(self.input_conv_layer[1])
             head = self.input_conv_layer[0]
             st = False
-            if blocks is not None and head.nOut % 8 == 0 and head.nIn % 8 == 0 and EX._require_bias(head):
+            if (blocks is not None and all(u.is_default for u in blocks) and head.nOut % 8 == 0 and head.nIn % 8 == 0
+                    and EX._require_bias(head)):
                 st = EX.compile_encoder_stage(0, head, blocks, head.nIn, self.bf16, cast_first=True, cast_last=False)
             object.__setattr__(self, "_input_stage", st)
         if not st:

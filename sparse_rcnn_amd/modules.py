@@ -99,7 +99,8 @@ def _head_of(m):
 
 
 def _stage_of(m):
-    """(head, (ReLU in front, ReLU behind)) of an encoder level's input stage (module_factory.py:438-486), or None."""
+    """(head, (the ReLU in front | None, the ReLU behind | None)) of an encoder level's input stage (module_factory.py:438-486),
+    or None."""
     from . import executor as EX
     relus = EX._stage_relus(m)
     if relus is None:
@@ -108,21 +109,18 @@ def _stage_of(m):
     return None if head is None else (head, relus)
 
 
-_TREE_FORMS = ("post", "post_bottleneck", "plain_pre", "plain_post")
-
-
 def _tree_blocks(seq):
-    """executor._unit_blocks of a Sequential of units, limited to the forms a foreign tree's stages take."""
+    """executor._units of a Sequential of units, limited to the forms a foreign tree's stages take (`Unit.tree_form`)."""
     from . import executor as EX
-    blocks = EX._unit_blocks(seq)
-    if blocks and any(isinstance(b[0], str) and b[0] not in _TREE_FORMS for b in blocks):
+    blocks = EX._units(seq)
+    if blocks and not all(u.tree_form for u in blocks):
         return None
     return blocks
 
 
 def _default_form(blocks, relus):
     """The shapes the stages always took: plain pre-activation units behind a bare head / ReLU -> Deconvolution."""
-    return relus[1] is False and not any(isinstance(b[0], str) for b in blocks)
+    return relus[1] is None and all(u.is_default for u in blocks)
 
 
 # A cached shape (`_stage_kind`) / compiled plan (`_stages`) of a Sequential captures its WHOLE subtree: the head, the inner
@@ -172,7 +170,6 @@ def _kind(seq):
     kind = seq.__dict__.get("_stage_kind")
     if kind is not None:
         return kind or None
-    from . import executor as EX
     mods = list(seq._modules.values())
     kind = False
     if (len(mods) == 2 and type(mods[0]) is ReLU and type(mods[1]) is Deconvolution and mods[1].bias is not None
@@ -183,7 +180,7 @@ def _kind(seq):
         kind = "up_post"
     elif len(mods) == 2 and type(mods[1]) is Sequential and _stage_of(mods[0]) is not None:
         (head, relus), blocks = _stage_of(mods[0]), _tree_blocks(mods[1])
-        if (blocks and head.bias is not None and head.pad_out_to is None and all(EX._block_width(b) == head.nOut for b in blocks)
+        if (blocks and head.bias is not None and head.pad_out_to is None and all(u.c == head.nOut for u in blocks)
                 and head.nOut % 8 == 0 and (type(head) is SubmanifoldConvolution or head.nIn % 8 == 0)):
             kind = "enc"
     elif mods and _tree_blocks(seq):
@@ -242,8 +239,7 @@ def _dec_stage(seq, input):
     _, up_t, skip_t, nin = tag
     if not (isinstance(up_t, DeferredTensor) and up_t.pending and up_t.tag[0] == "up"):
         return NotImplemented
-    _, coarse_t, deconv, *post = up_t.tag
-    relus = (False, True) if post else (True, False)
+    _, coarse_t, deconv, relus = up_t.tag
     xc, xs = coarse_t.features, skip_t.features
     c = deconv.nOut
     blocks = _tree_blocks(seq)
@@ -251,7 +247,7 @@ def _dec_stage(seq, input):
         return NotImplemented
     if not (_usable(xc) and _usable(xs) and xc.dtype == xs.dtype and xs.shape[1] == c and nin.nIn == 2 * c and nin.nOut == c
             and nin.bias is not None and c % 8 == 0 and deconv.nIn % 8 == 0 and xc.shape[1] == deconv.nIn
-            and deconv.pad_out_to is None and nin.pad_out_to is None and all(EX._block_width(b) == c for b in blocks)):
+            and deconv.pad_out_to is None and nin.pad_out_to is None and all(u.c == c for u in blocks)):
         return NotImplemented
     md = input.metadata
     fine = tuple(int(s) for s in input.spatial_size)
@@ -330,15 +326,15 @@ class Sequential(torch.nn.Sequential):
                     return y
                 STAGE_STATS["layerwise_units"] += 1
             elif kind == "up" and _usable(input.features):
-                deconv = self._modules["1"]
+                relu, deconv = self._modules["0"], self._modules["1"]
                 out_size = torch.as_tensor([int(s) * 2 for s in input.spatial_size], dtype=torch.long)
                 return DeferredTensor(lambda: deconv(input, relu_in=True).features, input.metadata, out_size,
-                                      ("up", input, deconv))
+                                      ("up", input, deconv, (relu, None)))
             elif kind == "up_post" and _usable(input.features):
                 deconv, relu = self._modules["0"], self._modules["1"]
                 out_size = torch.as_tensor([int(s) * 2 for s in input.spatial_size], dtype=torch.long)
                 return DeferredTensor(lambda: relu(deconv(input)).features, input.metadata, out_size,
-                                      ("up", input, deconv, "post"))
+                                      ("up", input, deconv, (None, relu)))
         mods = list(self._modules.values())
         i = 0
         while i < len(mods):

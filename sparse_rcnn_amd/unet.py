@@ -408,15 +408,15 @@ class SparseUNet(nn.Module):
         ch, L = self.channels, len(self.channels)
         ok = not self.bf16_blocks and all(c % 8 == 0 for c in ch[1:]) and (self.phys0 % 8 == 0)
         ok = ok and self.dec_channels == tuple(ch[:-1])      # (min_channels in effect: the layer-by-layer path)
-        enc_blocks = [EX._unit_blocks(lvl[1], bn) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
-        dec_blocks = [EX._unit_blocks(d["units"], bn) for d in self.decoder]
+        enc_blocks = [EX._units(lvl[1], bn) if not (l == 0 and self.identity_first) else [] for l, lvl in enumerate(self.encoder)]
+        dec_blocks = [EX._units(d["units"], bn) for d in self.decoder]
         heads = [stage_layer(lvl[0]) for l, lvl in enumerate(self.encoder) if not (l == 0 and self.identity_first)]
         ok = ok and EX._require_bias(*heads, *[stage_layer(d["up"]) for d in self.decoder], *[d["nin"] for d in self.decoder])
         ok = ok and all(EX._stage_relus(lvl[0], bn) is not None for l, lvl in enumerate(self.encoder)
                         if not (l == 0 and self.identity_first)) and all(EX._stage_relus(d["up"], bn) is not None for d in self.decoder)
         # batch norm: fp32 slabs exactly as wide as the layers; in a decoder level only behind the deconvolution
         ok = ok and not (bn and (self.phys0 != ch[0] or self.bf16_all
-                                 or any(EX._bn_of(EX._stage_relus(d["up"], bn)[0]) is not None for d in self.decoder)))
+                                 or any(isinstance(EX._stage_relus(d["up"], bn)[0], M._BatchNorm) for d in self.decoder)))
         mode = dict(bn_training=training) if bn else {}
         if ok and all(b is not None for b in enc_blocks + dec_blocks):
             bf16 = self.bf16_all
