@@ -84,7 +84,8 @@ extern "C" {
  *      additive within 5: + scn_conv_tiles_plan_describe (178 entry points);
  *      additive within 5: + the executor op SCN_OP_ADD_RELU, no new entry point (178 entry points);
  *      additive within 5: + the executor ops SCN_OP_BN_STATS / _BN_FWD / _BN_BWD and the op flag SCN_XF_BN_TRAINING;
- *                           SCN_OP_WGRAD_SUBM with b < 0 is scn_wgrad_rules(_bf16); no new entry point (178 entry points) */
+ *                           SCN_OP_WGRAD_SUBM with b < 0 is scn_wgrad_rules(_bf16); no new entry point (178 entry points);
+ *      additive within 5: + scn_conv_tiles_bf16_plan_describe (179 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -375,14 +376,19 @@ int scn_conv_tiles_finish(int cin, int64_t n_out, const float* bias, const float
                           float* Y, int cout, int flags, void* scratch, scn_stream_t stream);
 
 /* The same convolution for bf16 STORAGE (BASELINE configs 3-5): X, residual, relu_mask and Y are bf16
- * (uint16 bit patterns, row-major, cin % 8 == 0 and cout % 8 == 0: 16-byte row pieces); products accumulate in fp32 on
+ * (uint16 bit patterns, row-major; cin % 8 == 0 and cin >= 8: 16-byte row pieces of X; ANY cout); products accumulate in fp32 on
  * v_mfma_f32_16x16x32_bf16 and the result is rounded to bf16 once.  Same tiles, flags and per-row summation order as
  * scn_conv_tiles.  The layer's master weights stay fp32: scn_conv_tiles_bf16_pack rounds them (round-to-nearest-even)
  * into `image` (scn_conv_tiles_bf16_image_bytes bytes, 16-byte aligned), laid out as the kernel's workgroups stage it;
  * SCN_F_W_TRANSPOSED / SCN_F_OFF_REVERSE are properties of the IMAGE (pass them to the pack; the convolution ignores
  * them), so one layer has a forward image and a backward-data image.  An image is valid until the weights change.
  * `arrival`: zeroed counters for the in-launch K reduction, contract as in scn_conv_tiles
- * (scn_conv_tiles_bf16_arrival_counters entries); NULL: second launch.
+ * (scn_conv_tiles_bf16_arrival_counters entries); NULL, or SCN_F_SPLIT_SUM: second launch inside the same call (there is
+ * no _finish for bf16).  X and image are 16-byte aligned (SCN_EINVAL otherwise).  Y, residual and relu_mask need only their
+ * 2-byte element alignment: the tile kernels' VECTOR epilogue (a lane's NB = 2 or 4 consecutive columns of a row as one 4- or
+ * 8-byte access) needs cout % NB == 0 and Y / residual / relu_mask on a 2 NB-byte boundary; otherwise every element is its
+ * own 2-byte access -- same results.  bias and scratch need 4 bytes; with an `arrival` array the scratch is 16-byte aligned
+ * (the in-launch K reduction stores 16-byte pieces to it).
  * Serves SubmanifoldConvolution / Convolution forward and SubM / Deconvolution backward-data
  * (module_factory.py:232-234,256-258,404-406). */
 int64_t scn_conv_tiles_bf16_image_bytes(int cin, int cout, int n_off);
@@ -398,6 +404,26 @@ int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, const int32_t*
                         const int32_t* perm, const int32_t* tile_order, int n_off, int64_t n_out, const uint16_t* image,
                         const float* bias, const uint16_t* residual, const uint16_t* relu_mask, uint16_t* Y, int cout,
                         int flags, void* scratch, int32_t* arrival, scn_stream_t stream);
+/* Which path a scn_conv_tiles_bf16 call takes (host only: launches nothing, allocates nothing; tests and tools).  The launcher
+ * takes every decision from the function that fills this report, under the developer switches set at the time of the call.
+ *   with_arrival: the call passes an `arrival` array.
+ *   y_ptr_bits: the low 4 bits of Y | residual | relu_mask;  scratch_ptr_bits: the low 4 bits of scratch | bias.
+ *   out[0]  stream: 1 = the offset-outer weight-streaming kernel k_conv_tbs<KS, n_off, NW> takes the call; then
+ *   out[1]  KS (K-chunks of 32 a wave contracts per offset)  out[2] NW (waves = tiles per workgroup batch)
+ *   out[3]  n_wgb: workgroups per column chunk (a workgroup walks every n_wgb-th batch of NW tiles); 0 without stream
+ *   out[4]  NB (16-column blocks per workgroup: 2 or 4)  out[5] KH (32-channel planes per K-chunk: 1 or 2)
+ *   out[6]  FUSED (in-launch K reduction)  out[7] PART (Cin no multiple of the K-chunk)       -- k_conv_tb<NB, KH, FUSED, PART>
+ *   out[8]  K-chunks  out[9] column chunks
+ *   out[10] workgroups per (column chunk, K-chunk) slice of k_conv_tb (0 with stream)  out[11] workgroups of the tile launch
+ *   out[12] xbins: groups of XCDs of the XCD-local hand-out (SCN_F_TILE_ORDER_X), 1 = the plain order (0 with stream)
+ *   out[13] 1: the tile kernel's epilogue is the vector form, 0: element by element
+ *   out[14] 1: the call makes a K-chunk sum launch (k_conv_tb_sum)  out[15] its elements per thread (4 or 1; 0: no sum launch)
+ *   out[16] tiles  out[17] dynamic LDS bytes of the tile launch
+ * n_out == 0 (the launcher returns without a launch): all zero.  SCN_EINVAL for arguments the launcher rejects (cin % 8,
+ * cin < 8, n_off outside 1..27, the row limits) and for pointer bits below the element size (2 bytes for y_ptr_bits, 4 for
+ * scratch_ptr_bits). */
+int scn_conv_tiles_bf16_plan_describe(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags, int with_arrival,
+                                      int y_ptr_bits, int scratch_ptr_bits, int64_t out[18]);
 
 /* Rule-list gather GEMM with row scatter:  Y[out_rows[p]] = bias + in(X[in_rows[p]]) . W[o(p)]
  * where every output row occurs in exactly one pair (Deconvolution fwd, module_factory.py:256-258; backward-data

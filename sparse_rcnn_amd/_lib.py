@@ -69,6 +69,7 @@ _SIGS = {
     "scn_conv_tiles_bf16_scratch_bytes": (i64, [i32, i64, i32]),
     "scn_conv_tiles_bf16_arrival_counters": (i64, [i32, i64, i32]),
     "scn_conv_tiles_bf16": (C.c_int, [p, i64, i32, p, p, p, p, i32, i64, p, p, p, p, p, i32, i32, p, p, p]),
+    "scn_conv_tiles_bf16_plan_describe": (C.c_int, [i64, i32, i32, i64, i32, i32, i32, i32, i32, C.POINTER(i64)]),
     "scn_gemm_rules": (C.c_int, [p, i32, p, p, C.POINTER(i64), i32, p, p, p, p, i32, i32, p]),
     "scn_wgrad_scratch_bytes": (i64, [i32, i32, C.POINTER(i64), i32]),
     "scn_wgrad_rules": (C.c_int, [p, i32, p, i32, p, p, C.POINTER(i64), i32, p, p, i32, p]),

@@ -26,6 +26,7 @@
 // K split over workgroups (Cin > 32 or 64): the partial tiles are added inside the launch by the wave that arrives last
 // at a (tile, column chunk) -- the pipelined hand-off of k_conv_ts (scn_conv_ts.hip), fp32 partials, fixed K-chunk order.
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 #include "scn_common.h"
@@ -48,6 +49,13 @@ static constexpr int TB_NW = 16;        // waves per workgroup
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 __device__ __forceinline__ unsigned short f32_to_bf16(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
+
+// The vector epilogue of k_conv_tb / k_conv_tbs (a lane's NB consecutive bf16 columns of a row as one 4- or 8-byte access):
+// cout % NB == 0 and Y, residual, relu_mask on a 2 NB-byte boundary (y_bits: the low 4 bits of Y | residual | relu_mask; a
+// missing operand is a NULL pointer: no bits).  ONE expression for the two kernels and the host's path report (tb_plan).
+__host__ __device__ __forceinline__ bool tb_vec_ok(int cout, int nb, unsigned y_bits) {
+    return cout % nb == 0 && (y_bits & (unsigned)(2 * nb - 1)) == 0;
+}
 
 template <int NB, int KH, bool FUSED, bool PART>
 __global__ __launch_bounds__(TB_NW * 64) __attribute__((amdgpu_waves_per_eu(NB == 2 && KH == 1 && !FUSED ? 8 : 4))) void k_conv_tb(
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(TB_NW * 64) __attribute__((amdgpu_waves_per_eu(NB =
     // and shifts -- element-indexed short vectors made the compiler spill to scratch.  vec_ok: cout % NB == 0 and aligned
     // operands; otherwise every column is its own 2-byte access.
     constexpr int NWD = NB / 2;
-    const bool vec_ok = (cout % NB == 0) && ((((uintptr_t)Y | (uintptr_t)residual | (uintptr_t)relu_mask) & (2 * NB - 1)) == 0);
+    const bool vec_ok = tb_vec_ok(cout, NB, (unsigned)(((uintptr_t)Y | (uintptr_t)residual | (uintptr_t)relu_mask) & 15));
     auto tb_load_ops = [&](const int (&orow)[4], unsigned (&rw)[4][NWD], unsigned (&mw)[4][NWD]) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                                // all operand loads first, one wait
@@ -501,7 +509,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_tbs(
         wdst[u] = (p / (CT * 4)) * (CT * 4) + (r >> 6) * 64 + (r & 3) * 16 + ((r >> 2) & 15);
     }
     constexpr int NWD = NB / 2;
-    const bool vec_ok = (cout % NB == 0) && ((((uintptr_t)Y | (uintptr_t)residual | (uintptr_t)relu_mask) & (2 * NB - 1)) == 0);
+    const bool vec_ok = tb_vec_ok(cout, NB, (unsigned)(((uintptr_t)Y | (uintptr_t)residual | (uintptr_t)relu_mask) & 15));
 
 #define TBS_WLOAD(O, V)                                                                                        \
     _Pragma("unroll") for (int u_ = 0; u_ < PW; ++u_)                                                          \
@@ -873,21 +881,45 @@ extern "C" int64_t scn_conv_tiles_bf16_arrival_counters(int cin, int64_t n_out, 
     return sh.n_kc > 1 ? cdiv(n_out, TB_T) * sh.n_chunks : 0;
 }
 
-extern "C" int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, const int32_t* tstab,
-                                   const uint32_t* tile_mask, const int32_t* perm, const int32_t* tile_order, int n_off,
-                                   int64_t n_out, const uint16_t* image, const float* bias, const uint16_t* residual,
-                                   const uint16_t* relu_mask, uint16_t* Y, int cout, int flags, void* scratch,
-                                   int32_t* arrival, scn_stream_t stream) {
-    SCN_REQUIRE(n_off >= 1 && n_off <= 27 && n_out >= 0 && n_in >= 0 && cin >= 8 && cout >= 1);
-    SCN_REQUIRE(cin % 8 == 0);                                   // 16-byte row pieces of X (any cout)
-    if (n_out == 0) return SCN_OK;
-    SCN_REQUIRE(X && tstab && tile_mask && perm && tile_order && image && Y && scratch);
-    SCN_REQUIRE((((uintptr_t)X | (uintptr_t)image) & 15) == 0);
-    SCN_REQUIRE(n_in < (1ll << 23) && n_in * cin * 2 < (1ll << 32) - (1ll << 24));    // 24-bit rows, 32-bit offsets
-    SCN_REQUIRE(n_out < (1ll << 23));                             // the tile table is addressed with 31-bit byte offsets
-    const int64_t nt = cdiv(n_out, TB_T);
-    const TbShape sh = tb_shape(cin, cout);
-    const int nb = sh.nb, kh = sh.kh, ct = sh.ct, kcs = sh.kc, n_chunks = sh.n_chunks, n_kc = sh.n_kc;
+// The K-chunk sum moves 4 elements per thread (16-byte slab and bias reads, 8-byte bf16 accesses) when every buffer it touches
+// allows it (s_bits: the low 4 bits of scratch | bias -- the slabs start 256 bytes into the scratch; y_bits: of
+// Y | residual | relu_mask)
+static bool tb_sum_v4(int cout, unsigned y_bits, unsigned s_bits) {
+    return cout % 4 == 0 && (s_bits & 15) == 0 && (y_bits & 7) == 0;
+}
+
+// Everything the host decides about one scn_conv_tiles_bf16 call -- the ONE place it is decided: the launcher launches what
+// this says, scn_conv_tiles_bf16_plan_describe reports it (after TsPlan / ts_plan of scn_conv_ts.hip).
+namespace {
+struct TbPlan {
+    int64_t nt;                         // tiles
+    TbShape sh;                         // nb, kh, column chunks, K-chunks (tb_shape: shared with the pack)
+    bool stream;                        // k_conv_tbs takes the call; then:
+    int ks, nw;                         //   k_conv_tbs<KS, n_off, NW, D>
+    int64_t n_wgb;                      //   workgroups per column chunk (a workgroup walks every n_wgb-th batch of NW tiles)
+    bool fused, part;                   // k_conv_tb<NB, KH, FUSED, PART>
+    size_t lds;
+    int64_t n_tg;                       // workgroups per (column chunk, K-chunk) slice
+    int64_t grid_x;
+    int xbins;                          // XCD-local hand-out: groups of XCDs (1: the plain LPT order)
+    bool vec_ok;                        // the tile kernel's epilogue: vector (else element by element)
+    bool sum;                           // the call makes a K-chunk sum launch, k_conv_tb_sum<sum_v>
+    int sum_v;
+};
+
+TbPlan tb_plan(int cin, int n_off, int64_t n_out, int cout, int flags, bool with_arrival, unsigned y_bits, unsigned s_bits) {
+    TbPlan p;
+    p.nt = cdiv(n_out, TB_T);
+    p.sh = tb_shape(cin, cout);
+    const int64_t nt = p.nt;
+    const int nb = p.sh.nb, kh = p.sh.kh, ct = p.sh.ct, kcs = p.sh.kc, n_chunks = p.sh.n_chunks, n_kc = p.sh.n_kc;
+    p.vec_ok = tb_vec_ok(cout, nb, y_bits);
+    p.ks = p.nw = 0;
+    p.n_wgb = 0;
+    p.fused = p.part = p.sum = false;
+    p.n_tg = 0;
+    p.xbins = 0;
+    p.sum_v = 0;
     // ---- the offset-outer, weight-streaming kernel (k_conv_tbs above).  Measured on the cfg-2 scene (tools/ablate_tbs_exp.py,
     // profiles/r4_tbs_streaming_experiment.txt): 26.2 / 39.3 / 47.9 us per launch at levels 1 / 2 / 3 against k_conv_tb's
     // 30.0 / 26.9 / 27.7 -- it wins only where one offset's slice is small (Cin = 64), so THAT is what it runs by default:
@@ -897,17 +929,92 @@ extern "C" int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, con
     const int ts_mode = ts_sw.set ? (int)ts_sw.i : -1;
     const bool ts_eligible = n_kc >= 2 && kh == 1 && nb == 4 && cin % 32 == 0 && (n_kc == 2 || n_kc == 4 || n_kc == 8) &&
                              (n_off == 27 || n_off == 8) && !(flags & SCN_F_SPLIT_SUM);
-    if (ts_eligible && ts_mode != 0 && (ts_mode == 1 || (n_kc == 2 && n_off == 27))) {
-        hipStream_t st = S(stream);
+    p.stream = ts_eligible && ts_mode != 0 && (ts_mode == 1 || (n_kc == 2 && n_off == 27));
+    if (p.stream) {
         // waves per workgroup: 8 (one tile each); 4 when the level has too few tiles to put a workgroup on every CU
         const bool small = cdiv(nt, 8) * n_chunks < 224;
-        const int nw = small ? 4 : 8;
-        int64_t n_wgb = cdiv(nt, nw);
+        p.ks = n_kc;
+        p.nw = small ? 4 : 8;
+        p.n_wgb = cdiv(nt, p.nw);
         const int64_t cap = (int64_t)(n_kc == 2 ? 512 : 256) / n_chunks;          // resident workgroups: 2 per CU at Cin = 64
-        if (n_wgb > cap) n_wgb = cap < 8 ? 8 : cap;
-        const int64_t n_wgb8 = cdiv(n_wgb, 8) * 8;
-        dim3 grid((unsigned)(n_wgb8 * n_chunks));
-        const size_t lds = (size_t)2 * n_kc * 64 * 32 * sizeof(uint16_t) + (size_t)nw * (((n_off + 1) * 16 + 63) / 64 * 64) * 4 + 16;
+        if (p.n_wgb > cap) p.n_wgb = cap < 8 ? 8 : cap;
+        p.grid_x = cdiv(p.n_wgb, 8) * 8 * n_chunks;
+        p.lds = (size_t)2 * n_kc * 64 * 32 * sizeof(uint16_t) + (size_t)p.nw * (((n_off + 1) * 16 + 63) / 64 * 64) * 4 + 16;
+        return p;
+    }
+    p.lds = (size_t)n_off * ct * kcs * sizeof(uint16_t) + 16;
+    int wg_per_cu = (int)((160 * 1024) / p.lds);
+    if (wg_per_cu > 2) wg_per_cu = 2;
+    if (wg_per_cu < 1) wg_per_cu = 1;
+    p.n_tg = ((int64_t)scn::cu_budget() * wg_per_cu) / ((int64_t)n_chunks * n_kc);
+    if (p.n_tg > cdiv(nt, TB_NW)) p.n_tg = cdiv(nt, TB_NW);
+    if (p.n_tg < 1) p.n_tg = 1;
+    p.fused = n_kc > 1 && with_arrival && !(flags & SCN_F_SPLIT_SUM) &&
+              nt * n_chunks * n_kc * (int64_t)(TB_T * ct * 4) < (1ll << 31);
+    p.grid_x = p.n_tg * n_chunks * n_kc;
+    p.part = cin % kcs != 0;                                       // the last K-chunk has channel groups past Cin
+    // XCD-local hand-out (SCN_F_TILE_ORDER_X): possible when the slices of a tile group fall on 8 / n_slices whole groups of
+    // XCDs, i.e. 1, 2 or 4 slices; with 8 or more every XCD sees every tile group anyway
+    const int n_slices = n_chunks * n_kc;
+    const bool x_off = scn::sw(scn::SW_TB_NO_XORDER).set;             // (scn_debug_set: the tests switch it inside one process)
+    p.xbins = ((flags & SCN_F_TILE_ORDER_X) && !x_off && (n_slices == 1 || n_slices == 2 || n_slices == 4) && p.n_tg >= 8)
+                  ? 8 / n_slices : 1;
+    p.sum = n_kc > 1 && !p.fused;
+    p.sum_v = p.sum ? (tb_sum_v4(cout, y_bits, s_bits) ? 4 : 1) : 0;
+    return p;
+}
+}  // namespace
+
+// What the launcher rejects about the sizes of a call (the pointers apart)
+#define TB_REQUIRE_SIZES()                                                                                          \
+    do {                                                                                                            \
+        SCN_REQUIRE(n_off >= 1 && n_off <= 27 && n_out >= 0 && n_in >= 0 && cin >= 8 && cout >= 1);                 \
+        SCN_REQUIRE(cin % 8 == 0);                                   /* 16-byte row pieces of X (any cout) */        \
+    } while (0)
+#define TB_REQUIRE_RANGES()                                                                                         \
+    do {                                                                                                            \
+        SCN_REQUIRE(n_in < (1ll << 23) && n_in * cin * 2 < (1ll << 32) - (1ll << 24));    /* 24-bit rows, 32-bit offsets */ \
+        SCN_REQUIRE(n_out < (1ll << 23));                /* the tile table is addressed with 31-bit byte offsets */  \
+    } while (0)
+
+extern "C" int scn_conv_tiles_bf16_plan_describe(int64_t n_in, int cin, int n_off, int64_t n_out, int cout, int flags,
+                                                 int with_arrival, int y_ptr_bits, int scratch_ptr_bits, int64_t out[18]) {
+    SCN_REQUIRE(out != nullptr);
+    TB_REQUIRE_SIZES();
+    SCN_REQUIRE(y_ptr_bits >= 0 && y_ptr_bits < 16 && scratch_ptr_bits >= 0 && scratch_ptr_bits < 16);
+    SCN_REQUIRE((y_ptr_bits & 1) == 0 && (scratch_ptr_bits & 3) == 0);        // bf16 / float buffers
+    memset(out, 0, 18 * sizeof(int64_t));
+    if (n_out == 0) return SCN_OK;
+    TB_REQUIRE_RANGES();
+    const TbPlan p = tb_plan(cin, n_off, n_out, cout, flags, with_arrival != 0, (unsigned)y_ptr_bits, (unsigned)scratch_ptr_bits);
+    const int64_t v[18] = {p.stream, p.ks, p.nw, p.n_wgb, p.sh.nb, p.sh.kh, p.fused, p.part, p.sh.n_kc, p.sh.n_chunks, p.n_tg,
+                           p.grid_x, p.xbins, p.vec_ok, p.sum, p.sum_v, p.nt, (int64_t)p.lds};
+    memcpy(out, v, sizeof(v));
+    return SCN_OK;
+}
+
+extern "C" int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, const int32_t* tstab,
+                                   const uint32_t* tile_mask, const int32_t* perm, const int32_t* tile_order, int n_off,
+                                   int64_t n_out, const uint16_t* image, const float* bias, const uint16_t* residual,
+                                   const uint16_t* relu_mask, uint16_t* Y, int cout, int flags, void* scratch,
+                                   int32_t* arrival, scn_stream_t stream) {
+    TB_REQUIRE_SIZES();
+    if (n_out == 0) return SCN_OK;
+    SCN_REQUIRE(X && tstab && tile_mask && perm && tile_order && image && Y && scratch);
+    SCN_REQUIRE((((uintptr_t)X | (uintptr_t)image) & 15) == 0);
+    TB_REQUIRE_RANGES();
+    float* slabs = (float*)((char*)scratch + 256);
+    const TbPlan pl = tb_plan(cin, n_off, n_out, cout, flags, arrival != nullptr,
+                              (unsigned)(((uintptr_t)Y | (uintptr_t)residual | (uintptr_t)relu_mask) & 15),
+                              (unsigned)(((uintptr_t)slabs | (uintptr_t)bias) & 15));
+    const int64_t nt = pl.nt;
+    const int nb = pl.sh.nb, kh = pl.sh.kh, n_chunks = pl.sh.n_chunks, n_kc = pl.sh.n_kc;
+    const size_t lds = pl.lds;
+    dim3 grid((unsigned)pl.grid_x);
+    hipStream_t st = S(stream);
+    if (pl.stream) {
+        const int nw = pl.nw;
+        const int64_t n_wgb = pl.n_wgb;
 #define LAUNCH_TBS(KS_, NO_, NW_, D_)                                                                                  \
     do {                                                                                                            \
         static scn::DeviceOnce attr_set;                                                                               \
@@ -925,33 +1032,16 @@ extern "C" int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, con
         if (n_off == 27) { if (nw == 8) LAUNCH_TBS(KS_, 27, 8, D_); else LAUNCH_TBS(KS_, 27, 4, D_); }              \
         else { if (nw == 8) LAUNCH_TBS(KS_, 8, 8, D_); else LAUNCH_TBS(KS_, 8, 4, D_); }                            \
     } while (0)
-        if (n_kc == 2) PICK_TBS(2, 4);
-        else if (n_kc == 4) PICK_TBS(4, 4);
+        if (pl.ks == 2) PICK_TBS(2, 4);
+        else if (pl.ks == 4) PICK_TBS(4, 4);
         else PICK_TBS(8, 2);
 #undef PICK_TBS
 #undef LAUNCH_TBS
         SCN_LAUNCH_CHECK();
         return SCN_OK;
     }
-    float* slabs = (float*)((char*)scratch + 256);
-    const size_t lds = (size_t)n_off * ct * kcs * sizeof(uint16_t) + 16;
-    int wg_per_cu = (int)((160 * 1024) / lds);
-    if (wg_per_cu > 2) wg_per_cu = 2;
-    if (wg_per_cu < 1) wg_per_cu = 1;
-    int64_t n_tg = ((int64_t)scn::cu_budget() * wg_per_cu) / ((int64_t)n_chunks * n_kc);
-    if (n_tg > cdiv(nt, TB_NW)) n_tg = cdiv(nt, TB_NW);
-    if (n_tg < 1) n_tg = 1;
-    const bool fused = n_kc > 1 && arrival != nullptr && !(flags & SCN_F_SPLIT_SUM) &&
-                       nt * n_chunks * n_kc * (int64_t)(TB_T * ct * 4) < (1ll << 31);
-    dim3 grid((unsigned)(n_tg * n_chunks * n_kc));
-    hipStream_t st = S(stream);
-    const bool part = cin % kcs != 0;                              // the last K-chunk has channel groups past Cin
-    // XCD-local hand-out (SCN_F_TILE_ORDER_X): possible when the slices of a tile group fall on 8 / n_slices whole groups of
-    // XCDs, i.e. 1, 2 or 4 slices; with 8 or more every XCD sees every tile group anyway
-    const int n_slices = n_chunks * n_kc;
-    const bool x_off = scn::sw(scn::SW_TB_NO_XORDER).set;             // (scn_debug_set: the tests switch it inside one process)
-    const int xbins = ((flags & SCN_F_TILE_ORDER_X) && !x_off && (n_slices == 1 || n_slices == 2 || n_slices == 4) &&
-                       n_tg >= 8) ? 8 / n_slices : 1;
+    const bool fused = pl.fused, part = pl.part;
+    const int xbins = pl.xbins;
 #define LAUNCH_TB(N, K, FU, PT)                                                                                     \
     do {                                                                                                            \
         static scn::DeviceOnce attr_set;                                                                               \
@@ -977,11 +1067,9 @@ extern "C" int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, con
 #undef PICK_TB
 #undef LAUNCH_TB
     SCN_LAUNCH_CHECK();
-    if (n_kc > 1 && !fused) {
+    if (pl.sum) {
         const int rl = (flags & SCN_F_RESIDUAL_LAST) ? 1 : 0;
-        const bool v4 = cout % 4 == 0 && ((((uintptr_t)slabs | (uintptr_t)bias) & 15) == 0) &&
-                        ((((uintptr_t)Y | (uintptr_t)residual | (uintptr_t)relu_mask) & 7) == 0);
-        if (v4)
+        if (pl.sum_v == 4)
             hipLaunchKernelGGL(k_conv_tb_sum<4>, dim3(scn::ew_grid(n_out * cout / 4, 256)), dim3(256), 0, st,
                                (const float*)slabs, n_kc, (long long)n_out, cout, bias, residual, relu_mask, Y, rl);
         else
@@ -991,3 +1079,5 @@ extern "C" int scn_conv_tiles_bf16(const uint16_t* X, int64_t n_in, int cin, con
     }
     return SCN_OK;
 }
+#undef TB_REQUIRE_RANGES
+#undef TB_REQUIRE_SIZES

@@ -18,8 +18,8 @@ Every case
   * a second identical call into the same scratch and arrival buffers gives the same bits.
 
 Misaligned pointers are one float off a 16-byte boundary.  The scratch is misaligned only without an arrival array (the fused
-form stores 16-byte pieces to it).  Out of scope: scn_conv_tiles_bf16 (test_fuzz_conv_tiles_bf16, the bf16 parity tests),
-scn_conv_tiles_chain (tests/test_gpu_chain.py), the >= 2^23-row limits of the fast path.
+form stores 16-byte pieces to it).  scn_conv_tiles_bf16 has the same kind of file: tests/test_gpu_conv_bf16_paths.py.  Out of
+scope: scn_conv_tiles_chain (tests/test_gpu_chain.py), the >= 2^23-row limits of the fast path.
 """
 import ctypes as C
 

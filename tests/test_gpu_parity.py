@@ -1394,20 +1394,21 @@ def test_conv_tiles_bf16_forward_and_backward_data(gpu, cin, cout, relu_in):
                                             image=img))
 
 
-def _bf16_image_restated(W, cin, cout, n_off, wt, rev):
-    """The documented layout of the bf16 weight image (scn_conv_ts_bf16.hip: image[chunk * n_kc + kci][o][n = 16 nb + i][kk] =
-    bf16(W[o'][k = 32 kci + kk][col = ct chunk + NB i + nb]), zero outside the layer; NB = 4 / ct = 64 above 32 output columns,
-    else 2 / 32) built with torch indexing -> int16 bit patterns."""
-    nb = 4 if cout > 32 else 2
-    ct, n_chunks, n_kc = 16 * nb, -(-cout // (16 * nb)), -(-cin // 32)
+def _bf16_image_restated(W, cin, cout, n_off, wt, rev, nb=None, kh=1):
+    """The documented layout of the bf16 weight image (scn_conv_ts_bf16.hip: image[chunk * n_kc + kci][o][plane h][n = 16 nb + i]
+    [kk] = bf16(W[o'][k = 32 KH kci + 32 h + kk][col = ct chunk + NB i + nb]), zero outside the layer; NB = 4 / ct = 64 above 32
+    output columns, else 2 / 32, unless SCN_TB_NB forces one (`nb`); KH = 1 plane per K-chunk, 2 under SCN_TB_KH=2 (`kh`, which
+    also makes NB 2)) built with torch indexing -> int16 bit patterns."""
+    nb = nb or (4 if cout > 32 else 2)
+    ct, n_chunks, n_kc = 16 * nb, -(-cout // (16 * nb)), -(-cin // (32 * kh))
     Wd = W.flip(0) if rev else W
     Wd = Wd.transpose(1, 2) if wt else Wd                              # -> [o][k][col]
-    full = torch.zeros(n_off, n_kc * 32, n_chunks * ct)
+    full = torch.zeros(n_off, n_kc * 32 * kh, n_chunks * ct)
     full[:, :cin, :cout] = Wd
     n = torch.arange(ct)
     col_of_n = nb * (n % 16) + n // 16                                 # n = 16 nb_idx + i  ->  local column NB i + nb_idx
-    img = full.view(n_off, n_kc, 32, n_chunks, ct)[..., col_of_n]      # [o][kci][kk][chunk][n]
-    img = img.permute(3, 1, 0, 4, 2).contiguous()                      # [chunk][kci][o][n][kk]
+    img = full.view(n_off, n_kc, kh, 32, n_chunks, ct)[..., col_of_n]  # [o][kci][h][kk][chunk][n]
+    img = img.permute(4, 1, 0, 2, 5, 3).contiguous()                   # [chunk][kci][o][h][n][kk]
     return img.to(torch.bfloat16).view(torch.int16).reshape(-1)
 
 
@@ -1432,6 +1433,43 @@ def test_bf16_weight_image_layout_bit_for_bit(gpu, cin, cout, n_off):
         for flags, want, (ci, co) in cases:
             got = F.packed_image(Wg, ci, co, n_off, flags).view(torch.int16).cpu()
             assert torch.equal(got, want), flags
+
+
+@pytest.mark.parametrize("cin,cout,n_off,sw,nb,kh", [
+    (64, 64, 27, {"SCN_TB_KH": 2}, None, 2), (96, 32, 27, {"SCN_TB_KH": 2}, None, 2), (72, 48, 8, {"SCN_TB_KH": 2}, None, 2),
+    (32, 64, 27, {"SCN_TB_NB": 2}, 2, 1), (32, 16, 8, {"SCN_TB_NB": 4}, 4, 1),
+    (30, 24, 8, {}, None, 1), (64, 70, 8, {}, None, 1)])
+def test_bf16_weight_image_layout_under_the_shape_switches_and_on_the_scalar_routes(gpu, cin, cout, n_off, sw, nb, kh):
+    """The same restatement for what the default shapes do not reach: the plane dimension of SCN_TB_KH=2 (a full second plane, a
+    dead one, a partial first one), SCN_TB_NB forced both ways, and the scalar read routes of tb_pack_unit under
+    SCN_F_W_TRANSPOSED -- a W pointer one float off its 16-byte boundary, and a row length that is no multiple of 4 (the layer
+    (cout -> cin) read as [o][col][k] has rows of `cout` floats: 70 is none; 16, 24, 32, 48, 64 stay on the 16-byte route while
+    W is aligned; (30, 24) adds a forward image whose last K-chunk is cut inside a 16-byte piece) -- through both entry points,
+    forward and backward-data image, W_TRANSPOSED and OFF_REVERSE also one at a time."""
+    import contextlib
+    from sparse_rcnn_amd import functional as F, _lib as L
+    g = torch.Generator().manual_seed(cin * 1000 + cout + 7)
+    W = torch.randn(n_off, cin, cout, generator=g)
+    flat = torch.empty(W.numel() + 1, device=gpu)
+    flat[1:] = W.reshape(-1).to(gpu)
+    Wg, Wg_off = W.to(gpu), flat[1:].view(n_off, cin, cout)
+    assert Wg.data_ptr() % 16 == 0 and Wg_off.data_ptr() % 16 == 4
+    back = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
+    # as above: the backward-data image of [o][cin][cout] is the image of a (cout -> cin) layer stored [o][col][k]
+    cases = [(0, False, False, (cin, cout)), (back, True, True, (cout, cin)), (L.F_W_TRANSPOSED, True, False, (cout, cin)),
+             (L.F_OFF_REVERSE, False, True, (cin, cout))]
+    with contextlib.ExitStack() as st:
+        for k, v in sw.items():
+            st.enter_context(L.debug_switch(k, v))
+        for flags, wt, rev, (ci, co) in cases:
+            k2 = kh if ci > 32 else 1                                 # (tb_shape: one plane up to 32 input channels; two make NB 2)
+            want = _bf16_image_restated(W, ci, co, n_off, wt, rev, nb=2 if k2 == 2 else nb, kh=k2)
+            for w in (Wg, Wg_off):
+                got = F.pack_weights_bf16(w, ci, co, n_off, flags).view(torch.int16).cpu()
+                assert got.numel() == want.numel() and torch.equal(got, want), (flags, w.data_ptr() % 16, int((got != want).sum()))
+            with F.packed_weights([(Wg_off, ci, co, n_off, flags), (Wg, ci, co, n_off, flags)]):
+                for w in (Wg, Wg_off):
+                    assert torch.equal(F.packed_image(w, ci, co, n_off, flags).view(torch.int16).cpu(), want), flags
 
 
 def test_conv_tiles_bf16_rejects_unsupported_inputs(gpu):
