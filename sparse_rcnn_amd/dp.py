@@ -328,3 +328,10 @@ class FlatParams:
 def broadcast_params(fp: FlatParams, src: int = 0):
     if _dist_on(2):
         dist.broadcast(fp.flat, src)
+
+
+def broadcast_tensors(tensors, src: int = 0):
+    """Tensors outside a flat buffer (a step's frozen parameters), one collective each, once; nothing without a second rank."""
+    if _dist_on(2):
+        for t in tensors:
+            dist.broadcast(t, src)

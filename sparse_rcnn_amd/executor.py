@@ -24,6 +24,11 @@ SCN_OP_BN_FWD writing a slab of its own, SCN_OP_BN_BWD on the way back; its batc
 and the host applies the running-statistics update after the forward call (`run_stage`), with the statements
 functional.BatchNormReLUFunction uses.
 
+Frozen parts (trainstep.SceneStep(train=...), or any caller that sets requires_grad False): a stage none of whose operands
+requires a gradient runs the forward-only slab plan (`_lean`), and a backward pass runs only the ops of the stored list that
+what autograd asks for needs (`Stage.backward_pass`: frozen parameters drop the weight-gradient ops, inputs that need no gradient
+the backward-data ops nothing else reads); what still runs gives the same bits.
+
 Not covered (the layer-by-layer path runs instead): batch norm without `bn_stages`, `bf16_blocks=True` (casts around every
 run of units), channel plans the two-source NetworkInNetwork kernel does not take, empty levels, and any step in which
 `profiling.TIMER` brackets single launches with events.  A batch-norm network also steps aside while `modules._BatchNorm.SYNC`
@@ -579,7 +584,8 @@ class Stage:
         self.stat_entries = [(k, d[1], "running_mean" if d[0] == "rm" else "running_var") for k, d in enumerate(self.params)
                              if d[0] in ("rm", "rv")]
         self.bn_phys = frozenset(2 * i + j for i, (m, _) in enumerate(self.mods) if isinstance(m, M._BatchNorm) for j in (0, 1))
-        self.grad_views = {}                              # tuple of parameter shapes -> (region offsets, total, views)
+        self.grad_views = {}                              # (parameter shapes, regions of the pass) -> (region offsets, total, views)
+        self._bwd_passes = {}                             # (inputs need a gradient, parameters need one) -> _BackwardPass
         # a main-path unit that ends the stage: its backward masks by the stage's OUTPUT slab, which then is saved for backward
         self.bwd_reads_out = any(getattr(op, f) == self.out_id for op in self.bwd for f in ("x", "y", "r", "m", "x1", "y1"))
         self._lean_slots()
@@ -589,6 +595,94 @@ class Stage:
         if covered != want:
             raise RuntimeError("executor plan: every parameter must sit in exactly one gradient region")
         return self
+
+
+_BUF_FIELDS = ("x", "y", "r", "m", "x1", "y1")
+_WGRAD_OPS = (OP_WGRAD_SUBM, OP_WGRAD_DOWN, OP_WGRAD_UP, OP_WGRAD_IDENT)
+
+
+def _op_io(op):
+    """(buffer ids read, buffer ids written, gradient regions written) of one op, as run_op in csrc/scn_exec.hip uses its fields."""
+    k = op.op
+    if k in (OP_GEMM_IDENT, OP_CONV_SUBM, OP_CONV_CHILD):
+        io = (op.x, op.r, op.m), (op.y,), ()
+    elif k == OP_RULES_CHILD:
+        io = (op.x, op.m), (op.y,), ()
+    elif k == OP_ROWS2:                       # y1 >= 0: one source, two destinations (backward-data of the NiN over a JoinTable)
+        io = ((op.x,), (op.y, op.y1), ()) if op.y1 >= 0 else ((op.x, op.x1), (op.y,), ())
+    elif k in _WGRAD_OPS:
+        io = (op.x, op.y), (), (op.w, op.b)
+    elif k == OP_WGRAD2_SUBM:
+        io = (op.x, op.y, op.x1, op.y1), (), (op.w, op.b)
+    elif k == OP_COLSUM:
+        io = (op.x,), (), (op.b,)
+    elif k in (OP_ADD, OP_ADD_RELU):
+        io = (op.x, op.x1), (op.y,), ()
+    elif k in (OP_CAST, OP_RELU, OP_BN_STATS):
+        io = (op.x,), (op.y,), ()
+    elif k == OP_RELU_BWD:
+        io = (op.m, op.x1), (op.y,), ()
+    elif k == OP_BN_FWD:
+        io = (op.x, op.x1), (op.y,), ()
+    elif k == OP_BN_BWD:                      # dx and dgamma | dbeta leave one launch
+        io = (op.x, op.m, op.x1), (op.y,), (op.b,)
+    else:
+        raise RuntimeError(f"executor plan: unknown op {k}")
+    return tuple(tuple(v for v in part if v >= 0) for part in io)
+
+
+class _BackwardPass(NamedTuple):
+    """What one backward call runs: the stored list, or the part of it that autograd's request needs (`Stage.backward_pass`)."""
+    ops: list                   # ExecOp, in the order of `Stage.bwd`
+    arr: object                 # the same as a ctypes array
+    ws: list                    # ids of the backward workspace slabs a kept op names
+    specs: list                 # their (level, row bytes)
+    dins: frozenset             # input-gradient ids a kept op writes
+    regions: frozenset          # gradient regions a kept op writes
+
+
+def _backward_pass(self, inputs=True, params=True):
+    """The backward pass for a request (do the inputs need a gradient, do the parameters), derived once from the unchanged
+    `bwd` list by a reverse liveness pass over WHOLE ops: an op stays when it writes a needed input-gradient slab, a needed
+    gradient region or a slab a later kept op reads; an op with several outputs stays whole when any of them is live.  Kept ops
+    keep every field and their order, so what still runs gives the bits of the full pass.  (Every slab of a backward list is
+    written by one op, so a write ends no liveness here: the pass only ever adds to the live set.)"""
+    key = (bool(inputs), bool(params))
+    got = self._bwd_passes.get(key)
+    if got is not None:
+        return got
+    if key == (True, True):
+        got = _BackwardPass(self.bwd, self.bwd_arr, self.bwd_ws, self.bwd_specs, frozenset(self.din_ids),
+                            frozenset(range(len(self.gregions))))
+    else:
+        live = set(self.din_ids) if key[0] else set()
+        keep = [False] * len(self.bwd)
+        for t in range(len(self.bwd) - 1, -1, -1):
+            reads, writes, regions = _op_io(self.bwd[t])
+            if (key[1] and regions) or any(v in live for v in writes):
+                keep[t] = True
+                live.update(reads)
+        ops = [op for op, k in zip(self.bwd, keep) if k]
+        named, written, regions = set(), set(), set()
+        for op in ops:
+            r, w, g = _op_io(op)
+            named.update(r, w)
+            written.update(w)
+            regions.update(g)
+        ws = [i for i in self.bwd_ws if i in named]
+        got = _BackwardPass(ops, (ExecOp * len(ops))(*ops), ws, [(self.bufs[i][0], self.bufs[i][1] * self.bufs[i][2]) for i in ws],
+                            frozenset(i for i in self.din_ids if i in written), frozenset(regions))
+    self._bwd_passes[key] = got
+    return got
+
+
+def _backward_ops(self, inputs=True, params=True):
+    """The ops a backward pass runs when the stage's inputs / its parameters need a gradient (`backward_pass`), for inspection."""
+    return list(self.backward_pass(inputs, params).ops)
+
+
+Stage.backward_pass = _backward_pass
+Stage.backward_ops = _backward_ops
 
 
 def _lean_slots(self):
@@ -974,6 +1068,7 @@ def _step_eligible(stage, kept, needs, pending=()):
 
 
 LAST_FORWARD = {"lean": False, "ws_bytes": 0}      # what the last stage forward did (tests)
+LAST_BACKWARD = {"ops": 0, "of": 0}                # ops the last stage backward ran, out of the stage's stored list (tests)
 
 
 def _lean(inputs, phys):
@@ -1060,6 +1155,14 @@ class StageFunction(torch.autograd.Function):
     def backward(ctx, dout):
         kept = ctx.saved_tensors                 # (raises when the graph's buffers have been freed)
         stage, levels, ptab = ctx.stage, ctx.levels, ctx.ptab
+        n_in = stage.n_inputs
+        needs_in, needs_p = ctx.needs_input_grad[3:3 + n_in], ctx.needs_input_grad[3 + n_in:]
+        # what autograd asked for decides what runs: frozen parameters drop the weight-gradient ops, inputs that need no gradient
+        # the backward-data ops nothing else reads (`Stage.backward_pass`; everything needed: the stored list itself)
+        bp = stage.backward_pass(any(needs_in), any(needs_p))
+        LAST_BACKWARD["ops"], LAST_BACKWARD["of"] = len(bp.ops), len(stage.bwd)
+        if not bp.ops:
+            return (None,) * (3 + n_in + len(needs_p))
         table = type(ctx.table).from_buffer_copy(ctx.table)      # a fresh table per pass: the forward's entries stay as they were
         ns = levels[2]
         dev = dout.device
@@ -1067,24 +1170,33 @@ class StageFunction(torch.autograd.Function):
         dout = dout.contiguous()
         if dout.element_size() != es:
             dout = dout.to(torch.float32 if es == 4 else torch.bfloat16)
-        offs, total = _layout(stage.bwd_specs, ns)
+        offs, total = _layout(bp.specs, ns)
         ws = torch.empty(max(total, 256), dtype=torch.uint8, device=dev)
         base = ws.data_ptr()
-        for i, o in zip(stage.bwd_ws, offs):
+        for i, o in zip(bp.ws, offs):
             table[i] = base + o
         table[stage.dout_id] = dout.data_ptr()
-        dins = []
-        for i in stage.din_ids:
+        dins, unasked = [], []
+        for i, need in zip(stage.din_ids, needs_in):
+            if i not in bp.dins:                 # no kept op writes it (and nobody asked for it)
+                dins.append(None)
+                continue
             blv, bch, bes, _ = stage.bufs[i]
             t = torch.empty((ns[blv], bch), dtype=torch.float32 if bes == 4 else torch.bfloat16, device=dev)
-            dins.append(t)
+            dins.append(t if need else None)     # (a slab a kept op writes beside a needed one: it lives until the pass is queued)
+            if not need:
+                unasked.append(t)
             table[i] = t.data_ptr()
-        # gradient regions back to back in one fp32 buffer; the returned gradients are views of it
+        # the gradient regions of the pass back to back in one fp32 buffer; the returned gradients are views of it
         shapes = ctx.phys_shapes
-        cached = stage.grad_views.get(shapes)
+        all_regions = len(bp.regions) == len(stage.gregions)
+        cached = stage.grad_views.get((shapes, None if all_regions else bp.regions))
         if cached is None:
             goffs, gtot, views = [], 0, [None] * len(shapes)
-            for reg in stage.gregions:
+            for k, reg in enumerate(stage.gregions):
+                if k not in bp.regions:
+                    goffs.append(None)
+                    continue
                 goffs.append(gtot)
                 start = gtot
                 for mi, kind in reg:
@@ -1098,26 +1210,29 @@ class StageFunction(torch.autograd.Function):
                 if gtot == start:                    # (plans are only compiled for layers WITH bias: _require_bias)
                     raise L.ScnError("executor: a gradient region without a tensor (bias=None layer in a compiled stage)")
                 gtot = (gtot + 63) & ~63
-            cached = stage.grad_views[shapes] = (goffs, gtot, views)
+            cached = stage.grad_views[(shapes, None if all_regions else bp.regions)] = (goffs, gtot, views)
         goffs, gtot, views = cached
+        if not any(needs_p):                     # (a batch-norm backward-data op still writes its dgamma | dbeta: nobody reads them)
+            views = [None] * len(shapes)
         flat = torch.empty(max(gtot, 1), dtype=torch.float32, device=dev)
         gtab = (vp * max(len(stage.gregions), 1))()
         gb = flat.data_ptr()
         for k, o in enumerate(goffs):
-            gtab[k] = gb + 4 * o
+            if o is not None:
+                gtab[k] = gb + 4 * o
         scope = getattr(_step_scope, "scope", None)
         late = None
-        if scope is not None:
-            late = _step_eligible(stage, kept, ctx.needs_input_grad[3 + stage.n_inputs:], scope.pending)
+        if scope is not None and any(needs_p):
+            late = _step_eligible(stage, kept, needs_p, scope.pending)
         if late is not None and L.lib().scn_wgrad_step_hold(1) == 1:
             # the C side holds this pass's weight-gradient launches and sums back until the scope's flush: the pass gets a
             # scratch allocation of its own, and the scope keeps what those launches touch
             own = []
             try:
-                _run(stage, stage.bwd_arr, levels, table, ptab, gtab, dev, own_scratch=own)
+                _run(stage, bp.arr, levels, table, ptab, gtab, dev, own_scratch=own)
             finally:
                 L.lib().scn_wgrad_step_hold(0)
-            scope.keep.append((kept, ws, dout, flat, own, levels, table, gtab))
+            scope.keep.append((kept, ws, dout, flat, own, levels, table, gtab, unasked))
             for j, p in late:
                 v = views[j]
                 scope.deliver.append((p, flat[v[0]:v[0] + v[1]].view(v[2])))
@@ -1125,7 +1240,7 @@ class StageFunction(torch.autograd.Function):
             scope.passes += 1
             return (None, None, None, *dins,
                     *[flat[v[0]:v[0] + v[1]].view(v[2]) if (j in stage.bn_phys and v is not None) else None for j, v in enumerate(views)])
-        _run(stage, stage.bwd_arr, levels, table, ptab, gtab, dev, side=True)
+        _run(stage, bp.arr, levels, table, ptab, gtab, dev, side=True)
         grads = [None if v is None else flat[v[0]:v[0] + v[1]].view(v[2]) for v in views]
         del kept
         return (None, None, None, *dins, *grads)

@@ -33,11 +33,12 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from .dp import FlatParams, broadcast_params
+from .dp import FlatParams, broadcast_params, broadcast_tensors
 from .maskhead import MaskBranch
 from .synthetic import make_batch, make_boxes, make_instances, make_segmentation
 from .unet import Backbone
 
+PARTS = ("backbone", "rpn", "class", "mask", "segmentation")      # what SceneStep(train=...) names: the sub-modules of its model
 REF_PLAN = (32, 48, 64, 80, 96, 112)      # the reference's own sparse U-Net plan, `arange * 16 + 32` (scannet_config/run.py:539-549,587-591)
 
 WORKLOADS = {      # name -> (channels, grid, active voxels per sample, boxes per scene, BASELINE.json entry, samples per rank)
@@ -207,8 +208,28 @@ class SceneStep:
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
                  upsample_heads=False, class_storage=None, simple_class=False, multitask_loss=False, loss_weights=None,
                  bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True,
-                 bn_stages=False):
-        """bn_stages (a "-bn" workload; False: nothing changes): the batch-norm backbone runs as step-executor stages, one
+                 bn_stages=False, train=None, init_state=None):
+        """train (None: nothing changes -- every parameter is trained): a non-empty tuple of part names out of `PARTS`
+        ("backbone", "rpn", "class", "mask", "segmentation"); the parameters of every part NOT named are frozen
+        (requires_grad False) before the flat buffer is built, so the flat buffer, the gradient buckets and the optimizer cover
+        the named parts only and a frozen parameter never receives a `.grad` -- the reference's training in stages:
+        `mask_only` (run.py:332,1420-1427: train=("mask",)) and `unet_tweak` (run.py:1414-1418: every part but "backbone").  A
+        requested loss is computed only if its gradient reaches a trainable parameter (the reference's `calc_* and not
+        mask_only`, run.py:891-893): the RPN loss with rpn or backbone trainable, the class loss with class or backbone (with
+        dense_class also rpn), the mask loss with mask or backbone, the segmentation loss with segmentation or backbone.  A loss
+        that is not computed queues no targets, draws or selector launches, its head is not run in forward_backward (predict()
+        and evaluate() still run it) and its attribute (`.rpn_losses`, ...) stays None; a root that requires no gradient gets no
+        synthetic gradient either.  The input features require a gradient only with "backbone" trainable: otherwise `.fin.grad`
+        stays None and the frozen parts run the executor's forward-only slab plan.  A name that is unknown or names a part the
+        step does not have, an empty tuple, or multitask_loss=True beside it: ValueError.  With more than one rank the frozen
+        parameters are broadcast once at construction.  `loss_weights` may name every requested loss; the container combines
+        the computed ones.
+        init_state (None: nothing changes): a `state_dict` of an earlier step's `.model`, the hand-over between stages, applied
+        before the flat buffer is built with the reference's `ignore_load` rule (run.py:1376-1410): every key present on both
+        sides is loaded, a shape mismatch on such a key is a ValueError, everything else keeps its own initialisation.
+        `.init_missing`: the model keys the dict lacked; `.init_unused`: the dict keys the model lacks (the two lists the
+        reference prints).
+        bn_stages (a "-bn" workload; False: nothing changes): the batch-norm backbone runs as step-executor stages, one
         autograd node per level (unet.SparseUNet; the developer switch SCN_EXEC_BN=1 does the same for a step built without
         the keyword).  Same kernels, arguments and bits as the layer-by-layer path, which stays the default.
         bottleneck_divisor, main_path_relu (0 / False: nothing changes): the backbone's residual units take the reference's
@@ -383,6 +404,36 @@ class SceneStep:
         if dtype not in ("f32", "bf16", "bf16-blocks"):
             raise ValueError("dtype: f32 | bf16 | bf16-blocks")
         storage = {"f32": False, "bf16": "all", "bf16-blocks": True}[dtype]
+        have = {"backbone": True, "rpn": workload.endswith("-rpn"), "class": bool(class_loss), "mask": bool(self.n_boxes),
+                "segmentation": bool(segmentation_loss)}
+        if train is not None:
+            if isinstance(train, str):
+                raise ValueError("train: a tuple of part names required, e.g. train=('mask',), got the string " + repr(train))
+            train = tuple(train)
+            if not train:
+                raise ValueError("train: an empty tuple trains nothing; None trains every part")
+            for name in train:
+                if name not in PARTS:
+                    raise ValueError(f"train: unknown part {name!r} (the parts: " + ", ".join(PARTS) + ")")
+                if not have[name]:
+                    raise ValueError(f"train: this step has no part {name!r} (it has: " + ", ".join(p for p in PARTS if have[p]) + ")")
+            if multitask_loss:
+                raise ValueError("multitask_loss=True together with train: the learned log-weights of a step that trains only "
+                                 "some parts are not provided")
+        self.train = train
+        self.trainable = tuple(p for p in PARTS if have[p] and (train is None or p in train))
+        self.frozen = tuple(p for p in PARTS if have[p] and p not in self.trainable)
+        on = set(self.trainable)
+        # a requested loss is computed only if its gradient reaches a trainable parameter (run.py:891-893 `calc_* and not mask_only`)
+        computed = {"rpn": bool(rpn_loss) and bool(on & {"rpn", "backbone"}),
+                    "class": bool(class_loss) and bool(on & ({"class", "backbone", "rpn"} if dense_class else {"class", "backbone"})),
+                    "mask": bool(mask_loss) and bool(on & {"mask", "backbone"}),
+                    "segmentation": bool(segmentation_loss) and bool(on & {"segmentation", "backbone"})}
+        requested = {"rpn": bool(rpn_loss), "class": bool(class_loss), "mask": bool(mask_loss), "segmentation": bool(segmentation_loss)}
+        self.losses_not_computed = tuple(k for k in requested if requested[k] and not computed[k])
+        self._computed = computed
+        # the mask branch runs in forward_backward when something trainable lies under its logits
+        self._run_mask = bool(self.n_boxes) and bool(on & {"mask", "backbone"})
         self._scenes = []
         self.from_batches = batches is not None
         # level constraint on a batch's spatial size: every 2^3/2 convolution halves an even size -- levels - 1 in the backbone,
@@ -431,7 +482,7 @@ class SceneStep:
             from .loss import LossCombiner
             self.combiner = self.model.loss_combiner = LossCombiner(
                 tuple(self._loss_weights.values()), self.multitask_loss,
-                has=(bool(rpn_loss), bool(class_loss), bool(mask_loss), bool(segmentation_loss))).to(self.device)
+                has=(computed["rpn"], computed["class"], computed["mask"], computed["segmentation"])).to(self.device)
         if self.with_rpn:
             self._init_rpn()
         self.rpn_loss = bool(rpn_loss)
@@ -485,8 +536,18 @@ class SceneStep:
                 sc["gt_dev"] = [b.float().to(self.device) for b in sc["gt_boxes"]]
                 if self.segmentation_loss:             # one label per point row, in the batch's row order (sample-major)
                     sc["seg_target"] = torch.cat(make_segmentation(labels, masks)).to(self.device)
+        self.init_missing = self.init_unused = None
+        if init_state is not None:
+            self.init_missing, self.init_unused = self._load_init_state(init_state)
+        frozen_params = []
+        if self.train is not None:
+            for name in self.frozen:
+                for p in self._part(name).parameters():
+                    p.requires_grad_(False)
+                    frozen_params.append(p)
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
+        broadcast_tensors([p.data for p in frozen_params])      # (more than one rank: the frozen parameters are equal everywhere too)
         if self.combiner is not None:
             self._root_grad = torch.zeros(L.LOSS_TERMS, dtype=torch.float32, device=self.device)
             self._root_grad_views = [self._root_grad[i] for i in range(L.LOSS_TERMS)]
@@ -517,6 +578,26 @@ class SceneStep:
         self.out = self.logits = self.fin = None
 
     # ------------------------------------------------------------------------------------------------------------
+    def _part(self, name):
+        """The sub-module of the step's model that `train=` calls `name` (PARTS)."""
+        m = self.model
+        return {"backbone": m.backbone, "rpn": m.rpn, "class": m.class_branch, "mask": m.mask, "segmentation": m.segmentation}[name]
+
+    def _load_init_state(self, state):
+        """The reference's `ignore_load` (run.py:1376-1410) on the step's model: every key of `state` the model has is copied
+        in (a shape mismatch: ValueError), everything else keeps its initialisation.
+        -> (model keys `state` lacks, keys of `state` the model lacks)."""
+        own = self.model.state_dict()
+        for key, v in own.items():
+            got = state.get(key)
+            if got is not None and tuple(got.shape) != tuple(v.shape):
+                raise ValueError(f"init_state[{key!r}]: shape {tuple(got.shape)} where the model has {tuple(v.shape)}")
+        with torch.no_grad():
+            for key, v in own.items():
+                if key in state:
+                    v.copy_(state[key].to(device=v.device, dtype=v.dtype))
+        return [k for k in own if k not in state], [k for k in state if k not in own]
+
     def _scene_from_batch(self, batch, k):
         """The scene dict of micro-batch k from a collated batch (sample.collate / the reference's collate_fn layout)."""
         from .loss import PackedMasks, pack_gt_masks
@@ -624,10 +705,10 @@ class SceneStep:
         `rpn_bbox`, `class`, `mask`, `segment` (one copy; without a container every weight is 1)."""
         if self.combiner is not None:
             return self.combiner.get_weights()
-        out = {}
-        if self.rpn_loss:
+        out, do = {}, self._computed
+        if do["rpn"]:
             out["rpn_score"] = out["rpn_bbox"] = 1.0
-        for key, on in (("class", self.class_loss), ("mask", self.mask_loss), ("segment", self.segmentation_loss)):
+        for key, on in (("class", do["class"]), ("mask", do["mask"]), ("segment", do["segmentation"])):
             if on:
                 out[key] = 1.0
         return out
@@ -646,7 +727,9 @@ class SceneStep:
         if k != self._k:
             self._use_scene(k)
         scale = 1.0 / self.batches_per_step
-        fin = self.feats.detach().requires_grad_()
+        do = self._computed                     # which of the requested losses this step computes (train=None: all of them)
+        # (a frozen backbone takes the features as they are: nothing below it asks for a gradient, its stages run forward-only)
+        fin = self.feats.detach().requires_grad_() if "backbone" in self.trainable else self.feats
         md = self._take_index(k)
         # the index structures of the NEXT batch depend on its coordinates only (a data loader's output): a helper thread
         # builds them on the high-priority index stream while this batch runs; every step contains one complete build
@@ -666,10 +749,10 @@ class SceneStep:
         # boxes of a step are known before its backbone runs (here: synthetic; in the reference: the RPN's proposals of
         # the same forward, so this applies to the mask branch's SECOND use of a scene, e.g. evaluation on cached proposals)
         cut = None
-        if m.mask is not None and EARLY_ROI_CUT and not self.mask_loss:
+        if m.mask is not None and EARLY_ROI_CUT and not self.mask_loss and self._run_mask:
             cut = m.mask.prepare_cut(self.coords, self.size, self.boxes)      # (resident int64 coords: no dependency on md)
         rpn_prep = None
-        if self.rpn_loss:
+        if do["rpn"]:
             # the RPN loss's targets and draw depend on the anchors (the scene shape) and the boxes only: queued ahead of the
             # backbone, they overlap nothing the forward waits for
             calc, gt, offs = self._rpn_target_setup(k)
@@ -677,7 +760,8 @@ class SceneStep:
             rpn_prep = (ov, am, tg) + tuple(self.rpn_criterion.bbox_target_selector(ov))
         out = m.backbone(self.coords, fin, self.size, self.batch_size, metadata=md, after_encoder=hook)
         self._start_prefetch(k)      # (LATE_PREFETCH: the helper thread is started once this batch's forward kernels are queued)
-        if self.segmentation_loss:
+        roots, root_grads = [], []
+        if do["segmentation"]:
             # the reference's real gradient at the backbone output: the segmentation head's logits (fp32; bf16 storage widened)
             # against the scene's per-point labels, in place of the seeded N(0, 1) direction
             seg_logits = m.segmentation(out)
@@ -688,16 +772,18 @@ class SceneStep:
             seg_target = self._scenes[k]["seg_target"]
             self.segmentation_losses = self.segmentation_criterion(seg_logits, seg_target)
             self.segmentation_out = (seg_logits, seg_target)
-            root0, gys = self.segmentation_losses, self._seg_grad
+            roots, root_grads = [self.segmentation_losses], [self._seg_grad]
             terms[4], term_pos[4] = self.segmentation_losses, 0
+            self.n_active = int(out.features.shape[0]) * self.batches_per_step
+        elif not out.features.requires_grad:
+            # nothing trainable under the backbone output: no root here, and no synthetic gradient is drawn for one
             self.n_active = int(out.features.shape[0]) * self.batches_per_step
         else:
             gy = self._gys.get(k)
             if gy is None or gy.shape != out.features.shape:
                 gy = self._gys[k] = torch.randn(out.features.shape, generator=self._gen).to(self.device)   # upstream grad dY ~ N(0,1)
                 self.n_active = sum(g.shape[0] for g in self._gys.values())
-            gys = gy if scale == 1.0 else gy * scale
-            root0 = out.features
+            roots, root_grads = [out.features], [gy if scale == 1.0 else gy * scale]
         if self.weighting == "count":             # before backward: the bucketed path scales slices as it packs them
             import torch.distributed as dist
             self.flat.rank_weight = float(out.features.shape[0])
@@ -709,11 +795,11 @@ class SceneStep:
         if m.mask is None:
             if zero:
                 self.flat.zero_grad()
-            _backward([root0], [gys], step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
+            _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
             logits = None
         else:
             scene = (self.coords, fin, self.size, self.batch_size, self.splits)
-            boxes, roots, root_grads = self.boxes, [root0], [gys]
+            boxes = self.boxes
             if self.with_rpn:
                 # configs[2] as written (model.py:141-160): the proposals are this forward's -- dense heads on the coarsest
                 # encoder level, top-k + NMS on the device; the RPN losses' gradients arrive at rpn_bbox / rpn_score
@@ -724,7 +810,7 @@ class SceneStep:
                 self.rpn_out = (rpn_bbox, rpn_score, anchors, roi_score, boxes, roi_index)
                 descs = overlaps = None
                 proposals = boxes
-                if self.mask_loss:
+                if do["mask"]:
                     # model.py:172-196: OverlapCalculator + TrainSelector on this forward's proposals, one launch; the mask
                     # branch runs on the drawn proposals ++ every ground-truth box
                     sc = self._scenes[k]
@@ -732,10 +818,10 @@ class SceneStep:
                     boxes = list(boxes)
                 elif self.mask_boxes is not None:     # (the reference's mask head trains on <= 24 selected proposals per sample)
                     boxes = [b[:self.mask_boxes] for b in boxes]
-                if self.keep_rpn_grads:
+                if self.keep_rpn_grads and rpn_bbox.requires_grad:
                     rpn_bbox.retain_grad()
                     rpn_score.retain_grad()
-                if self.rpn_loss:
+                if do["rpn"]:
                     calc = self._rpn_targets[k][0]
                     if calc.anchors.data_ptr() != anchors.data_ptr() or calc.anchors.shape != anchors.shape:
                         raise L.ScnError("SceneStep: the RPN loss's anchors are not the ones the RPN returned")
@@ -744,14 +830,14 @@ class SceneStep:
                     term_pos[0], term_pos[1] = len(roots), len(roots) + 1
                     roots += list(self.rpn_losses)           # (score_loss + bbox_loss) / batches_per_step
                     root_grads += [self._rpn_grad, self._rpn_grad]
-                else:
+                elif rpn_bbox.requires_grad:               # (no RPN loss: the seeded direction, where a gradient can arrive)
                     gr = self._grs.get(k)
                     if gr is None or gr[0].shape != rpn_bbox.shape:
                         gr = self._grs[k] = tuple((torch.randn(t.shape, generator=self._gen) * 1e-3).to(self.device)
                                                   for t in (rpn_bbox, rpn_score))
                     roots += [rpn_bbox, rpn_score]
                     root_grads += [g if scale == 1.0 else g * scale for g in gr]
-            if self.class_loss:
+            if do["class"]:
                 # model.py:170-183: the class network's TrainSelector draws from the same overlap descriptions as the mask
                 # network's; the branch runs on its forward boxes (drawn proposals ++ every ground-truth box)
                 sc = self._scenes[k]
@@ -768,41 +854,44 @@ class SceneStep:
                 terms[2], term_pos[2] = self.class_losses, len(roots)
                 roots.append(self.class_losses)
                 root_grads.append(self._class_grad)
-            logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
-            gm = self._gms.get(k)
-            if self.mask_loss:
-                sc = self._scenes[k]
-                if self.keep_mask_grads and logits.requires_grad:
-                    logits.retain_grad()
-                self.mask_out = (selection, descs)
-                self.mask_losses = self.mask_criterion(logits, selection, descs, sc["gt_label"], sc["gt_mask"])
-                terms[3] = self.mask_losses
-                if self.mask_losses.requires_grad:
-                    term_pos[3] = len(roots)
-                    roots.append(self.mask_losses)
-                    root_grads.append(self._mask_grad)
-                self.n_roi_rows = int(logits.shape[0])
-            elif gm is None or gm.shape != logits.shape:
-                if self.with_rpn:
-                    # the proposals -- and with them the number of cropped points -- change from step to step: dM is a slice
-                    # of one device-resident pool (drawing 2 M normals on the host per step would be timed as part of it)
-                    pool = self._gm_pool
-                    if pool is None or pool.shape[0] < logits.shape[0] or pool.shape[1:] != logits.shape[1:]:
-                        rows = max(2 * logits.shape[0], 1 << 18)
-                        pool = self._gm_pool = torch.randn((rows,) + tuple(logits.shape[1:]), generator=self._gen).to(self.device)
-                    gm = self._gms[k] = pool[:logits.shape[0]]
-                else:
-                    gm = self._gms[k] = torch.randn(logits.shape, generator=self._gen).to(self.device)
-                self.n_roi_rows = sum(g.shape[0] for g in self._gms.values())
-            if logits.requires_grad and logits.shape[0] and not self.mask_loss:
-                roots.append(logits)
-                root_grads.append(gm if scale == 1.0 else gm * scale)
+            logits = None
+            if self._run_mask:         # (else: mask branch and backbone frozen -- nothing trainable lies under the logits)
+                logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
+                gm = self._gms.get(k)
+                if do["mask"]:
+                    sc = self._scenes[k]
+                    if self.keep_mask_grads and logits.requires_grad:
+                        logits.retain_grad()
+                    self.mask_out = (selection, descs)
+                    self.mask_losses = self.mask_criterion(logits, selection, descs, sc["gt_label"], sc["gt_mask"])
+                    terms[3] = self.mask_losses
+                    if self.mask_losses.requires_grad:
+                        term_pos[3] = len(roots)
+                        roots.append(self.mask_losses)
+                        root_grads.append(self._mask_grad)
+                    self.n_roi_rows = int(logits.shape[0])
+                elif gm is None or gm.shape != logits.shape:
+                    if self.with_rpn:
+                        # the proposals -- and with them the number of cropped points -- change from step to step: dM is a slice
+                        # of one device-resident pool (drawing 2 M normals on the host per step would be timed as part of it)
+                        pool = self._gm_pool
+                        if pool is None or pool.shape[0] < logits.shape[0] or pool.shape[1:] != logits.shape[1:]:
+                            rows = max(2 * logits.shape[0], 1 << 18)
+                            pool = self._gm_pool = torch.randn((rows,) + tuple(logits.shape[1:]), generator=self._gen).to(self.device)
+                        gm = self._gms[k] = pool[:logits.shape[0]]
+                    else:
+                        gm = self._gms[k] = torch.randn(logits.shape, generator=self._gen).to(self.device)
+                    self.n_roi_rows = sum(g.shape[0] for g in self._gms.values())
+                if logits.requires_grad and logits.shape[0] and not do["mask"]:
+                    roots.append(logits)
+                    root_grads.append(gm if scale == 1.0 else gm * scale)
             # (an empty crop -- no proposal caught a point: the mask branch contributes nothing on this rank)
             if zero:
                 self.flat.zero_grad()
             if self.combiner is not None:
                 self._combine_losses(terms, term_pos, root_grads, zero)
-            _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
+            if roots:                  # (none: an empty crop in a step that trains the mask branch alone)
+                _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
         self.out, self.logits, self.fin = out, logits, fin
 
     def forward_only(self, k=0):
@@ -1057,6 +1146,16 @@ class SceneStep:
             s += ("; the segmentation head (SubM 1^3 to 20 classes, one row per point) trains on the reference's segmentation "
                   "loss: cross entropy against the instances' labels + 2, -100 (ignored) outside every instance; its gradient "
                   "replaces the synthetic one at the backbone output (scn_xent.hip)")
+        if self.train is not None:
+            s += ("; TRAINING IN STAGES (train=" + repr(self.train) + "; the reference's mask_only / unet_tweak, run.py:332,"
+                  "1414-1427): trainable parts " + ", ".join(self.trainable) + "; frozen parts "
+                  + (", ".join(self.frozen) or "none") + " (requires_grad False, outside the flat buffer and the optimizer, "
+                  "forward-only where nothing trainable lies below them); requested losses not computed: "
+                  + (", ".join(self.losses_not_computed) or "none")
+                  + " (no targets, draws or selector launches, the head not run in the step; predict() / evaluate() run it)")
+        if self.init_missing is not None:
+            s += (f"; initialised from an earlier stage's state_dict (init_state, the reference's ignore_load): "
+                  f"{len(self.init_missing)} model keys kept their own initialisation, {len(self.init_unused)} keys of the dict unused")
         if self.combiner is not None:
             s += ("; the losses are combined by the reference's loss container (loss.LossCombiner: loss = sum of term x "
                   "exp(-log-weight) + the log-weights, the two RPN weights crossed as in loss.py:111-114; "
