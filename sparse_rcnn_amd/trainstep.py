@@ -88,6 +88,31 @@ def _backward(roots, grads, step_scope=False):
         torch.autograd.backward(roots, grads)
 
 
+# the loss container's term slots, in the order of the library's LOSS_TERMS (loss.loss_combine)
+TERM_RPN_SCORE, TERM_RPN_BBOX, TERM_CLASS, TERM_MASK, TERM_SEGMENTATION = range(L.LOSS_TERMS)
+
+
+class _RootLedger:
+    """What one micro-batch hands to backward, filled by the parts of `forward_backward` in the order they run: the roots, the
+    gradient each is back-propagated with, and -- for the roots that are loss values -- the loss container's view of them:
+    `terms[i]` the value of term i (None: not computed), `term_pos[i]` its position among the roots."""
+    __slots__ = ("roots", "grads", "terms", "term_pos")
+
+    def __init__(self):
+        self.roots, self.grads = [], []
+        self.terms, self.term_pos = [None] * L.LOSS_TERMS, {}
+
+    def add(self, value, grad, term=None):
+        """grad=None (a loss nothing trainable lies under): the container records the term, backward gets no root."""
+        if term is not None:
+            self.terms[term] = value
+            if grad is None:
+                return
+            self.term_pos[term] = len(self.roots)
+        self.roots.append(value)
+        self.grads.append(grad)
+
+
 class SparseStepModel(torch.nn.Module):
     """Backbone (+ mask branch for cfg3) as one module, so that one flat parameter buffer covers the step."""
 
@@ -118,15 +143,11 @@ class SparseStepModel(torch.nn.Module):
         with_segmentation: the reference's segmentation head (classhead.SegmentationHead, 20 classes) on the backbone output.
         Both are constructed AFTER the other modules: under one seed the others start from the same values with or without."""
         super().__init__()
-        stage_kw = dict(relu_first=relu_first, drop_input_relu=drop_input_relu, use_residuals=use_residuals)
-        self.backbone = Backbone(7, channels, batchnorm=batchnorm, bf16_blocks=storage,
-                                 **(dict(bottleneck_divisor=bottleneck_divisor, main_path_relu=main_path_relu)
-                                    if (bottleneck_divisor or main_path_relu) else {}),
-                                 **({} if all(stage_kw.values()) else stage_kw),
-                                 **(dict(bn_stages=True) if bn_stages else {}))
+        self.backbone = Backbone(7, channels, batchnorm=batchnorm, bf16_blocks=storage, bottleneck_divisor=bottleneck_divisor,
+                                 main_path_relu=main_path_relu, relu_first=relu_first, drop_input_relu=drop_input_relu,
+                                 use_residuals=use_residuals, bn_stages=bool(bn_stages))
         self.mask = MaskBranch(channels[0], 7, bf16_blocks=storage) if with_mask else None
-        self.rpn = self.roi_selector = None
-        self.rpn_levels = None                 # indices of the encoder levels the RPN reads
+        self.rpn = self.roi_selector = self.rpn_levels = None      # (rpn_levels: indices of the encoder levels the RPN reads)
         if class_storage not in (None, "bf16"):
             raise ValueError("class_storage: None | 'bf16'")
         if class_storage and (with_class != "dense" or storage != "all"):
@@ -140,32 +161,9 @@ class SparseStepModel(torch.nn.Module):
                              "belongs to DenseClassBranch")
         if upsample_heads and with_rpn != "reference":
             raise ValueError("upsample_heads=True needs with_rpn='reference' (the reference's two anchor levels)")
-        if with_rpn == "reference" and upsample_heads:
-            from .rpn import MultiLevelRpn, RoiSelector, REF_EXTRA_STRIDE_LEVELS, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS
-            self.rpn_levels = (2, 3)
-            self.rpn = MultiLevelRpn([(channels[2], 4, 128, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS[0]),
-                                      (channels[3], 8, 256, REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS[1])], num_dilations=5,
-                                     extra_stride_levels=REF_EXTRA_STRIDE_LEVELS,
-                                     **(dict(autocast_bf16=True) if storage else {}),
-                                     **(dict(keep_volume=True) if with_class == "dense" else {}))
-            self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:847-853: 1024 / 256 / 0.5
-        elif with_rpn == "reference":
-            from .rpn import MultiLevelRpn, RoiSelector, REF_ANCHOR_LEVELS_VOXELS
-            # run.py:525-549: anchor paths on the two levels behind the in-between downsamplers (64 ch at stride 4, 80 ch at
-            # stride 8 in the plan 32-48-64-80-96-112), anchor_output_channels = [128, 256], num_dilations = 5 (run.py:609)
-            self.rpn_levels = (2, 3)
-            self.rpn = MultiLevelRpn([(channels[2], 4, 128, REF_ANCHOR_LEVELS_VOXELS[0]),
-                                      (channels[3], 8, 256, REF_ANCHOR_LEVELS_VOXELS[1])], num_dilations=5,
-                                     autocast_bf16=bool(storage), **(dict(keep_volume=True) if with_class == "dense" else {}))
-            self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:847-853: 1024 / 256 / 0.5
-        elif with_rpn:               # one anchor path on the coarsest level (run.py:524: num_anchor_pathes = 1), stride 2^(L-1)
-            from .rpn import DenseRpn, RoiSelector
-            self.rpn_levels = (len(channels) - 1,)
-            self.rpn = DenseRpn(channels[-1], stride=2 ** (len(channels) - 1), autocast_bf16=bool(storage),
-                                **(dict(keep_volume=True) if with_class == "dense" else {}))
-            self.roi_selector = RoiSelector(1024, n_boxes, 0.5)          # run.py:848-850 with ~64 proposals kept per scene
-        self.class_branch = self.segmentation = None
-        self.class_level = None
+        if with_rpn:
+            self._build_rpn(channels, with_rpn, bool(storage), n_boxes, upsample_heads, keep_volume=with_class == "dense")
+        self.class_branch = self.segmentation = self.class_level = None
         if with_class:
             if self.rpn is None:
                 raise ValueError("with_class needs an RPN (the class branch reads its coarsest level)")
@@ -177,13 +175,31 @@ class SparseStepModel(torch.nn.Module):
                     self.class_branch = ReshapeClassBranch(src.width, src.stride)
                 else:
                     self.class_branch = DenseClassBranch(src.width, src.stride,
-                                                         **(dict(storage=torch.bfloat16) if class_storage else {}))
+                                                         storage=torch.bfloat16 if class_storage else torch.float32)
             else:
                 self.class_level = self.rpn_levels[-1]
                 self.class_branch = ClassBranch(channels[self.class_level], 2 ** self.class_level)
         if with_segmentation:
             from .classhead import SegmentationHead
             self.segmentation = SegmentationHead(channels[0], 20)
+
+    def _build_rpn(self, channels, kind, autocast_bf16, n_boxes, upsample_heads, keep_volume):
+        """The RPN of `kind` and its selector: which encoder levels it reads, (channels, stride, stack width, anchors) of each."""
+        from . import rpn as R
+        if kind == "reference":
+            # run.py:525-549: anchor paths on the two levels behind the in-between downsamplers (64 ch at stride 4, 80 ch at
+            # stride 8 in the plan 32-48-64-80-96-112), anchor_output_channels = [128, 256], num_dilations = 5 (run.py:609);
+            # upsample_heads: the anchors of the committed heads and their extra strides (run.py:339,532-537)
+            anchors = R.REF_UPSAMPLE_ANCHOR_LEVELS_VOXELS if upsample_heads else R.REF_ANCHOR_LEVELS_VOXELS
+            self.rpn_levels = (2, 3)
+            self.rpn = R.MultiLevelRpn([(channels[i], 2 ** i, width, a) for i, width, a in zip(self.rpn_levels, (128, 256), anchors)],
+                                       num_dilations=5, autocast_bf16=autocast_bf16, keep_volume=keep_volume,
+                                       extra_stride_levels=R.REF_EXTRA_STRIDE_LEVELS if upsample_heads else None)
+        else:                        # one anchor path on the coarsest level (run.py:524: num_anchor_pathes = 1), stride 2^(L-1)
+            self.rpn_levels = (len(channels) - 1,)
+            self.rpn = R.DenseRpn(channels[-1], stride=2 ** (len(channels) - 1), autocast_bf16=autocast_bf16, keep_volume=keep_volume)
+        # run.py:847-853: 1024 / 256 / 0.5 (the stand-in: run.py:848-850 with ~64 proposals kept per scene)
+        self.roi_selector = R.RoiSelector(1024, n_boxes, 0.5)
 
     def run_rpn(self, interims):
         lv = [interims[i] for i in self.rpn_levels]
@@ -316,13 +332,54 @@ class SceneStep:
         (each rank in proportion to its active voxels: what a loss normalised by batch-level counts gives when the
         batch is sharded one scene per rank, loss.py:401-431; the counts are summed over ranks once per step)."""
         ch, gr, tg, nb, self.baseline_entry, n_samples = WORKLOADS[workload]
-        if rpn_loss and not workload.endswith("-rpn"):
-            raise ValueError("rpn_loss=True needs an RPN in the step (the -rpn workloads)")
-        if mask_loss and not workload.endswith("-rpn"):
-            raise ValueError("mask_loss=True needs an RPN in the step (the -rpn workloads)")
-        if class_loss and not workload.endswith("-rpn"):
-            raise ValueError("class_loss=True needs an RPN in the step (the -rpn workloads)")
-        if dense_class and not class_loss:
+        self.with_rpn = workload.endswith("-rpn")
+        requested = {"rpn": bool(rpn_loss), "class": bool(class_loss), "mask": bool(mask_loss), "segmentation": bool(segmentation_loss)}
+        # 1. option checks, before anything is allocated
+        self._check_heads(workload, requested, nb, dtype, dense_class, class_storage, simple_class, upsample_heads, n_gt)
+        self._check_loss_weights(requested, loss_weights, multitask_loss)
+        batches = self._check_run(workload, dtype, prefetch, batches, n_gt, batches_per_step, optimizer, lr, weighting, step_group)
+        self.channels, self.grid = tuple(channels or ch), tuple(grid or gr)
+        self.n_boxes = nb if n_boxes is None else n_boxes
+        if dtype not in ("f32", "bf16", "bf16-blocks"):
+            raise ValueError("dtype: f32 | bf16 | bf16-blocks")
+        self._check_train(train, requested, multitask_loss)
+        if requested["segmentation"] and not self.n_boxes:
+            raise ValueError("segmentation_loss=True needs boxes (n_boxes > 0)")
+        # 2. the scenes, resident on the device
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._build_scenes(batches, n_samples, target or tg, seed)
+        # 3. the model.  The order of construction under one seed decides every initial value: class branch and segmentation
+        # head last (SparseStepModel), the loss container after the model, the RPN heads' own initialisation after that
+        torch.manual_seed(0)
+        self._build_model(dtype, bottleneck_divisor, main_path_relu, relu_first, drop_input_relu, use_residuals, bn_stages)
+        # 4. the loss objects, 5. the ground-truth instances they are computed against
+        self._build_losses(seed)
+        if self.mask_loss or self.class_loss or self.segmentation_loss:
+            self._build_instances(seed)
+        # 6. an earlier stage's values, 7. what is frozen, 8. the flat buffer over the rest, 9. the container's views of it
+        self.init_missing = self.init_unused = None
+        if init_state is not None:
+            self.init_missing, self.init_unused = self._load_init_state(init_state)
+        self._build_flat(n_buckets)
+        if self.combiner is not None:
+            self._build_container_views()
+        # 10. the optimizer
+        self.adam = None
+        if optimizer == "adam":
+            from .optim import FlatAdam
+            self.adam = FlatAdam(self.flat, lr=self.lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._gen = torch.Generator(device="cpu").manual_seed(grad_seed)
+        self._gys, self._gms, self._grs = {}, {}, {}
+        self._gm_pool = self._md_next = None
+        self.n_active = self.n_roi_rows = 0
+        self.out = self.logits = self.fin = self.rpn_out = None
+
+    # ---- the constructor's phases, in the order they run ---------------------------------------------------------------
+    def _check_heads(self, workload, requested, nb, dtype, dense_class, class_storage, simple_class, upsample_heads, n_gt):
+        for name in ("rpn", "mask", "class"):
+            if requested[name] and not self.with_rpn:
+                raise ValueError(f"{name}_loss=True needs an RPN in the step (the -rpn workloads)")
+        if dense_class and not requested["class"]:
             raise ValueError("dense_class=True chooses the class branch's arm: it needs class_loss=True")
         if class_storage not in (None, "bf16"):
             raise ValueError("class_storage: None | 'bf16'")
@@ -337,16 +394,20 @@ class SceneStep:
         if upsample_heads and workload != "ref-crop-rpn":
             raise ValueError("upsample_heads=True is the reference's RPN head: only ref-crop-rpn has its two anchor levels")
         self.upsample_heads = bool(upsample_heads)
-        if segmentation_loss and not nb:
+        if requested["segmentation"] and not nb:
             raise ValueError("segmentation_loss=True needs a workload with boxes (cfg3, cfg3-rpn, ref-crop-rpn): the labels "
                              "come from the scene's instances")
-        if n_gt is not None and not workload.endswith("-rpn"):
+        if n_gt is not None and not self.with_rpn:
             raise ValueError("n_gt applies to the ground truth of the -rpn workloads")
         if n_gt is not None and int(n_gt) < 1:
             raise ValueError("n_gt >= 1 required")
         self.n_gt = None if n_gt is None else int(n_gt)
-        loss_on = {"rpn_class": bool(rpn_loss), "rpn_bbox": bool(rpn_loss), "class": bool(class_loss), "mask": bool(mask_loss),
-                   "segmentation": bool(segmentation_loss)}
+        self.dense_class = bool(dense_class)
+        self.rpn_loss, self.class_loss, self.mask_loss, self.segmentation_loss = requested.values()
+
+    def _check_loss_weights(self, requested, loss_weights, multitask_loss):
+        loss_on = {"rpn_class": requested["rpn"], "rpn_bbox": requested["rpn"], "class": requested["class"],
+                   "mask": requested["mask"], "segmentation": requested["segmentation"]}
         weights = dict.fromkeys(loss_on, 1.0)
         if loss_weights is not None:
             if not isinstance(loss_weights, dict):
@@ -366,8 +427,10 @@ class SceneStep:
         # the loss container exists only when it has something to do: a learned or a non-unit weight
         self._loss_weights = weights if (multitask_loss or any(v != 1.0 for v in weights.values())) else None
         self.multitask_loss = bool(multitask_loss)
+
+    def _check_run(self, workload, dtype, prefetch, batches, n_gt, batches_per_step, optimizer, lr, weighting, step_group):
         if batches is not None:
-            if not workload.endswith("-rpn"):
+            if not self.with_rpn:
                 raise ValueError("batches= applies to the -rpn workloads (the ground truth feeds the RPN, mask and class losses)")
             if n_gt is not None:
                 raise ValueError("n_gt cuts the synthetic ground truth; a batch brings its own")
@@ -382,10 +445,8 @@ class SceneStep:
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer: sgd | adam")
         self.optimizer = optimizer
-        if optimizer == "adam":
-            self.lr = 4e-4 if lr is None else float(lr)
-        else:
-            self.lr = (1e-8 if workload.endswith("-rpn") else 1e-6) if lr is None else float(lr)
+        default_lr = 4e-4 if optimizer == "adam" else (1e-8 if self.with_rpn else 1e-6)
+        self.lr = default_lr if lr is None else float(lr)
         if weighting not in ("equal", "count"):
             raise ValueError("weighting: equal | count")
         self.weighting = weighting
@@ -397,15 +458,11 @@ class SceneStep:
             raise ValueError("count-weighted ranks with gradient accumulation: scale each micro-batch's loss by its own count "
                              "instead (rank_weight applies to the accumulated sum when a slice is packed)")
         self._total_weight = None
-        self.channels = tuple(channels or ch)
-        self.grid = tuple(grid or gr)
-        self.n_boxes = nb if n_boxes is None else n_boxes
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dtype not in ("f32", "bf16", "bf16-blocks"):
-            raise ValueError("dtype: f32 | bf16 | bf16-blocks")
-        storage = {"f32": False, "bf16": "all", "bf16-blocks": True}[dtype]
-        have = {"backbone": True, "rpn": workload.endswith("-rpn"), "class": bool(class_loss), "mask": bool(self.n_boxes),
-                "segmentation": bool(segmentation_loss)}
+        return batches
+
+    def _check_train(self, train, requested, multitask_loss):
+        have = {"backbone": True, "rpn": self.with_rpn, "class": self.class_loss, "mask": bool(self.n_boxes),
+                "segmentation": self.segmentation_loss}
         if train is not None:
             if isinstance(train, str):
                 raise ValueError("train: a tuple of part names required, e.g. train=('mask',), got the string " + repr(train))
@@ -425,120 +482,103 @@ class SceneStep:
         self.frozen = tuple(p for p in PARTS if have[p] and p not in self.trainable)
         on = set(self.trainable)
         # a requested loss is computed only if its gradient reaches a trainable parameter (run.py:891-893 `calc_* and not mask_only`)
-        computed = {"rpn": bool(rpn_loss) and bool(on & {"rpn", "backbone"}),
-                    "class": bool(class_loss) and bool(on & ({"class", "backbone", "rpn"} if dense_class else {"class", "backbone"})),
-                    "mask": bool(mask_loss) and bool(on & {"mask", "backbone"}),
-                    "segmentation": bool(segmentation_loss) and bool(on & {"segmentation", "backbone"})}
-        requested = {"rpn": bool(rpn_loss), "class": bool(class_loss), "mask": bool(mask_loss), "segmentation": bool(segmentation_loss)}
-        self.losses_not_computed = tuple(k for k in requested if requested[k] and not computed[k])
-        self._computed = computed
+        under = {"rpn": {"rpn", "backbone"}, "class": {"class", "backbone", "rpn"} if self.dense_class else {"class", "backbone"},
+                 "mask": {"mask", "backbone"}, "segmentation": {"segmentation", "backbone"}}
+        self._computed = {k: requested[k] and bool(on & under[k]) for k in requested}
+        self.losses_not_computed = tuple(k for k in requested if requested[k] and not self._computed[k])
         # the mask branch runs in forward_backward when something trainable lies under its logits
         self._run_mask = bool(self.n_boxes) and bool(on & {"mask", "backbone"})
+
+    def _build_scenes(self, batches, n_samples, target, seed):
         self._scenes = []
         self.from_batches = batches is not None
         # level constraint on a batch's spatial size: every 2^3/2 convolution halves an even size -- levels - 1 in the backbone,
         # two more in the SPARSE class branch, which cuts its boxes out of the coarsest level's grid (the dense one resamples
         # every box to its own 16^3 grid: the volume's stride is one of the backbone's)
-        self.dense_class = bool(dense_class)
-        self._size_factor = 2 ** (len(self.channels) - 1) * (4 if class_loss and not dense_class else 1)
+        self._size_factor = 2 ** (len(self.channels) - 1) * (4 if self.class_loss and not self.dense_class else 1)
         for k in range(self.batches_per_step):
             if self.from_batches:
                 self._scenes.append(self._scene_from_batch(batches[k], k))
                 continue
-            coords, feats, size, bs, splits = make_batch(n_samples, self.grid, target or tg, dup=1.15, seed=seed + 1000 * k)
+            coords, feats, size, bs, splits = make_batch(n_samples, self.grid, target, dup=1.15, seed=seed + 1000 * k)
             boxes = make_boxes(coords, self.n_boxes, seed=seed + 1000 * k + 2) if self.n_boxes else None
             gt_boxes = boxes if (boxes is None or self.n_gt is None) else [b[:self.n_gt] for b in boxes]
             self._scenes.append(dict(coords_cpu=coords, feats_cpu=feats, size=size, batch_size=bs, splits=splits,
                                      coords=coords.to(self.device), feats=feats.to(self.device), boxes=boxes,
                                      gt_boxes=gt_boxes))   # resident in HBM
         self._use_scene(0)
-        torch.manual_seed(0)
-        self.with_rpn = workload.endswith("-rpn")
+
+    def _build_model(self, dtype, bottleneck_divisor, main_path_relu, relu_first, drop_input_relu, use_residuals, bn_stages):
         # ref-crop-rpn: 256 proposals per sample survive the selection (run.py:847-853); the mask network then works on the
         # <= 24 its TrainSelector draws from them (mask_network_params.selection_tuple = (24, 0, True), run.py:799-810;
         # model.py:919-1014 draws by ground-truth overlap -- out of scope: here the 24 best-scored ones)
-        self.mask_boxes = 24 if workload == "ref-crop-rpn" else None
-        rpn_kind = "reference" if workload == "ref-crop-rpn" else ("stand-in" if self.with_rpn else False)
-        self.class_loss, self.segmentation_loss = bool(class_loss), bool(segmentation_loss)
-        if self.segmentation_loss and not self.n_boxes:
-            raise ValueError("segmentation_loss=True needs boxes (n_boxes > 0)")
+        self.mask_boxes = 24 if self.workload == "ref-crop-rpn" else None
+        rpn_kind = "reference" if self.workload == "ref-crop-rpn" else ("stand-in" if self.with_rpn else False)
         self.bottleneck_divisor, self.main_path_relu = int(bottleneck_divisor or 0), bool(main_path_relu)
         self.relu_first, self.drop_input_relu, self.use_residuals = bool(relu_first), bool(drop_input_relu), bool(use_residuals)
-        stage_kw = dict(relu_first=self.relu_first, drop_input_relu=self.drop_input_relu, use_residuals=self.use_residuals)
         self.bn_stages = bool(bn_stages)
+        storage = {"f32": False, "bf16": "all", "bf16-blocks": True}[dtype]
         self.model = SparseStepModel(self.channels, bool(self.n_boxes), storage, rpn_kind, self.n_boxes,
-                                     batchnorm=workload.endswith("-bn"),
+                                     batchnorm=self.workload.endswith("-bn"),
                                      with_class="dense" if self.dense_class else self.class_loss,
-                                     with_segmentation=self.segmentation_loss,
-                                     **(dict(upsample_heads=True) if self.upsample_heads else {}),
-                                     **(dict(class_storage=class_storage) if class_storage else {}),
-                                     **(dict(simple_class=True) if self.simple_class else {}),
-                                     **(dict(bottleneck_divisor=self.bottleneck_divisor, main_path_relu=self.main_path_relu)
-                                        if (self.bottleneck_divisor or self.main_path_relu) else {}),
-                                     **({} if all(stage_kw.values()) else stage_kw),
-                                     **(dict(bn_stages=True) if self.bn_stages else {})).to(self.device)
+                                     with_segmentation=self.segmentation_loss, upsample_heads=self.upsample_heads,
+                                     class_storage=self.class_storage, simple_class=self.simple_class,
+                                     bottleneck_divisor=self.bottleneck_divisor, main_path_relu=self.main_path_relu,
+                                     relu_first=self.relu_first, drop_input_relu=self.drop_input_relu,
+                                     use_residuals=self.use_residuals, bn_stages=self.bn_stages).to(self.device)
         self.combiner = self.loss_record = None
         if self._loss_weights is not None:
             from .loss import LossCombiner
+            do = self._computed
             self.combiner = self.model.loss_combiner = LossCombiner(
                 tuple(self._loss_weights.values()), self.multitask_loss,
-                has=(computed["rpn"], computed["class"], computed["mask"], computed["segmentation"])).to(self.device)
+                has=(do["rpn"], do["class"], do["mask"], do["segmentation"])).to(self.device)
         if self.with_rpn:
             self._init_rpn()
-        self.rpn_loss = bool(rpn_loss)
-        self.rpn_losses = None
-        self.keep_rpn_grads = False            # (tests: retain the gradients that reach rpn_bbox / rpn_score)
+
+    def _build_losses(self, seed):
+        from . import loss as RL
+        # the gradient every loss root is back-propagated with when no container weighs it: 1 / batches_per_step on the device
+        self._loss_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
+        self.rpn_losses = self.mask_losses = self.class_losses = self.segmentation_losses = None
+        self.mask_out = self.class_out = self.segmentation_out = None
+        # (tests: retain the gradients that reach rpn_bbox / rpn_score, the mask logits, the class scores / segmentation logits)
+        self.keep_rpn_grads = self.keep_mask_grads = self.keep_class_grads = False
         if self.rpn_loss:
-            from .loss import BatchwiseBboxTargetSelector, RpnLoss
-            self.rpn_criterion = RpnLoss(BatchwiseBboxTargetSelector(0.35, 0.15, max_weight=1 / 8, seed=seed), sigma=2.)
+            self.rpn_criterion = RL.RpnLoss(RL.BatchwiseBboxTargetSelector(0.35, 0.15, max_weight=1 / 8, seed=seed), sigma=2.)
             self._rpn_targets = {}
-            self._rpn_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
-        self.mask_loss = bool(mask_loss)
-        self.mask_losses = None
-        self.mask_out = None
-        self.keep_mask_grads = False           # (tests: retain the gradient that reaches the mask logits)
         if self.mask_loss:
-            from .loss import MaskLoss, TrainSelector, pack_gt_masks
             # run.py:799-810: mask_network_params.selection_tuple = (24, 0, True) behind TrainSelector(0.2); MaskLoss without
             # class weights (run.py:398, 876-891)
-            self.mask_selector = TrainSelector(0.2, 0, (24, 0, True), seed=seed + 17)
-            self.mask_criterion = MaskLoss(class_weights=None)
-            self._mask_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
-        self.class_losses = self.segmentation_losses = None
-        self.class_out = self.segmentation_out = None
-        self.keep_class_grads = False          # (tests: retain the gradients that reach the class scores / segmentation logits)
+            self.mask_selector = RL.TrainSelector(0.2, 0, (24, 0, True), seed=seed + 17)
+            self.mask_criterion = RL.MaskLoss(class_weights=None)
         if self.class_loss:
-            from .loss import ClassLoss, ClassLossSelector, TrainSelector
             # run.py:399,520-521,729-732: positive_threshold 0.1, selection_tuple (32, 0, True); ClassLoss without weights
-            self.class_selector = TrainSelector(0.1, 0, (32, 0, True), seed=seed + 29)
-            self.class_loss_selector = ClassLossSelector(0.1)
-            self.class_criterion = ClassLoss(class_weights=None)
-            self._class_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
+            self.class_selector = RL.TrainSelector(0.1, 0, (32, 0, True), seed=seed + 29)
+            self.class_loss_selector = RL.ClassLossSelector(0.1)
+            self.class_criterion = RL.ClassLoss(class_weights=None)
         if self.segmentation_loss:
-            from .loss import CrossEntropyLoss
-            self.segmentation_criterion = CrossEntropyLoss(weight=None, ignore_index=-100)
-            self._seg_grad = torch.full((), 1.0 / self.batches_per_step, dtype=torch.float32, device=self.device)
-        if self.mask_loss or self.class_loss or self.segmentation_loss:
-            for k, sc in enumerate(self._scenes):      # instances built (and packed, for the mask loss) once per scene
-                if self.from_batches:                  # (a converted batch brought its instances: _scene_from_batch)
-                    continue
-                labels, masks = make_instances(sc["coords_cpu"], sc["gt_boxes"], n_classes=self.model.mask.classes,
-                                               seed=seed + 1000 * k + 5)
-                flat = torch.cat(labels).to(self.device)
-                views, o = [], 0
-                for l in labels:
-                    views.append(flat[o:o + l.shape[0]])
-                    o += l.shape[0]
-                sc["gt_label"] = views
-                sc["gt_mask_cpu"] = masks
-                if self.mask_loss:
-                    sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in masks])
-                sc["gt_dev"] = [b.float().to(self.device) for b in sc["gt_boxes"]]
-                if self.segmentation_loss:             # one label per point row, in the batch's row order (sample-major)
-                    sc["seg_target"] = torch.cat(make_segmentation(labels, masks)).to(self.device)
-        self.init_missing = self.init_unused = None
-        if init_state is not None:
-            self.init_missing, self.init_unused = self._load_init_state(init_state)
+            self.segmentation_criterion = RL.CrossEntropyLoss(weight=None, ignore_index=-100)
+
+    def _build_instances(self, seed):
+        """Instances built (and packed, for the mask loss) once per scene; a converted batch brought its own
+        (_scene_from_batch)."""
+        from .loss import pack_gt_masks
+        for k, sc in enumerate(self._scenes):
+            if self.from_batches:
+                continue
+            labels, masks = make_instances(sc["coords_cpu"], sc["gt_boxes"], n_classes=self.model.mask.classes,
+                                           seed=seed + 1000 * k + 5)
+            sc["gt_label"] = list(torch.cat(labels).to(self.device).split([l.shape[0] for l in labels]))    # views of one tensor
+            sc["gt_mask_cpu"] = masks
+            if self.mask_loss:
+                sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in masks])
+            sc["gt_dev"] = [b.float().to(self.device) for b in sc["gt_boxes"]]
+            if self.segmentation_loss:             # one label per point row, in the batch's row order (sample-major)
+                sc["seg_target"] = torch.cat(make_segmentation(labels, masks)).to(self.device)
+
+    def _build_flat(self, n_buckets):
+        """Freeze the parts `train=` does not name, then the flat buffer over what is left; equal on every rank."""
         frozen_params = []
         if self.train is not None:
             for name in self.frozen:
@@ -548,34 +588,23 @@ class SceneStep:
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
         broadcast_params(self.flat)
         broadcast_tensors([p.data for p in frozen_params])      # (more than one rank: the frozen parameters are equal everywhere too)
-        if self.combiner is not None:
-            self._root_grad = torch.zeros(L.LOSS_TERMS, dtype=torch.float32, device=self.device)
-            self._root_grad_views = [self._root_grad[i] for i in range(L.LOSS_TERMS)]
-            self._weight_params = self._weight_grad_views = self._weight_grad_slab = None
-            if self.multitask_loss:
-                # the five log-weights are the model's last parameters: their gradient views lie back to back in the flat buffer
-                index = {id(p): i for i, p in enumerate(self.flat.params)}
-                self._weight_params = self.combiner.log_weights()
-                self._weight_grad_views = [self.flat.grad_views[index[id(p)]] for p in self._weight_params]
-                first = self._weight_grad_views[0].storage_offset()
-                if [v.storage_offset() for v in self._weight_grad_views] != list(range(first, first + L.LOSS_TERMS)):
-                    raise L.ScnError("SceneStep: the log-weights are not adjacent in the flat gradient buffer")
-                self._weight_grad_slab = self.flat.flat_grad[first:first + L.LOSS_TERMS]
-                on = (self.rpn_loss, self.rpn_loss, self.class_loss, self.mask_loss, self.segmentation_loss)
-                self._weights_on = [p for p, o in zip(self._weight_params, on) if o]
-                self._weight_grad_views = [v if o else None for v, o in zip(self._weight_grad_views, on)]
-        self.adam = None
-        if optimizer == "adam":
-            from .optim import FlatAdam
-            self.adam = FlatAdam(self.flat, lr=self.lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        self._gen = torch.Generator(device="cpu").manual_seed(grad_seed)
-        self._gys, self._gms, self._grs = {}, {}, {}
-        self._gm_pool = None
-        self.rpn_out = None
-        self._md_next = None
-        self.n_active = 0
-        self.n_roi_rows = 0
-        self.out = self.logits = self.fin = None
+
+    def _build_container_views(self):
+        self._root_grad = torch.zeros(L.LOSS_TERMS, dtype=torch.float32, device=self.device)
+        self._root_grad_views = [self._root_grad[i] for i in range(L.LOSS_TERMS)]
+        self._weight_params = self._weight_grad_views = self._weight_grad_slab = None
+        if self.multitask_loss:
+            # the five log-weights are the model's last parameters: their gradient views lie back to back in the flat buffer
+            index = {id(p): i for i, p in enumerate(self.flat.params)}
+            self._weight_params = self.combiner.log_weights()
+            self._weight_grad_views = [self.flat.grad_views[index[id(p)]] for p in self._weight_params]
+            first = self._weight_grad_views[0].storage_offset()
+            if [v.storage_offset() for v in self._weight_grad_views] != list(range(first, first + L.LOSS_TERMS)):
+                raise L.ScnError("SceneStep: the log-weights are not adjacent in the flat gradient buffer")
+            self._weight_grad_slab = self.flat.flat_grad[first:first + L.LOSS_TERMS]
+            on = (self.rpn_loss, self.rpn_loss, self.class_loss, self.mask_loss, self.segmentation_loss)
+            self._weights_on = [p for p, o in zip(self._weight_params, on) if o]
+            self._weight_grad_views = [v if o else None for v, o in zip(self._weight_grad_views, on)]
 
     # ------------------------------------------------------------------------------------------------------------
     def _part(self, name):
@@ -622,10 +651,8 @@ class SceneStep:
 
     def _use_scene(self, k):
         sc = self._scenes[k]
-        self.coords_cpu, self.feats_cpu, self.size, self.batch_size, self.splits = (
-            sc["coords_cpu"], sc["feats_cpu"], sc["size"], sc["batch_size"], sc["splits"])
-        self.coords, self.feats, self.boxes = sc["coords"], sc["feats"], sc["boxes"]
-        self.gt_boxes = sc["gt_boxes"]
+        for key in ("coords_cpu", "feats_cpu", "size", "batch_size", "splits", "coords", "feats", "boxes", "gt_boxes"):
+            setattr(self, key, sc[key])
         self._k = k
 
     def _scene_shape(self):
@@ -637,10 +664,8 @@ class SceneStep:
         got = self._rpn_targets.get(k)
         if got is None:
             rpn = self.model.rpn
-            if hasattr(rpn, "levels"):
-                calc = rpn.target_calculator(tuple(int(v) for v in self.size), self.device)
-            else:
-                calc = rpn.target_calculator(tuple(int(v) // rpn.stride for v in self.size), self.device)
+            stride = 1 if hasattr(rpn, "levels") else rpn.stride      # (the levels take the scene's shape, one level its own grid's)
+            calc = rpn.target_calculator(tuple(int(v) // stride for v in self.size), self.device)
             offs = [0]
             for b in self.gt_boxes:
                 offs.append(offs[-1] + b.shape[0])
@@ -653,17 +678,13 @@ class SceneStep:
         NMS have something to decide) -- seeded, the same on every rank."""
         g = torch.Generator().manual_seed(1234)
         rpn = self.model.rpn
+        up = getattr(rpn, "anchor_network", None)                 # (the up-sampling heads' weights: [C, A_g * 7, s0, s1, s2])
+        heads = up.heads() if up is not None else ([r.head for r in rpn.levels] if hasattr(rpn, "levels") else [rpn.head])
         with torch.no_grad():
-            if getattr(rpn, "anchor_network", None) is not None:
-                for h in rpn.anchor_network.heads():                                 # weight [C, A_g * 7, s0, s1, s2]
-                    w = torch.randn(h.weight.shape, generator=g) * 0.02
-                    w[:, 6::7] = torch.randn(w[:, 6::7].shape, generator=g) * 0.5
-                    h.weight.copy_(w.to(h.weight.device))
-                    h.bias.zero_()
-                return
-            for h in ([r.head for r in rpn.levels] if hasattr(rpn, "levels") else [rpn.head]):
+            for h in heads:
                 w = torch.randn(h.weight.shape, generator=g) * 0.02              # box deltas: boxes stay near their anchors
-                w[6::7] = torch.randn(w[6::7].shape, generator=g) * 0.5          # channel a*7+6 = the score of anchor a
+                scores = w[:, 6::7] if up is not None else w[6::7]               # channel a*7+6 = the score of anchor a
+                scores.copy_(torch.randn(scores.shape, generator=g) * 0.5)
                 h.weight.copy_(w.to(h.weight.device))
                 h.bias.zero_()
 
@@ -678,8 +699,8 @@ class SceneStep:
             nx = self._scenes[(k + 1) % self.batches_per_step]
             self._md_next = self.model.backbone.prefetch_in_thread(nx["coords"], nx["size"], nx["batch_size"])
 
-    def _combine_losses(self, terms, term_pos, root_grads, zero):
-        """The loss container's launch of one micro-batch, between forward and backward: root_grads[term_pos[i]] becomes the
+    def _combine_losses(self, ledger, zero):
+        """The loss container's launch of one micro-batch, between forward and backward: the gradient of term i's root becomes the
         device scalar exp(-log-weight of term i) / batches_per_step, and with multitask_loss the log-weights' gradients are
         added into their views of the flat gradient buffer (zeroed at the step's first micro-batch), which become their
         `.grad`."""
@@ -692,11 +713,11 @@ class SceneStep:
             if zero:
                 self._weight_grad_slab.zero_()
             self.flat.adopt_views(self._weights_on)
-        record = RL.loss_combine(terms, cb.log_weights(), 1.0 / self.batches_per_step, root_grad=self._root_grad,
+        record = RL.loss_combine(ledger.terms, cb.log_weights(), 1.0 / self.batches_per_step, root_grad=self._root_grad,
                                  weight_grads=views, running=cb._running_for(self._root_grad.device))
-        self.loss_record = RL.LossRecord(record, [t is not None for t in terms])
-        for i, pos in term_pos.items():
-            root_grads[pos] = self._root_grad_views[i]
+        self.loss_record = RL.LossRecord(record, [t is not None for t in ledger.terms])
+        for i, pos in ledger.term_pos.items():
+            ledger.grads[pos] = self._root_grad_views[i]
         if self.multitask_loss and self.flat.sync:
             self.flat.mark_ready(self._weights_on)       # (bucketed all-reduce: autograd never reaches these parameters)
 
@@ -705,13 +726,8 @@ class SceneStep:
         `rpn_bbox`, `class`, `mask`, `segment` (one copy; without a container every weight is 1)."""
         if self.combiner is not None:
             return self.combiner.get_weights()
-        out, do = {}, self._computed
-        if do["rpn"]:
-            out["rpn_score"] = out["rpn_bbox"] = 1.0
-        for key, on in (("class", do["class"]), ("mask", do["mask"]), ("segment", do["segmentation"])):
-            if on:
-                out[key] = 1.0
-        return out
+        keys = (("rpn_score", "rpn"), ("rpn_bbox", "rpn"), ("class", "class"), ("mask", "mask"), ("segment", "segmentation"))
+        return {key: 1.0 for key, loss in keys if self._computed[loss]}
 
     def upstream_grads(self, k=0):
         """(dY of the backbone output, dY of the mask logits or None) of micro-batch k, BEFORE the 1 / batches_per_step scale."""
@@ -726,8 +742,6 @@ class SceneStep:
         #  attribute stores are 40-50 us the first forward kernels would wait for)
         if k != self._k:
             self._use_scene(k)
-        scale = 1.0 / self.batches_per_step
-        do = self._computed                     # which of the requested losses this step computes (train=None: all of them)
         # (a frozen backbone takes the features as they are: nothing below it asks for a gradient, its stages run forward-only)
         fin = self.feats.detach().requires_grad_() if "backbone" in self.trainable else self.feats
         md = self._take_index(k)
@@ -737,13 +751,11 @@ class SceneStep:
             self._start_prefetch(k)
         # cfg3-rpn: the RPN reads the ENCODER outputs only (model.py:141-160), so its heads, top-k and NMS are queued between
         # encoder and decoder, and the one host wait of the selection falls while the decoder's kernels run
-        rpn_state = {}
-        terms, term_pos = [None] * L.LOSS_TERMS, {}     # the loss container's view of this micro-batch: values, root positions
+        rpn_state = []
 
         def rpn_after_encoder(interims):
             rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
-            rpn_state["out"] = (rpn_bbox, rpn_score, anchors,
-                                m.roi_selector.start(rpn_bbox, rpn_score, anchors, self._scene_shape()))
+            rpn_state.append((rpn_bbox, rpn_score, anchors, m.roi_selector.start(rpn_bbox, rpn_score, anchors, self._scene_shape())))
         hook = rpn_after_encoder if (self.with_rpn and RPN_BEFORE_DECODER) else None
         # cfg3: the ROI crop's selection and the ROI batch's index structures depend on coordinates and boxes only -- the
         # boxes of a step are known before its backbone runs (here: synthetic; in the reference: the RPN's proposals of
@@ -751,20 +763,62 @@ class SceneStep:
         cut = None
         if m.mask is not None and EARLY_ROI_CUT and not self.mask_loss and self._run_mask:
             cut = m.mask.prepare_cut(self.coords, self.size, self.boxes)      # (resident int64 coords: no dependency on md)
-        rpn_prep = None
-        if do["rpn"]:
-            # the RPN loss's targets and draw depend on the anchors (the scene shape) and the boxes only: queued ahead of the
-            # backbone, they overlap nothing the forward waits for
-            calc, gt, offs = self._rpn_target_setup(k)
-            ov, am, tg = calc.from_concatenated(gt, offs)
-            rpn_prep = (ov, am, tg) + tuple(self.rpn_criterion.bbox_target_selector(ov))
+        rpn_prep = self._queue_rpn_targets(k) if self._computed["rpn"] else None
         out = m.backbone(self.coords, fin, self.size, self.batch_size, metadata=md, after_encoder=hook)
         self._start_prefetch(k)      # (LATE_PREFETCH: the helper thread is started once this batch's forward kernels are queued)
-        roots, root_grads = [], []
-        if do["segmentation"]:
+        ledger = _RootLedger()
+        self._backbone_roots(ledger, k, out)
+        if self.weighting == "count":             # before backward: the bucketed path scales slices as it packs them
+            self._count_weight(out)
+        boxes, logits = self.boxes, None
+        proposals = overlaps = descs = None
+        if self.with_rpn and m.mask is not None:
+            if not rpn_state:
+                rpn_after_encoder(m.backbone.unet.interims)
+            boxes, proposals, overlaps, descs = self._rpn_roots(ledger, k, rpn_state[0], rpn_prep)
+        if self._computed["class"]:
+            self._class_roots(ledger, k, proposals, overlaps)
+        if self._run_mask:             # (else: mask branch and backbone frozen -- nothing trainable lies under the logits)
+            # (the crop's selection stays referenced until backward has run, as it always did: released earlier, its blocks --
+            #  the ROI batch's coordinates among them -- would be handed to the backward pass's allocations)
+            scene = (self.coords, fin, self.size, self.batch_size, self.splits)
+            logits, selection = self._mask_roots(ledger, k, scene, out, boxes, descs, cut)
+        if zero:
+            self.flat.zero_grad()
+        if self.combiner is not None:
+            self._combine_losses(ledger, zero)
+        if ledger.roots:               # (none: an empty crop in a step that trains the mask branch alone)
+            _backward(ledger.roots, ledger.grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
+        self.out, self.logits, self.fin = out, logits, fin
+
+    # ---- the parts of forward_backward, in the order they run: each adds its roots to the ledger ------------------------
+    def _seeded(self, cache, k, shape, draw):
+        """The synthetic gradient of micro-batch k in `cache`: drawn from `self._gen` by `draw()` at first use and kept (the same
+        direction every step; a draw per step would be timed as part of it), drawn again when the shape it was drawn for has
+        changed.  -> (what the cache holds, whether it was drawn now)"""
+        got = cache.get(k)
+        lead = got[0] if type(got) is tuple else got
+        if lead is not None and lead.shape == shape:
+            return got, False
+        got = cache[k] = draw()
+        return got, True
+
+    def _scaled(self, g):
+        """The upstream gradient of one micro-batch out of `batches_per_step`."""
+        return g if self.batches_per_step == 1 else g * (1.0 / self.batches_per_step)
+
+    def _queue_rpn_targets(self, k):
+        """The RPN loss's targets and draw depend on the anchors (the scene shape) and the boxes only: queued ahead of the
+        backbone, they overlap nothing the forward waits for."""
+        calc, gt, offs = self._rpn_target_setup(k)
+        ov, am, tg = calc.from_concatenated(gt, offs)
+        return (ov, am, tg) + tuple(self.rpn_criterion.bbox_target_selector(ov))
+
+    def _backbone_roots(self, ledger, k, out):
+        if self._computed["segmentation"]:
             # the reference's real gradient at the backbone output: the segmentation head's logits (fp32; bf16 storage widened)
             # against the scene's per-point labels, in place of the seeded N(0, 1) direction
-            seg_logits = m.segmentation(out)
+            seg_logits = self.model.segmentation(out)
             if seg_logits.dtype != torch.float32:
                 seg_logits = seg_logits.float()
             if self.keep_class_grads:
@@ -772,151 +826,168 @@ class SceneStep:
             seg_target = self._scenes[k]["seg_target"]
             self.segmentation_losses = self.segmentation_criterion(seg_logits, seg_target)
             self.segmentation_out = (seg_logits, seg_target)
-            roots, root_grads = [self.segmentation_losses], [self._seg_grad]
-            terms[4], term_pos[4] = self.segmentation_losses, 0
-            self.n_active = int(out.features.shape[0]) * self.batches_per_step
-        elif not out.features.requires_grad:
-            # nothing trainable under the backbone output: no root here, and no synthetic gradient is drawn for one
-            self.n_active = int(out.features.shape[0]) * self.batches_per_step
-        else:
-            gy = self._gys.get(k)
-            if gy is None or gy.shape != out.features.shape:
-                gy = self._gys[k] = torch.randn(out.features.shape, generator=self._gen).to(self.device)   # upstream grad dY ~ N(0,1)
+            ledger.add(self.segmentation_losses, self._loss_grad, TERM_SEGMENTATION)
+        elif out.features.requires_grad:
+            shape = out.features.shape
+            gy, drawn = self._seeded(self._gys, k, shape, lambda: torch.randn(shape, generator=self._gen).to(self.device))  # dY ~ N(0,1)
+            if drawn:
                 self.n_active = sum(g.shape[0] for g in self._gys.values())
-            roots, root_grads = [out.features], [gy if scale == 1.0 else gy * scale]
-        if self.weighting == "count":             # before backward: the bucketed path scales slices as it packs them
-            import torch.distributed as dist
-            self.flat.rank_weight = float(out.features.shape[0])
-            tot = torch.tensor([self.flat.rank_weight], dtype=torch.float64)
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                tot = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
-                dist.all_reduce(tot)
-            self._total_weight = float(tot.item())
-        if m.mask is None:
-            if zero:
-                self.flat.zero_grad()
-            _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
-            logits = None
+            ledger.add(out.features, self._scaled(gy))
+            return
+        # (reached with the segmentation loss, or with nothing trainable under the backbone output: then there is no root here,
+        #  and no synthetic gradient is drawn for one)
+        self.n_active = int(out.features.shape[0]) * self.batches_per_step
+
+    def _count_weight(self, out):
+        import torch.distributed as dist
+        self.flat.rank_weight = float(out.features.shape[0])
+        tot = torch.tensor([self.flat.rank_weight], dtype=torch.float64)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            tot = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(tot)
+        self._total_weight = float(tot.item())
+
+    def _rpn_roots(self, ledger, k, rpn_out, rpn_prep):
+        """configs[2] as written (model.py:141-160): the proposals are this forward's -- dense heads on the coarsest encoder
+        level, top-k + NMS on the device; the RPN losses' gradients arrive at rpn_bbox / rpn_score.
+        -> (the boxes the mask branch runs on, the proposals, and -- with the mask loss -- its overlaps and descriptions)"""
+        rpn_bbox, rpn_score, anchors, sel_state = rpn_out
+        roi_score, boxes, roi_index = self.model.roi_selector.finish(sel_state)
+        self.rpn_out = (rpn_bbox, rpn_score, anchors, roi_score, boxes, roi_index)
+        descs = overlaps = None
+        proposals = boxes
+        if self._computed["mask"]:
+            # model.py:172-196: OverlapCalculator + TrainSelector on this forward's proposals, one launch; the mask
+            # branch runs on the drawn proposals ++ every ground-truth box
+            overlaps, boxes, descs = self.mask_selector.select(boxes, self._scenes[k]["gt_dev"])
+            boxes = list(boxes)
+        elif self.mask_boxes is not None:     # (the reference's mask head trains on <= 24 selected proposals per sample)
+            boxes = [b[:self.mask_boxes] for b in boxes]
+        if self.keep_rpn_grads and rpn_bbox.requires_grad:
+            rpn_bbox.retain_grad()
+            rpn_score.retain_grad()
+        if self._computed["rpn"]:
+            calc = self._rpn_targets[k][0]
+            if calc.anchors.data_ptr() != anchors.data_ptr() or calc.anchors.shape != anchors.shape:
+                raise L.ScnError("SceneStep: the RPN loss's anchors are not the ones the RPN returned")
+            self.rpn_losses = self.rpn_criterion.loss(rpn_prep, rpn_score, rpn_bbox)
+            for term, value in zip((TERM_RPN_SCORE, TERM_RPN_BBOX), self.rpn_losses):       # (score_loss + bbox_loss) / batches_per_step
+                ledger.add(value, self._loss_grad, term)
+        elif rpn_bbox.requires_grad:               # (no RPN loss: the seeded direction, where a gradient can arrive)
+            gr, _ = self._seeded(self._grs, k, rpn_bbox.shape, lambda: tuple(
+                (torch.randn(t.shape, generator=self._gen) * 1e-3).to(self.device) for t in (rpn_bbox, rpn_score)))
+            ledger.add(rpn_bbox, self._scaled(gr[0]))
+            ledger.add(rpn_score, self._scaled(gr[1]))
+        return boxes, proposals, overlaps, descs
+
+    def _class_roots(self, ledger, k, proposals, overlaps):
+        # model.py:170-183: the class network's TrainSelector draws from the same overlap descriptions as the mask
+        # network's; the branch runs on its forward boxes (drawn proposals ++ every ground-truth box)
+        m, sc = self.model, self._scenes[k]
+        if overlaps is None:
+            overlaps, cboxes, cdescs = self.class_selector.select(proposals, sc["gt_dev"])
         else:
-            scene = (self.coords, fin, self.size, self.batch_size, self.splits)
-            boxes = self.boxes
-            if self.with_rpn:
-                # configs[2] as written (model.py:141-160): the proposals are this forward's -- dense heads on the coarsest
-                # encoder level, top-k + NMS on the device; the RPN losses' gradients arrive at rpn_bbox / rpn_score
-                if "out" not in rpn_state:
-                    rpn_after_encoder(m.backbone.unet.interims)
-                rpn_bbox, rpn_score, anchors, sel_state = rpn_state["out"]
-                roi_score, boxes, roi_index = m.roi_selector.finish(sel_state)
-                self.rpn_out = (rpn_bbox, rpn_score, anchors, roi_score, boxes, roi_index)
-                descs = overlaps = None
-                proposals = boxes
-                if do["mask"]:
-                    # model.py:172-196: OverlapCalculator + TrainSelector on this forward's proposals, one launch; the mask
-                    # branch runs on the drawn proposals ++ every ground-truth box
-                    sc = self._scenes[k]
-                    overlaps, boxes, descs = self.mask_selector.select(boxes, sc["gt_dev"])
-                    boxes = list(boxes)
-                elif self.mask_boxes is not None:     # (the reference's mask head trains on <= 24 selected proposals per sample)
-                    boxes = [b[:self.mask_boxes] for b in boxes]
-                if self.keep_rpn_grads and rpn_bbox.requires_grad:
-                    rpn_bbox.retain_grad()
-                    rpn_score.retain_grad()
-                if do["rpn"]:
-                    calc = self._rpn_targets[k][0]
-                    if calc.anchors.data_ptr() != anchors.data_ptr() or calc.anchors.shape != anchors.shape:
-                        raise L.ScnError("SceneStep: the RPN loss's anchors are not the ones the RPN returned")
-                    self.rpn_losses = self.rpn_criterion.loss(rpn_prep, rpn_score, rpn_bbox)
-                    terms[0], terms[1] = self.rpn_losses
-                    term_pos[0], term_pos[1] = len(roots), len(roots) + 1
-                    roots += list(self.rpn_losses)           # (score_loss + bbox_loss) / batches_per_step
-                    root_grads += [self._rpn_grad, self._rpn_grad]
-                elif rpn_bbox.requires_grad:               # (no RPN loss: the seeded direction, where a gradient can arrive)
-                    gr = self._grs.get(k)
-                    if gr is None or gr[0].shape != rpn_bbox.shape:
-                        gr = self._grs[k] = tuple((torch.randn(t.shape, generator=self._gen) * 1e-3).to(self.device)
-                                                  for t in (rpn_bbox, rpn_score))
-                    roots += [rpn_bbox, rpn_score]
-                    root_grads += [g if scale == 1.0 else g * scale for g in gr]
-            if do["class"]:
-                # model.py:170-183: the class network's TrainSelector draws from the same overlap descriptions as the mask
-                # network's; the branch runs on its forward boxes (drawn proposals ++ every ground-truth box)
-                sc = self._scenes[k]
-                if overlaps is None:
-                    overlaps, cboxes, cdescs = self.class_selector.select(proposals, sc["gt_dev"])
-                else:
-                    cboxes, cdescs = self.class_selector(overlaps)
-                class_scores, csel = m.run_class(m.backbone.unet.interims, list(cboxes))
-                if self.keep_class_grads:
-                    class_scores.retain_grad()
-                sel_scores, sel_labels = self.class_loss_selector(class_scores, csel, cdescs, overlaps, sc["gt_label"])
-                self.class_losses = self.class_criterion(sel_scores, sel_labels)
-                self.class_out = (class_scores, csel, cdescs, sel_labels)
-                terms[2], term_pos[2] = self.class_losses, len(roots)
-                roots.append(self.class_losses)
-                root_grads.append(self._class_grad)
-            logits = None
-            if self._run_mask:         # (else: mask branch and backbone frozen -- nothing trainable lies under the logits)
-                logits, selection = m.mask(scene, out, boxes, prepared_cut=cut)
-                gm = self._gms.get(k)
-                if do["mask"]:
-                    sc = self._scenes[k]
-                    if self.keep_mask_grads and logits.requires_grad:
-                        logits.retain_grad()
-                    self.mask_out = (selection, descs)
-                    self.mask_losses = self.mask_criterion(logits, selection, descs, sc["gt_label"], sc["gt_mask"])
-                    terms[3] = self.mask_losses
-                    if self.mask_losses.requires_grad:
-                        term_pos[3] = len(roots)
-                        roots.append(self.mask_losses)
-                        root_grads.append(self._mask_grad)
-                    self.n_roi_rows = int(logits.shape[0])
-                elif gm is None or gm.shape != logits.shape:
-                    if self.with_rpn:
-                        # the proposals -- and with them the number of cropped points -- change from step to step: dM is a slice
-                        # of one device-resident pool (drawing 2 M normals on the host per step would be timed as part of it)
-                        pool = self._gm_pool
-                        if pool is None or pool.shape[0] < logits.shape[0] or pool.shape[1:] != logits.shape[1:]:
-                            rows = max(2 * logits.shape[0], 1 << 18)
-                            pool = self._gm_pool = torch.randn((rows,) + tuple(logits.shape[1:]), generator=self._gen).to(self.device)
-                        gm = self._gms[k] = pool[:logits.shape[0]]
-                    else:
-                        gm = self._gms[k] = torch.randn(logits.shape, generator=self._gen).to(self.device)
-                    self.n_roi_rows = sum(g.shape[0] for g in self._gms.values())
-                if logits.requires_grad and logits.shape[0] and not do["mask"]:
-                    roots.append(logits)
-                    root_grads.append(gm if scale == 1.0 else gm * scale)
-            # (an empty crop -- no proposal caught a point: the mask branch contributes nothing on this rank)
-            if zero:
-                self.flat.zero_grad()
-            if self.combiner is not None:
-                self._combine_losses(terms, term_pos, root_grads, zero)
-            if roots:                  # (none: an empty crop in a step that trains the mask branch alone)
-                _backward(roots, root_grads, step_scope=self.step_group and not self.flat.buckets and self.flat.sync)
-        self.out, self.logits, self.fin = out, logits, fin
+            cboxes, cdescs = self.class_selector(overlaps)
+        class_scores, csel = m.run_class(m.backbone.unet.interims, list(cboxes))
+        if self.keep_class_grads:
+            class_scores.retain_grad()
+        sel_scores, sel_labels = self.class_loss_selector(class_scores, csel, cdescs, overlaps, sc["gt_label"])
+        self.class_losses = self.class_criterion(sel_scores, sel_labels)
+        self.class_out = (class_scores, csel, cdescs, sel_labels)
+        ledger.add(self.class_losses, self._loss_grad, TERM_CLASS)
+
+    def _mask_roots(self, ledger, k, scene, out, boxes, descs, cut):
+        """-> the mask logits (an empty crop -- no proposal caught a point: the mask branch contributes nothing on this rank)
+        and the crop's selection."""
+        logits, selection = self.model.mask(scene, out, boxes, prepared_cut=cut)
+        if self._computed["mask"]:
+            sc = self._scenes[k]
+            if self.keep_mask_grads and logits.requires_grad:
+                logits.retain_grad()
+            self.mask_out = (selection, descs)
+            self.mask_losses = self.mask_criterion(logits, selection, descs, sc["gt_label"], sc["gt_mask"])
+            ledger.add(self.mask_losses, self._loss_grad if self.mask_losses.requires_grad else None, TERM_MASK)
+            self.n_roi_rows = int(logits.shape[0])
+        else:
+            gm, drawn = self._seeded(self._gms, k, logits.shape, lambda: self._draw_mask_grad(logits))
+            if drawn:
+                self.n_roi_rows = sum(g.shape[0] for g in self._gms.values())
+            if logits.requires_grad and logits.shape[0]:
+                ledger.add(logits, self._scaled(gm))
+        return logits, selection
+
+    def _draw_mask_grad(self, logits):
+        if not self.with_rpn:
+            return torch.randn(logits.shape, generator=self._gen).to(self.device)
+        # the proposals -- and with them the number of cropped points -- change from step to step: dM is a slice
+        # of one device-resident pool (drawing 2 M normals on the host per step would be timed as part of it)
+        pool = self._gm_pool
+        if pool is None or pool.shape[0] < logits.shape[0] or pool.shape[1:] != logits.shape[1:]:
+            rows = max(2 * logits.shape[0], 1 << 18)
+            pool = self._gm_pool = torch.randn((rows,) + tuple(logits.shape[1:]), generator=self._gen).to(self.device)
+        return pool[:logits.shape[0]]
 
     def forward_only(self, k=0):
         """Evaluation forward of micro-batch k under torch.no_grad() -- what the reference's `eval_model`
         (ndsis/training/training.py:244-304) and `SparseMaskPredictor` (model.py:826-882) run: index build + backbone
         (+ ROI crop + mask branch), no graph, the executor's forward-only slab plan (executor._lean_layout), no
         backward-data weight images.  Same bits as the training forward.  -> (backbone output tensor, mask logits | None)"""
+        run = self._infer(k, mask_boxes=self.mask_boxes)
+        return run["out"], run.get("logits")
+
+    # ---- the inference chain forward_only, predict and evaluate share --------------------------------------------------
+    def _infer(self, k, with_class=False, mask_boxes=None, classify_too=None, own_index=False):
+        """Micro-batch k under torch.no_grad(), on the index structures a helper thread built for it, the next build started
+        (own_index: a pending build is joined and dropped -- it is for "the scene after the last one run", not for k -- and the
+        forward builds its own): backbone -> RPN + proposal selection where the step has an RPN -> with_class: class branch + ClassPredictor on every
+        kept box -> mask branch on the kept boxes (mask_boxes: on the first so many per sample), on the scene's own boxes in a
+        step without RPN.  classify_too: further boxes for the class branch, run before the mask branch as evaluate() always ran
+        them (the ground truth).  -> dict: `out`, `interims`; `roi_score`, `boxes`; `class`, `class_too` (_infer_class);
+        `logits`, `selection`."""
         m = self.model
         if k != self._k:
             self._use_scene(k)
-        md = self._take_index(k)
-        self._start_prefetch(k)
+        md = None
+        if own_index:
+            self.finish()
+        else:
+            md = self._take_index(k)
+            self._start_prefetch(k)
         with torch.no_grad():
             out = m.backbone(self.coords, self.feats, self.size, self.batch_size, metadata=md)
-            logits = None
-            if m.mask is not None:
-                scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
-                boxes = self.boxes
-                if self.with_rpn:
-                    rpn_bbox, rpn_score, anchors = m.run_rpn(m.backbone.unet.interims)
-                    _, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
-                    if self.mask_boxes is not None:
-                        boxes = [b[:self.mask_boxes] for b in boxes]
-                logits, _ = m.mask(scene, out, boxes)
-        return out, logits
+            run = dict(out=out, interims=m.backbone.unet.interims)
+            if m.mask is None:
+                return run
+            boxes = self.boxes
+            if self.with_rpn:
+                rpn_bbox, rpn_score, anchors = m.run_rpn(run["interims"])
+                roi_score, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
+                run["roi_score"], run["boxes"] = list(roi_score), list(boxes)
+                boxes = run["boxes"]
+            if with_class:
+                run["class"] = self._infer_class(run["interims"], boxes)
+                if classify_too is not None:
+                    run["class_too"] = self._infer_class(run["interims"], classify_too)
+            if mask_boxes is not None and self.with_rpn:
+                boxes = [b[:mask_boxes] for b in boxes]
+            run["logits"], run["selection"] = self._infer_mask(out, boxes)
+        return run
+
+    def _infer_class(self, interims, boxes):
+        """-> (class scores, the branch's selection, ClassPredictor's (indices, probabilities, raw indices)) on `boxes`."""
+        from .loss import ClassPredictor
+        class_scores, csel = self.model.run_class(interims, boxes)
+        return class_scores, csel, ClassPredictor()(class_scores, csel)
+
+    def _infer_mask(self, out, boxes):
+        """-> (mask logits, (selection, counts, splits)) of the scene in use on `boxes`."""
+        return self.model.mask((self.coords, self.feats, self.size, self.batch_size, self.splits), out, boxes)
+
+    def _infer_segmentation(self, out):
+        """-> (fp32 segmentation logits, SegmentationPredictor's (classes, probabilities))."""
+        from .loss import SegmentationPredictor
+        seg_logits = self.model.segmentation(out).float()
+        return seg_logits, SegmentationPredictor(True)(seg_logits)
 
     def predict(self, k=0):
         """The reference's evaluation chain (model.py:185-219) on micro-batch k under torch.no_grad(): backbone -> RPN ->
@@ -925,31 +996,18 @@ class SceneStep:
         -> dict with the reference's keys in the reference's spelling: `roi_bbox` (list of [n_s, 2, 3]), `class` (list of
         int64 [n_s]), `class_propabilities` (list of [n_s, 18]), `mask` (list of fp32 [n_s, N_s]), and, when the step has the
         segmentation head, `segmentation_class` (int64 [N]) / `segmentation_probabilites` ([N, 20])."""
-        m = self.model
-        if m.class_branch is None:
+        if self.model.class_branch is None:
             raise ValueError("predict() needs the class branch: build the step with class_loss=True")
         from . import roi
-        from .loss import ClassPredictor, SegmentationPredictor
-        if k != self._k:
-            self._use_scene(k)
-        md = self._take_index(k)
-        self._start_prefetch(k)
+        run = self._infer(k, with_class=True)
+        class_scores, _, (class_indices, class_prob, class_raw) = run["class"]
+        logits, (sel, counts, splits) = run["logits"], run["selection"]
         with torch.no_grad():
-            out = m.backbone(self.coords, self.feats, self.size, self.batch_size, metadata=md)
-            interims = m.backbone.unet.interims
-            rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
-            _, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
-            boxes = list(boxes)
-            class_scores, csel = m.run_class(interims, boxes)
-            class_indices, class_prob, class_raw = ClassPredictor()(class_scores, csel)
-            scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
-            logits, (sel, counts, splits) = m.mask(scene, out, boxes)
             masks = roi.mask_predict(logits, sel, counts, splits, class_raw)
-            result = {"roi_bbox": boxes, "class": list(class_indices), "class_propabilities": list(class_prob), "mask": masks}
-            if m.segmentation is not None:
-                seg = m.segmentation(out)
-                result["segmentation_class"], result["segmentation_probabilites"] = SegmentationPredictor(True)(seg.float())
-            self.predict_out = (class_scores, logits, (sel, counts, splits))       # (for checks)
+            result = {"roi_bbox": run["boxes"], "class": list(class_indices), "class_propabilities": list(class_prob), "mask": masks}
+            if self.model.segmentation is not None:
+                _, (result["segmentation_class"], result["segmentation_probabilites"]) = self._infer_segmentation(run["out"])
+        self.predict_out = (class_scores, logits, (sel, counts, splits))       # (for checks)
         return result
 
     def evaluate(self, scenes=None, *, score_threshold=0.9, mask_threshold=0.5, overlap_thresholds=(0.25, 0.5), eval_on_gt=True):
@@ -967,7 +1025,7 @@ class SceneStep:
         if m.class_branch is None:
             raise ValueError("evaluate() needs the class branch: build the step with class_loss=True")
         from . import evaluation as E
-        from .loss import ClassPredictor, SegmentationPredictor, pack_gt_masks
+        from .loss import pack_gt_masks
         k_cls = m.mask.classes
         bbox_calc = E.BboxOverlapCalculator(score_threshold=score_threshold)
         mask_calc = E.MaskOverlapCalculator(mask_threshold, score_threshold=score_threshold)
@@ -977,33 +1035,23 @@ class SceneStep:
         bin_acc = E.BinaryConfusionAccumulator(E.BinaryMaskConfusionCalculator(mask_threshold))
         seg_acc = None
         for k in (range(self.batches_per_step) if scenes is None else scenes):
-            if k != self._k:
-                self._use_scene(k)
             sc = self._scenes[k]
-            self.finish()                      # a pending prefetch is for "the scene after the last one run", not for k
+            gt_boxes, gt_label = sc["gt_dev"], sc["gt_label"]
+            run = self._infer(k, with_class=True, classify_too=gt_boxes if eval_on_gt else None, own_index=True)
+            out, roi_score, boxes = run["out"], run["roi_score"], run["boxes"]
+            _, _, (class_indices, _, class_raw) = run["class"]
+            logits, (sel, counts, splits) = run["logits"], run["selection"]
             with torch.no_grad():
-                out = m.backbone(self.coords, self.feats, self.size, self.batch_size, metadata=None)
-                interims = m.backbone.unet.interims
-                rpn_bbox, rpn_score, anchors = m.run_rpn(interims)
-                roi_score, boxes, _ = m.roi_selector(rpn_bbox, rpn_score, anchors, self._scene_shape())
-                roi_score, boxes = list(roi_score), list(boxes)
-                class_scores, csel = m.run_class(interims, boxes)
-                class_indices, _, class_raw = ClassPredictor()(class_scores, csel)
-                gt_boxes, gt_label = sc["gt_dev"], sc["gt_label"]
-                if eval_on_gt:
-                    gt_class_scores, gcsel = m.run_class(interims, gt_boxes)
-                    gt_class, _, gt_class_raw = ClassPredictor()(gt_class_scores, gcsel)
-                scene = (self.coords, self.feats, self.size, self.batch_size, self.splits)
-                logits, (sel, counts, splits) = m.mask(scene, out, boxes)
                 pred_bits = E.mask_bits(logits, sel, counts, splits, class_raw, 0, mask_threshold)
                 if "gt_mask" not in sc:
                     sc["gt_mask"] = pack_gt_masks([mk.to(self.device) for mk in sc["gt_mask_cpu"]])
                 gt_mask = sc["gt_mask"]
                 acc["bbox"].add_batch(roi_score, boxes, gt_boxes, list(class_indices), gt_label)
                 acc["mask"].add_batch(roi_score, pred_bits, gt_mask, list(class_indices), gt_label)
-                if eval_on_gt:
+                if eval_on_gt:                 # model.py:194-238: the same two branches on the ground-truth boxes
+                    _, _, (gt_class, _, gt_class_raw) = run["class_too"]
                     pseudo = [b.new_ones((len(b),)) for b in gt_boxes]
-                    glogits, (gsel, gcounts, gsplits) = m.mask(scene, out, gt_boxes)
+                    glogits, (gsel, gcounts, gsplits) = self._infer_mask(out, gt_boxes)
                     gt_bits = E.mask_bits(glogits, gsel, gcounts, gsplits, gt_class_raw, 0, mask_threshold)
                     gtl_bits = E.mask_bits(glogits, gsel, gcounts, gsplits, torch.cat(list(gt_label)), 0, mask_threshold)
                     acc["gtbbox"].add_batch(pseudo, gt_boxes, gt_boxes, list(gt_class), gt_label)
@@ -1012,11 +1060,9 @@ class SceneStep:
                     acc["gtlabelmask"].add_batch(pseudo, gtl_bits, gt_mask, gt_label, gt_label)
                     bin_acc.add_batch(gtl_bits, gt_mask, gt_boxes, gt_label)
                 if m.segmentation is not None and "seg_target" in sc:
-                    seg_logits = m.segmentation(out).float()
-                    seg_class, _ = SegmentationPredictor(True)(seg_logits)
-                    seg_class_count = seg_logits.shape[1]
+                    seg_logits, (seg_class, _) = self._infer_segmentation(out)
                     if seg_acc is None:
-                        seg_acc = E.ConfusionAccumulator(E.ConfusionCalculator(int(seg_class_count)))
+                        seg_acc = E.ConfusionAccumulator(E.ConfusionCalculator(int(seg_logits.shape[1])))
                     seg_acc.add_batch(seg_class, sc["seg_target"])
         helper = E.EvaluationHelper(list(overlap_thresholds), list(range(k_cls)))
         combined, single_class, _, conf, oconf, binary = helper(
@@ -1035,17 +1081,16 @@ class SceneStep:
         self.forward_backward(n - 1, zero=(n == 1))       # the last micro-batch: bucket hooks armed, slices go out
         if self.adam is not None:
             self.adam.lr = self.lr
-            if self.weighting == "count":
-                self.flat.all_reduce_mean(total_weight=self._total_weight)
-                self.flat.adam_step(self.adam)
-            else:
-                self.flat.adam_step_single_rank(self.adam)
-            return
         if self.weighting == "count":
             self.flat.all_reduce_mean(total_weight=self._total_weight)
-            self.flat.sgd_step(self.lr)
-            return
-        self.flat.step_single_rank(self.lr)      # = all_reduce_mean + sgd_step; one rank: no packing into the flat bucket
+            if self.adam is not None:
+                self.flat.adam_step(self.adam)
+            else:
+                self.flat.sgd_step(self.lr)
+        elif self.adam is not None:
+            self.flat.adam_step_single_rank(self.adam)
+        else:
+            self.flat.step_single_rank(self.lr)  # = all_reduce_mean + sgd_step; one rank: no packing into the flat bucket
 
     def finish(self):
         """Join the index build started by the last step (it belongs to the timed region)."""
@@ -1054,62 +1099,82 @@ class SceneStep:
             self._md_next = None
 
     def describe(self):
-        s = (f"BASELINE {self.baseline_entry}: {self.batch_size} " + ("converted sample(s) per GPU (sample.convert_sample + collate),"
-             if self.from_batches else "synthetic ScanNet-shaped sample(s) per GPU,") + f" {self.n_active} "
-             f"active voxels (grid {self.grid[0]}x{self.grid[1]}x{self.grid[2]}, 1.15 points/voxel), U-Net "
-             + "-".join(map(str, self.channels)) + (", 2 pre-act residual blocks/level" if not (self.bottleneck_divisor or self.main_path_relu) else
-                ", 2 residual units/level (" + ", ".join(
-                    ([f"bottleneck_divisor={self.bottleneck_divisor}"] if self.bottleneck_divisor else [])
-                    + (["main_path_relu=True"] if self.main_path_relu else [])) + ")") + ", 2^3/2 conv+deconv"
-             + ("" if (self.relu_first and self.drop_input_relu and self.use_residuals) else " (" + ", ".join(
-                 ([] if self.relu_first else ["relu_first=False: post-activation units, layer -> ReLU input stages"])
-                 + ([] if self.drop_input_relu else ["drop_input_relu=False"])
-                 + ([] if self.use_residuals else ["use_residuals=False: plain convolution blocks"])) + ")")
-             + ((", BatchNormReLU in the residual units (training mode, fp64 statistics; "
-                 + ("step-executor stages, one node per level)" if self.model.backbone.unet._bn_staged() else "layer-by-layer path)"))
-                if self.workload.endswith("-bn") else ""))
-        if self.n_boxes and self.with_rpn:
-            r = self.model.rpn
-            sel = (f"-> anchors that leave the scene dropped (anchor.py:103-113) -> sigmoid, top-1024, boxes clipped to the scene, "
-                   f"one-launch NMS 0.5, <= {self.n_boxes} boxes/sample" + (f", the {self.mask_boxes} best of them per sample" if self.mask_boxes else "")
-                   + f" -> sparse ROI crop ({self.n_roi_rows} cropped points) -> mask "
-                   "branch (SubM1 + 2 units @16, internal U-Net 23-32-48-64, Linear 23-32-18); backward from the backbone "
-                   "output, rpn_bbox, rpn_score and the mask logits")
-            if hasattr(r, "levels"):
-                eng = r.levels[0].engine or r.levels[0].ENGINE
-                up = getattr(r, "anchor_network", None)
+        return "".join((self._describe_backbone(), self._describe_boxes(), self._describe_losses(), self._describe_stages(),
+                        self._describe_container(), self._describe_accumulation(), self._describe_optimizer(),
+                        self._describe_tail()))
 
-                def head(i, l):
-                    if up is None:
-                        return f"1x1 head ({l.n_anchors} anchors/cell)"
-                    return ("up-sampling heads (" + ", ".join("x".join(map(str, g["extra"])) + f": {g['n_anchors']}"
-                                                              for g in up._groups[i]) + " anchors per fine cell)")
-                s += ("; + the REFERENCE's RPN shape INSIDE the step (run.py:525-536,609,847-853): " + " + ".join(
-                    f"SparseToDense of the stride-{l.stride} level ({l.channels} ch) -> dense dilation stack {l.channels}"
-                    + f"-{l.width}" * (len(l.stack) // 2) + " (3^3) + " + head(i, l) for i, l in enumerate(r.levels))
-                    + f", dense layers on engine '{eng}' "
-                    + ("(this library's tile kernels on a fully active grid)" if eng == "tiles" else "(torch / MIOpen conv3d)")
-                    + ("; 1x1 heads (AnchorNetworkConv), every anchor on its level's own grid -- the reference's committed "
-                       "AnchorNetworkUpsample heads: upsample_heads=True " if up is None else
-                       "; the reference's AnchorNetworkUpsample heads (run.py:339,532-537): per level one transposed "
-                       "convolution with kernel = stride per group of anchors, as one row GEMM + one scatter "
-                       "(scn_anchor_up.hip)"
-                       + (", behind a bf16-STORED stack whose last ReLU runs on the bf16 slab (scn_relu_fwd_bf16 / _bwd_bf16); "
-                          "the heads' row GEMM, P, the scatter and rpn_bbox / rpn_score are fp32 "
-                          if self.dtype == "bf16" else " ")) + sel)
-            else:
-                eng = r.engine or r.ENGINE
-                s += (f"; + RPN boundary INSIDE the step, a STAND-IN lighter than the reference's (one anchor level, 2 x {r.width} "
-                      f"stack, {self.n_boxes} kept; the reference: two levels, 5 x 128 / 5 x 256, 256 kept -- `ref-crop-rpn`): "
-                      f"SparseToDense of the stride-{r.stride} level ({r.channels} ch) -> dense dilation stack {r.channels}"
-                      + f"-{r.width}" * (len(r.stack) // 2) + f" (3^3, engine '{eng}': "
-                      + ("this library's tile kernels on a fully active grid" if eng == "tiles" else "torch / MIOpen conv3d")
-                      + f") + 1x1 head ({r.n_anchors} anchors/cell) " + sel)
-        elif self.n_boxes:
-            s += (f"; + {self.n_boxes} fp32 boxes/scene (edges 8-96 voxels) -> sparse ROI crop ({self.n_roi_rows} cropped "
-                  "points) -> mask branch (SubM1 + 2 units @16, internal U-Net 23-32-48-64, Linear 23-32-18); CROP + MASK "
-                  "BRANCH ONLY: the boxes are synthetic and known before the forward (no RPN in this step; "
-                  "--workload cfg3-rpn has it)")
+    # ---- describe(), section by section --------------------------------------------------------------------------------
+    def _describe_backbone(self):
+        units = ", 2 pre-act residual blocks/level"
+        if self.bottleneck_divisor or self.main_path_relu:
+            units = (", 2 residual units/level (" + ", ".join(
+                ([f"bottleneck_divisor={self.bottleneck_divisor}"] if self.bottleneck_divisor else [])
+                + (["main_path_relu=True"] if self.main_path_relu else [])) + ")")
+        stages = ""
+        if not (self.relu_first and self.drop_input_relu and self.use_residuals):
+            stages = " (" + ", ".join(
+                ([] if self.relu_first else ["relu_first=False: post-activation units, layer -> ReLU input stages"])
+                + ([] if self.drop_input_relu else ["drop_input_relu=False"])
+                + ([] if self.use_residuals else ["use_residuals=False: plain convolution blocks"])) + ")"
+        bn = ""
+        if self.workload.endswith("-bn"):
+            bn = (", BatchNormReLU in the residual units (training mode, fp64 statistics; "
+                  + ("step-executor stages, one node per level)" if self.model.backbone.unet._bn_staged() else "layer-by-layer path)"))
+        return (f"BASELINE {self.baseline_entry}: {self.batch_size} " + ("converted sample(s) per GPU (sample.convert_sample + collate),"
+                if self.from_batches else "synthetic ScanNet-shaped sample(s) per GPU,") + f" {self.n_active} "
+                f"active voxels (grid {self.grid[0]}x{self.grid[1]}x{self.grid[2]}, 1.15 points/voxel), U-Net "
+                + "-".join(map(str, self.channels)) + units + ", 2^3/2 conv+deconv" + stages + bn)
+
+    def _describe_boxes(self):
+        """The RPN, the proposal selection, the crop and the mask branch."""
+        if not self.n_boxes:
+            return ""
+        if not self.with_rpn:
+            return (f"; + {self.n_boxes} fp32 boxes/scene (edges 8-96 voxels) -> sparse ROI crop ({self.n_roi_rows} cropped "
+                    "points) -> mask branch (SubM1 + 2 units @16, internal U-Net 23-32-48-64, Linear 23-32-18); CROP + MASK "
+                    "BRANCH ONLY: the boxes are synthetic and known before the forward (no RPN in this step; "
+                    "--workload cfg3-rpn has it)")
+        r = self.model.rpn
+        sel = (f"-> anchors that leave the scene dropped (anchor.py:103-113) -> sigmoid, top-1024, boxes clipped to the scene, "
+               f"one-launch NMS 0.5, <= {self.n_boxes} boxes/sample" + (f", the {self.mask_boxes} best of them per sample" if self.mask_boxes else "")
+               + f" -> sparse ROI crop ({self.n_roi_rows} cropped points) -> mask "
+               "branch (SubM1 + 2 units @16, internal U-Net 23-32-48-64, Linear 23-32-18); backward from the backbone "
+               "output, rpn_bbox, rpn_score and the mask logits")
+        if hasattr(r, "levels"):
+            return self._describe_reference_rpn(r) + sel
+        eng = r.engine or r.ENGINE
+        return (f"; + RPN boundary INSIDE the step, a STAND-IN lighter than the reference's (one anchor level, 2 x {r.width} "
+                f"stack, {self.n_boxes} kept; the reference: two levels, 5 x 128 / 5 x 256, 256 kept -- `ref-crop-rpn`): "
+                f"SparseToDense of the stride-{r.stride} level ({r.channels} ch) -> dense dilation stack {r.channels}"
+                + f"-{r.width}" * (len(r.stack) // 2) + f" (3^3, engine '{eng}': "
+                + ("this library's tile kernels on a fully active grid" if eng == "tiles" else "torch / MIOpen conv3d")
+                + f") + 1x1 head ({r.n_anchors} anchors/cell) " + sel)
+
+    def _describe_reference_rpn(self, r):
+        eng = r.levels[0].engine or r.levels[0].ENGINE
+        up = getattr(r, "anchor_network", None)
+
+        def head(i, l):
+            if up is None:
+                return f"1x1 head ({l.n_anchors} anchors/cell)"
+            return ("up-sampling heads (" + ", ".join("x".join(map(str, g["extra"])) + f": {g['n_anchors']}"
+                                                      for g in up._groups[i]) + " anchors per fine cell)")
+        return ("; + the REFERENCE's RPN shape INSIDE the step (run.py:525-536,609,847-853): " + " + ".join(
+            f"SparseToDense of the stride-{l.stride} level ({l.channels} ch) -> dense dilation stack {l.channels}"
+            + f"-{l.width}" * (len(l.stack) // 2) + " (3^3) + " + head(i, l) for i, l in enumerate(r.levels))
+            + f", dense layers on engine '{eng}' "
+            + ("(this library's tile kernels on a fully active grid)" if eng == "tiles" else "(torch / MIOpen conv3d)")
+            + ("; 1x1 heads (AnchorNetworkConv), every anchor on its level's own grid -- the reference's committed "
+               "AnchorNetworkUpsample heads: upsample_heads=True " if up is None else
+               "; the reference's AnchorNetworkUpsample heads (run.py:339,532-537): per level one transposed "
+               "convolution with kernel = stride per group of anchors, as one row GEMM + one scatter "
+               "(scn_anchor_up.hip)"
+               + (", behind a bf16-STORED stack whose last ReLU runs on the bf16 slab (scn_relu_fwd_bf16 / _bwd_bf16); "
+                  "the heads' row GEMM, P, the scatter and rpn_bbox / rpn_score are fp32 "
+                  if self.dtype == "bf16" else " ")))
+
+    def _describe_losses(self):
+        s = ""
         if self.rpn_loss:
             s += ("; the RPN trains on the reference's RPN loss (BCE-with-logits + smooth L1, sigma 2) against the synthetic "
                   "boxes: device anchor targets, batch-wide 0.35 / 0.15 sampling, max weight 1/8 (scn_rpnloss.hip)")
@@ -1122,30 +1187,39 @@ class SceneStep:
         elif self.n_gt:
             s += f"; ground truth: the first {self.n_gt} synthetic boxes per sample"
         if self.class_loss:
-            cb = self.model.class_branch
-            s += (("; the RESHAPING class head of the dense arm (`simple_class`: no input convolution; RoiAlign to " +
-                   "x".join(map(str, cb.cut_shape)) + " and max pool 2 in one pass out of the stride-" + str(cb.stride) +
-                   " volume of the RPN's dilation stack at its full width (scn_roialign_pool_fwd / _bwd" +
-                   ("" if cb.fused else ": OFF, the two-call pair") + "), " +
-                   ", ".join(f"3^3 same-conv {m.nIn}->{m.nOut}" for m in cb.output_conv_layer) + " on fully active box grids, "
-                   "channel-major flatten, Linear " + "-".join(str(m.in_features) for m in cb.linear_layer
-                                                                if isinstance(m, torch.nn.Linear)) + f"-{cb.num_classes}, fp32"
-                   ") trains the stack too, on the reference's class loss: ") if self.simple_class else
-                  ("; the DENSE class branch (1^3 conv + 1 unit @32 on the stride-" + str(cb.stride) + " volume of the RPN's dilation "
-                   "stack, RoiAlign to " + "x".join(map(str, cb.cut_shape)) + " (scn_roialign.hip), max pool 2 without clamp, "
-                   "2^3/2 conv + unit @64 and @128 on fully active box grids, mean pool, Linear 128-64-18" +
-                   (", its slabs bf16-STORED from the stack's stored volume to the mean pool (class_storage bf16: "
-                    "scn_roialign_fwd_bf16 / scn_dense_maxpool_fwd_bf16, fp32 accumulation, fp32 linear layers)"
-                    if self.class_storage else "") + ") trains the stack too, "
-                   "on the reference's class loss: ") if self.dense_class else
-                  ("; the class branch (SubM1 + 1 unit @32 on the stride-" + str(cb.stride) + " level, sparse "
-                   "ROI cut, 2^3/2 conv + unit @64 and @128, mean pool, Linear 128-64-18) trains on the reference's class loss: "))
+            s += self._describe_class_branch()
             s += ("TrainSelector(0.1, 0, (32, 0, True)) draws <= 32 proposals with IoU >= 0.1 per sample and appends every "
                   "ground-truth box, cross entropy against the associated instance's label (scn_xent.hip)")
         if self.segmentation_loss:
             s += ("; the segmentation head (SubM 1^3 to 20 classes, one row per point) trains on the reference's segmentation "
                   "loss: cross entropy against the instances' labels + 2, -100 (ignored) outside every instance; its gradient "
                   "replaces the synthetic one at the backbone output (scn_xent.hip)")
+        return s
+
+    def _describe_class_branch(self):
+        cb = self.model.class_branch
+        if self.simple_class:
+            return ("; the RESHAPING class head of the dense arm (`simple_class`: no input convolution; RoiAlign to " +
+                    "x".join(map(str, cb.cut_shape)) + " and max pool 2 in one pass out of the stride-" + str(cb.stride) +
+                    " volume of the RPN's dilation stack at its full width (scn_roialign_pool_fwd / _bwd" +
+                    ("" if cb.fused else ": OFF, the two-call pair") + "), " +
+                    ", ".join(f"3^3 same-conv {m.nIn}->{m.nOut}" for m in cb.output_conv_layer) + " on fully active box grids, "
+                    "channel-major flatten, Linear " + "-".join(str(m.in_features) for m in cb.linear_layer
+                                                                 if isinstance(m, torch.nn.Linear)) + f"-{cb.num_classes}, fp32"
+                    ") trains the stack too, on the reference's class loss: ")
+        if self.dense_class:
+            return ("; the DENSE class branch (1^3 conv + 1 unit @32 on the stride-" + str(cb.stride) + " volume of the RPN's dilation "
+                    "stack, RoiAlign to " + "x".join(map(str, cb.cut_shape)) + " (scn_roialign.hip), max pool 2 without clamp, "
+                    "2^3/2 conv + unit @64 and @128 on fully active box grids, mean pool, Linear 128-64-18" +
+                    (", its slabs bf16-STORED from the stack's stored volume to the mean pool (class_storage bf16: "
+                     "scn_roialign_fwd_bf16 / scn_dense_maxpool_fwd_bf16, fp32 accumulation, fp32 linear layers)"
+                     if self.class_storage else "") + ") trains the stack too, "
+                    "on the reference's class loss: ")
+        return ("; the class branch (SubM1 + 1 unit @32 on the stride-" + str(cb.stride) + " level, sparse "
+                "ROI cut, 2^3/2 conv + unit @64 and @128, mean pool, Linear 128-64-18) trains on the reference's class loss: ")
+
+    def _describe_stages(self):
+        s = ""
         if self.train is not None:
             s += ("; TRAINING IN STAGES (train=" + repr(self.train) + "; the reference's mask_only / unet_tweak, run.py:332,"
                   "1414-1427): trainable parts " + ", ".join(self.trainable) + "; frozen parts "
@@ -1156,25 +1230,34 @@ class SceneStep:
         if self.init_missing is not None:
             s += (f"; initialised from an earlier stage's state_dict (init_state, the reference's ignore_load): "
                   f"{len(self.init_missing)} model keys kept their own initialisation, {len(self.init_unused)} keys of the dict unused")
-        if self.combiner is not None:
-            s += ("; the losses are combined by the reference's loss container (loss.LossCombiner: loss = sum of term x "
-                  "exp(-log-weight) + the log-weights, the two RPN weights crossed as in loss.py:111-114; "
-                  + ("multitask_loss: the five log-weights are parameters in the flat buffer" if self.multitask_loss
-                     else "fixed weights " + ", ".join(f"{k} {v:g}" for k, v in self._loss_weights.items()))
-                  + "): one scn_loss_combine launch per micro-batch between forward and backward writes the roots' gradients"
-                  + (" and adds the log-weights' gradients into the flat gradient buffer" if self.multitask_loss else "")
-                  + " (scn_xent.hip)")
-        if self.batches_per_step > 1:
-            s += (f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
-                  "voxels = all of them")
+        return s
+
+    def _describe_container(self):
+        return "" if self.combiner is None else (
+                "; the losses are combined by the reference's loss container (loss.LossCombiner: loss = sum of term x "
+                "exp(-log-weight) + the log-weights, the two RPN weights crossed as in loss.py:111-114; "
+                + ("multitask_loss: the five log-weights are parameters in the flat buffer" if self.multitask_loss
+                   else "fixed weights " + ", ".join(f"{k} {v:g}" for k, v in self._loss_weights.items()))
+                + "): one scn_loss_combine launch per micro-batch between forward and backward writes the roots' gradients"
+                + (" and adds the log-weights' gradients into the flat gradient buffer" if self.multitask_loss else "")
+                + " (scn_xent.hip)")
+
+    def _describe_accumulation(self):
+        return "" if self.batches_per_step == 1 else (
+            f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
+            "voxels = all of them")
+
+    def _describe_optimizer(self):
         if self.adam is not None:
             a = self.adam
-            s += (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + Adam (the reference's optimizer, scannet_config/run.py:"
-                  f"1449) on the flat parameter buffer, lr {self.lr:g}, betas ({a.betas[0]:g}, {a.betas[1]:g}), eps {a.eps:g}, "
-                  f"weight decay {a.weight_decay:g}: one fused update launch per <= 80 tensors")
-        else:
-            s += (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + plain SGD on the flat parameter buffer, lr {self.lr:g} "
-                  "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)")
+            return (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + Adam (the reference's optimizer, scannet_config/run.py:"
+                    f"1449) on the flat parameter buffer, lr {self.lr:g}, betas ({a.betas[0]:g}, {a.betas[1]:g}), eps {a.eps:g}, "
+                    f"weight decay {a.weight_decay:g}: one fused update launch per <= 80 tensors")
+        return (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + plain SGD on the flat parameter buffer, lr {self.lr:g} "
+                "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)")
+
+    def _describe_tail(self):
+        s = ""
         if self.step_group and not self.flat.buckets and self.dtype == "f32" and self.batches_per_step == 1:
             s += ("; fp32 weight gradients of the whole step in one grid per kernel variant after the last backward pass "
                   "(workspaces and unit slabs live until then; step_group=False: per pass)")

@@ -384,3 +384,15 @@ def test_scene_step_evaluate(workload, n_gt):
           f"bbox_AP_0.25 {combined['bbox_AP_0.25']:.4f} segment_avg_iou {combined['segment_avg_iou']:.4f}; worst metric "
           f"difference {worst:.3e} (bound {ER.ap_bound(n_curve):.3e})")
     assert 0 < kept < len(scores)
+
+
+def test_forward_only_and_predict_share_their_chain():
+    """forward_only() and predict() run one inference chain (SceneStep._infer): the same backbone, RPN, selection and boxes --
+    cfg3-rpn cuts nothing off its proposals (`mask_boxes` None) -- so the mask logits of the two are the same bits."""
+    from sparse_rcnn_amd.trainstep import SceneStep
+    st = SceneStep("cfg3-rpn", target=10_000, grid=(128, 128, 64), n_gt=4, class_loss=True, prefetch=False)
+    assert st.mask_boxes is None
+    _, logits = st.forward_only(0)
+    st.predict(0)
+    assert logits.shape[0] > 0 and logits.shape == st.predict_out[1].shape
+    assert torch.equal(logits, st.predict_out[1])

@@ -15,6 +15,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+from call_count import counted, launching_calls
 from sparse_rcnn_amd import _lib as L
 from sparse_rcnn_amd.trainstep import SceneStep
 
@@ -23,29 +24,6 @@ WARMUP = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 NAMES = {1: "gemm_ident", 2: "conv_subm", 3: "conv_child", 4: "rules_child", 5: "rows2", 6: "wgrad_subm", 7: "wgrad2_subm",
          8: "wgrad_down", 9: "wgrad_up", 10: "wgrad_ident", 11: "colsum", 12: "add", 13: "cast", 14: "relu", 15: "relu_bwd",
          16: "add_relu", 17: "bn_stats", 18: "bn_fwd", 19: "bn_bwd"}
-QUIET = ("bytes", "counters", "version", "debug", "timing", "last_error", "step_begin", "step_hold", "step_flush",
-         "step_discard", "group_counts", "requirements", "describe", "launches")
-
-
-class _Counting:
-    """The library handle with every launching entry point counted by name."""
-
-    def __init__(self, lib):
-        self._lib, self.calls, self._made = lib, collections.Counter(), {}
-
-    def __getattr__(self, name):
-        fn = self._made.get(name)
-        if fn is None:
-            raw = getattr(self._lib, name)
-            if any(q in name for q in QUIET):
-                fn = raw
-            else:
-                def fn(*a, _raw=raw, _name=name):
-                    self.calls[_name] += 1
-                    return _raw(*a)
-            self._made[name] = fn
-        return fn
-
 
 def _nodes(t):
     names, seen, todo = collections.Counter(), set(), [t.grad_fn]
@@ -79,30 +57,18 @@ def measure(**kw):
     job.step()
     torch.cuda.synchronize()
     lib.scn_wgrad_group_counts(groups, 1)
-    counting = _Counting(lib)
-    L._lib = counting
-    lib.scn_exec_timing_enable(2)
-    try:
-        job.step()
-        torch.cuda.synchronize()
-    finally:
-        lib.scn_exec_timing_enable(0)
-        L._lib = lib
-    cap = 16384
-    tms, info = (C.c_float * cap)(), (C.c_int64 * (7 * cap))()
-    ops = lib.scn_exec_timing_collect(tms, info, cap)
+    py_calls, op_times = counted(job.step)
     by_op = collections.Counter()                  # us inside the executor's ops of the counted step, per op kind
-    for k in range(ops):
-        by_op[NAMES.get(int(info[7 * k]), int(info[7 * k]))] += float(tms[k]) * 1e3
-    runs = sum(v for k, v in counting.calls.items() if k.startswith("scn_exec_run"))
-    calls = sum(counting.calls.values()) - runs + ops
+    for op, ms_op in op_times:
+        by_op[NAMES.get(op, op)] += ms_op * 1e3
+    calls, runs, ops = launching_calls(py_calls, op_times)
     nodes = _nodes(job.out.features)
     what = job.describe()
     job.finish()
     return dict(ms=ms, calls=calls, exec_runs=runs, exec_ops=ops, nodes=sum(nodes.values()),
                 stage_nodes=sum(v for k, v in nodes.items() if k.startswith("StageFunction")),
                 bn_nodes=sum(v for k, v in nodes.items() if k.startswith("BatchNormReLUFunction")),
-                groups=list(groups), what=what, by_op=by_op, py_calls=counting.calls)
+                groups=list(groups), what=what, by_op=by_op, py_calls=py_calls)
 
 
 if __name__ == "__main__":

@@ -6,67 +6,24 @@ launch kernels per step.
 
 Both steps are built first and stay resident, so each block of either variant sees the same resident tensors; the peak is
 `torch.cuda.max_memory_allocated` over a variant's blocks after `reset_peak_memory_stats` at each block's start.  Calls are counted
-as tools/bn_stages_bench.py counts them: every launching entry point called from Python, plus one per op of every `scn_exec_run*`
+by tools/call_count.py: every launching entry point called from Python, plus one per op of every `scn_exec_run*`
 plan (scn_exec_timing_enable(2) records one entry per op).  `forward_only` of the joint step's model (the evaluation forward:
 index build + backbone + RPN + mask branch under no_grad) is timed beside them for orientation.
 --lr defaults to 0: the update launch does the same work and the weights stay as initialised, so both variants select the same
 proposals and crop the same points in every step (with a learning rate the joint step's RPN moves and the two crops drift apart).
 Without a GPU the command parses its arguments, lists what it would measure and measures nothing."""
 import argparse
-import collections
-import ctypes as C
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from sparse_rcnn_amd import _lib as L
+from call_count import counted, launching_calls
 from sparse_rcnn_amd.trainstep import SceneStep
 
 FOUR = dict(rpn_loss=True, mask_loss=True, class_loss=True, segmentation_loss=True)
 WORKLOADS = {"cfg3-rpn": dict(), "ref-crop-rpn": dict(upsample_heads=True, dense_class=True, n_gt=8)}
-QUIET = ("bytes", "counters", "version", "debug", "timing", "last_error", "step_begin", "step_hold", "step_flush",
-         "step_discard", "group_counts", "requirements", "describe", "launches")
-
-
-class _Counting:
-    """The library handle with every launching entry point counted by name (tools/bn_stages_bench.py)."""
-
-    def __init__(self, lib):
-        self._lib, self.calls, self._made = lib, collections.Counter(), {}
-
-    def __getattr__(self, name):
-        fn = self._made.get(name)
-        if fn is None:
-            raw = getattr(self._lib, name)
-            if any(q in name for q in QUIET):
-                fn = raw
-            else:
-                def fn(*a, _raw=raw, _name=name):
-                    self.calls[_name] += 1
-                    return _raw(*a)
-            self._made[name] = fn
-        return fn
-
-
-def count_calls(job):
-    """Launching library calls of one step: (total, executor passes, ops inside them)."""
-    lib = L.lib()
-    counting = _Counting(lib)
-    L._lib = counting
-    lib.scn_exec_timing_enable(2)
-    try:
-        job.step()
-        torch.cuda.synchronize()
-    finally:
-        lib.scn_exec_timing_enable(0)
-        L._lib = lib
-    cap = 65536
-    tms, info = (C.c_float * cap)(), (C.c_int64 * (7 * cap))()
-    ops = lib.scn_exec_timing_collect(tms, info, cap)
-    runs = sum(v for k, v in counting.calls.items() if k.startswith("scn_exec_run"))
-    return sum(counting.calls.values()) - runs + ops, runs, ops
 
 
 def timed_block(fn, steps):
@@ -109,7 +66,7 @@ def measure(workload, dtype, args, say):
     say(f"== {workload} {dtype}: {joint.n_active} active voxels, {args.blocks} blocks of {args.steps} steps after {args.warmup} warm-up "
         f"steps, Adam lr {args.lr:g}; {resident / 2**20:.0f} MiB resident between blocks (both steps) ==")
     for name, job in jobs.items():
-        calls, runs, ops = count_calls(job)
+        calls, runs, ops = launching_calls(*counted(job.step))
         job.finish()
         say(f"  {name:12s} ms/step per block: " + " ".join(f"{v:8.3f}" for v in ms[name])
             + f"   peak allocated {peak[name] / 2**20:8.0f} MiB   {calls:5d} launching calls/step ({runs} executor passes holding {ops} ops)"
