@@ -2,6 +2,11 @@
 
 Forward / backward definitions follow SURVEY.md Appendix B; each function names the reference call site it serves.
 No function here falls back to PyTorch arithmetic: feature math runs in libscn_mi355x kernels only.
+
+The convolution-type nodes (SubmanifoldConvolution, Convolution, Deconvolution, NetworkInNetwork and its joined form, the residual
+unit) differ in their forward and backward-data kernels; what they do for their parameters is one decision, held once in
+`_param_grads`, and every weight-gradient launch goes through one launcher, `_wgrad`.  The residual unit is ONE node for both
+storage types, `ResidualBlockFunction`.
 """
 from __future__ import annotations
 
@@ -91,14 +96,18 @@ _tb_sizes = {}
 FUSED_K = True      # scn_conv_tiles adds its K-chunk partial sums inside the launch (False: second launch k_conv_ts_sum)
 
 
+def _cache_put(cache, key, value):
+    """A miss of one of the size caches: they are bounded -- one that holds more than 4096 keys starts again empty."""
+    if len(cache) > 4096:
+        cache.clear()
+    cache[key] = value
+    return value
+
+
 def _conv_tiles_scratch_bytes(cin, n_out, cout):
     key = (cin, n_out, cout)
     v = _ts_scratch_cache.get(key)
-    if v is None:
-        if len(_ts_scratch_cache) > 4096:
-            _ts_scratch_cache.clear()
-        v = _ts_scratch_cache[key] = L.lib().scn_conv_tiles_scratch_bytes(cin, n_out, cout)
-    return v
+    return v if v is not None else _cache_put(_ts_scratch_cache, key, L.lib().scn_conv_tiles_scratch_bytes(cin, n_out, cout))
 
 
 def conv_rules(X, tiles, n_out, W, bias, cout, flags=0, residual=None, relu_mask=None, n_rules=0, image=None):
@@ -376,10 +385,8 @@ def conv_rules_bf16(X, tiles, n_out, W, bias, cout, flags=0, residual=None, relu
     key = (cin, n_out, cout)
     sz = _tb_sizes.get(key)
     if sz is None:
-        if len(_tb_sizes) > 4096:
-            _tb_sizes.clear()
-        sz = _tb_sizes[key] = (lib.scn_conv_tiles_bf16_scratch_bytes(cin, n_out, cout),
-                               lib.scn_conv_tiles_bf16_arrival_counters(cin, n_out, cout))
+        sz = _cache_put(_tb_sizes, key, (lib.scn_conv_tiles_bf16_scratch_bytes(cin, n_out, cout),
+                                         lib.scn_conv_tiles_bf16_arrival_counters(cin, n_out, cout)))
     scratch = L.scratch(sz[0], X.device)
     arr = L.arrival(sz[1], X.device) if (sz[1] and FUSED_K) else None
 
@@ -428,71 +435,86 @@ def _offset_chunk(prefix_host, o0):
     return prefix_host if o0 == 0 else C.cast(C.addressof(prefix_host.contents) + 8 * o0, C.POINTER(C.c_int64))
 
 
-def wgrad_rules_bf16(X, dY, in_rows, out_rows, prefix_host, n_off, flags=0):
-    """scn_wgrad_rules_bf16: dW (fp32) from bf16-stored X and dY -- the weight gradient of the bf16 storage path."""
-    if n_off > 32:          # (a 4^3 stride, a 5^3 filter: chunks of 32 offsets)
-        return torch.cat([wgrad_rules_bf16(X, dY, in_rows, out_rows, _offset_chunk(prefix_host, o0), min(32, n_off - o0), flags)
-                          for o0 in range(0, n_off, 32)], 0)
+def _wgrad(Xs, dYs, in_rows, out_rows, prefix_host, n_off, db_offsets, flags, want_db):
+    """The one weight-gradient launcher; the public forms below are fronts of it.  Xs, dYs: ONE operand pair (two tensors) or a
+    sequence of 2 ... 4 pairs that share the rule list and their channel counts; fp32 or bf16-stored, of one storage type,
+    contiguous (checked where it was always checked: bf16-stored operands and the several-pair form).  At most 32 offsets.
+    The entry point follows from (storage type, one pair or several, want_db):
+        one pair, no db     scn_wgrad_rules / _bf16
+        one pair, db        scn_wgrad_bias_rules / _bf16           (db over the rule lists of the offsets in `db_offsets`)
+        several pairs       scn_wgrad_bias_rules_n / _n_bf16       (db where want_db, else a NULL db)
+    -> fp32 (dW [n_off, cin, cout], db [cout] or None); several pairs: (dW [n_prob, n_off, cin, cout], db [n_prob, cout] or None)."""
     lib = L.lib()
-    for t in (X, dY):
-        if t.dtype != torch.bfloat16 or not t.is_contiguous():
-            raise L.ScnError("wgrad_rules_bf16 takes contiguous torch.bfloat16 operands")
+    one = torch.is_tensor(Xs)
+    X, dY = (Xs, dYs) if one else (Xs[0], dYs[0])
+    hb = X.dtype == torch.bfloat16
     cin, cout = X.shape[1], dY.shape[1]
-    nbytes = lib.scn_wgrad_scratch_bytes(cin, cout, prefix_host, n_off)
+    dev = X.device
+    if one:
+        if hb and (dY.dtype != torch.bfloat16 or not (X.is_contiguous() and dY.is_contiguous())):
+            raise L.ScnError("the weight gradient takes contiguous operands of one storage type")
+        n_prob = 1
+        nbytes = lib.scn_wgrad_scratch_bytes(cin, cout, prefix_host, n_off)
+        w_shape, b_shape = (n_off, cin, cout), (cout,)
+    else:
+        n_prob = len(Xs)
+        if any(t.dtype != X.dtype or not t.is_contiguous() for t in Xs + dYs):
+            raise L.ScnError("the weight gradient takes contiguous operands of one storage type")
+        nbytes = lib.scn_wgrad_scratch_bytes_n(cin, cout, prefix_host, n_off, n_prob)
+        w_shape, b_shape = (n_prob, n_off, cin, cout), (n_prob, cout)
     if nbytes < 0:
-        raise L.ScnError("scn_wgrad_scratch_bytes: bad arguments")
-    scratch = L.scratch(nbytes, X.device)
-    dW = torch.empty((n_off, cin, cout), dtype=torch.float32, device=X.device)
-    profiling.timed("k_wgrad_rules_bf16", 0.0, 0.0, lambda: L.check(lib.scn_wgrad_rules_bf16(
-        L.ptr(X), cin, L.ptr(dY), cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host, n_off, L.ptr(dW), L.ptr(scratch),
-        flags, L.stream())))
-    return dW
+        raise L.ScnError("scn_wgrad_scratch_bytes" + ("" if one else "_n") + ": bad arguments")
+    scratch = L.scratch(nbytes, dev)
+    dW = torch.empty(w_shape, dtype=torch.float32, device=dev)
+    db = torch.empty(b_shape, dtype=torch.float32, device=dev) if want_db else None
+    if not one:
+        entry = lib.scn_wgrad_bias_rules_n_bf16 if hb else lib.scn_wgrad_bias_rules_n
+        xp = (C.c_void_p * n_prob)(*[t.data_ptr() for t in Xs])
+        yp = (C.c_void_p * n_prob)(*[t.data_ptr() for t in dYs])
+
+        def run():
+            L.check(entry(xp, yp, n_prob, cin, cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host, n_off, L.ptr(dW), L.ptr(db),
+                          db_offsets, L.ptr(scratch), flags, L.stream()))
+    elif want_db:
+        entry = lib.scn_wgrad_bias_rules_bf16 if hb else lib.scn_wgrad_bias_rules
+
+        def run():
+            L.check(entry(L.ptr(X), cin, L.ptr(dY), cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host, n_off, L.ptr(dW),
+                          L.ptr(db), db_offsets, L.ptr(scratch), flags, L.stream()))
+    else:
+        entry = lib.scn_wgrad_rules_bf16 if hb else lib.scn_wgrad_rules
+
+        def run():
+            L.check(entry(L.ptr(X), cin, L.ptr(dY), cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host, n_off, L.ptr(dW),
+                          L.ptr(scratch), flags, L.stream()))
+    if hb and one and not want_db:
+        flops = moved = 0.0             # (a reporting gap as old as the bf16 no-bias form: it tells the timer nothing)
+    else:
+        P = int(prefix_host[n_off] - prefix_host[0])
+        flops = 2.0 * n_prob * P * cin * cout
+        moved = n_prob * ((2.0 if hb else 4.0) * (X.shape[0] * cin + dY.shape[0] * cout) + 4.0 * n_off * cin * cout + 8.0 * P)
+    profiling.timed("k_wgrad_rules_bf16" if hb else "k_wgrad_rules", flops, moved, run)
+    return dW, db
 
 
 def wgrad_rules(X, dY, in_rows, out_rows, prefix_host, n_off, flags=0):
-    if _is_bf16(X):
-        return wgrad_rules_bf16(X, dY, in_rows, out_rows, prefix_host, n_off, flags)
-    if n_off > 32:
+    """dW alone (scn_wgrad_rules; bf16-stored operands: scn_wgrad_rules_bf16, fp32 result)."""
+    if n_off > 32:          # (a 4^3 stride, a 5^3 filter: chunks of 32 offsets)
         return torch.cat([wgrad_rules(X, dY, in_rows, out_rows, _offset_chunk(prefix_host, o0), min(32, n_off - o0), flags)
                           for o0 in range(0, n_off, 32)], 0)
-    lib = L.lib()
-    cin, cout = X.shape[1], dY.shape[1]
-    nbytes = lib.scn_wgrad_scratch_bytes(cin, cout, prefix_host, n_off)
-    if nbytes < 0:
-        raise L.ScnError("scn_wgrad_scratch_bytes: bad arguments")
-    scratch = L.scratch(nbytes, X.device)
-    dW = _new((n_off, cin, cout), X)
-    P = int(prefix_host[n_off] - prefix_host[0])
+    return _wgrad(X, dY, in_rows, out_rows, prefix_host, n_off, 0, flags, False)[0]
 
-    def run():
-        L.check(lib.scn_wgrad_rules(L.ptr(X), cin, L.ptr(dY), cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host,
-                                    n_off, L.ptr(dW), L.ptr(scratch), flags, L.stream()))
-    profiling.timed("k_wgrad_rules", 2.0 * P * cin * cout,
-                    4.0 * (X.shape[0] * cin + dY.shape[0] * cout + n_off * cin * cout) + 8.0 * P, run)
-    return dW
+
+def wgrad_rules_bf16(X, dY, in_rows, out_rows, prefix_host, n_off, flags=0):
+    """`wgrad_rules` that refuses anything but bf16-stored operands -- the weight gradient of the bf16 storage path."""
+    if not (_is_bf16(X) and _is_bf16(dY)):
+        raise L.ScnError("wgrad_rules_bf16 takes contiguous torch.bfloat16 operands")
+    return wgrad_rules(X, dY, in_rows, out_rows, prefix_host, n_off, flags)
 
 
 def wgrad_bias_rules(X, dY, in_rows, out_rows, prefix_host, n_off, db_offsets, flags=0):
     """dW and db in one pass (scn_wgrad_bias_rules; bf16-stored operands: scn_wgrad_bias_rules_bf16, fp32 results)."""
-    cin, cout = X.shape[1], dY.shape[1]
-    lib = L.lib()
-    hb = _is_bf16(X)
-    if hb and (dY.dtype != torch.bfloat16 or not (X.is_contiguous() and dY.is_contiguous())):
-        raise L.ScnError("wgrad_bias_rules takes contiguous operands of one storage type")
-    nbytes = lib.scn_wgrad_scratch_bytes(cin, cout, prefix_host, n_off)
-    scratch = L.scratch(nbytes, X.device)
-    dW = torch.empty((n_off, cin, cout), dtype=torch.float32, device=X.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=X.device)
-    P = int(prefix_host[n_off] - prefix_host[0])
-    entry = lib.scn_wgrad_bias_rules_bf16 if hb else lib.scn_wgrad_bias_rules
-    es = 2.0 if hb else 4.0
-
-    def run():
-        L.check(entry(L.ptr(X), cin, L.ptr(dY), cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host,
-                      n_off, L.ptr(dW), L.ptr(db), db_offsets, L.ptr(scratch), flags, L.stream()))
-    profiling.timed("k_wgrad_rules_bf16" if hb else "k_wgrad_rules", 2.0 * P * cin * cout,
-                    es * (X.shape[0] * cin + dY.shape[0] * cout) + 4.0 * n_off * cin * cout + 8.0 * P, run)
-    return dW, db
+    return _wgrad(X, dY, in_rows, out_rows, prefix_host, n_off, db_offsets, flags, True)
 
 
 # residual units: both weight gradients in one launch (False / SCN_WGRAD_PAIR=0: one call each -- cross-check, A/B)
@@ -504,34 +526,11 @@ def wgrad_bias_rules_n(Xs, dYs, in_rows, out_rows, prefix_host, n_off, db_offset
     counts -- the two of a residual unit, the four of two stacked units -- in one launch + one sum
     (scn_wgrad_bias_rules_n / _bf16): operand pairs (Xs[p], dYs[p]) of one storage type.
     -> fp32 dW [n_prob, n_off, cin, cout], db [n_prob, cout] or None."""
-    lib = L.lib()
-    n_prob = len(Xs)
-    cin, cout = Xs[0].shape[1], dYs[0].shape[1]
-    hb = _is_bf16(Xs[0])
-    if any(_is_bf16(t) != hb or not t.is_contiguous() for t in tuple(Xs) + tuple(dYs)):
-        raise L.ScnError("wgrad_bias_rules_n takes contiguous operands of one storage type")
-    entry = lib.scn_wgrad_bias_rules_n_bf16 if hb else lib.scn_wgrad_bias_rules_n
-    es = 2.0 if hb else 4.0
-    nbytes = lib.scn_wgrad_scratch_bytes_n(cin, cout, prefix_host, n_off, n_prob)
-    if nbytes < 0:
-        raise L.ScnError("scn_wgrad_scratch_bytes_n: bad arguments")
-    scratch = L.scratch(nbytes, Xs[0].device)
-    dW = torch.empty((n_prob, n_off, cin, cout), dtype=torch.float32, device=Xs[0].device)
-    db = torch.empty((n_prob, cout), dtype=torch.float32, device=Xs[0].device) if db_offsets else None
-    P = int(prefix_host[n_off] - prefix_host[0])
-    xp = (C.c_void_p * n_prob)(*[t.data_ptr() for t in Xs])
-    yp = (C.c_void_p * n_prob)(*[t.data_ptr() for t in dYs])
-
-    def run():
-        L.check(entry(xp, yp, n_prob, cin, cout, L.ptr(in_rows), L.ptr(out_rows), prefix_host, n_off, L.ptr(dW), L.ptr(db),
-                      db_offsets, L.ptr(scratch), flags, L.stream()))
-    profiling.timed("k_wgrad_rules_bf16" if hb else "k_wgrad_rules", 2.0 * n_prob * P * cin * cout,
-                    n_prob * (es * (Xs[0].shape[0] * cin + dYs[0].shape[0] * cout) + 4.0 * n_off * cin * cout + 8.0 * P), run)
-    return dW, db
+    return _wgrad(tuple(Xs), tuple(dYs), in_rows, out_rows, prefix_host, n_off, db_offsets, flags, bool(db_offsets))
 
 
 def wgrad_bias_rules2(X0, dY0, X1, dY1, in_rows, out_rows, prefix_host, n_off, db_offsets, flags=0):
-    return wgrad_bias_rules_n((X0, X1), (dY0, dY1), in_rows, out_rows, prefix_host, n_off, db_offsets, flags)
+    return _wgrad((X0, X1), (dY0, dY1), in_rows, out_rows, prefix_host, n_off, db_offsets, flags, bool(db_offsets))
 
 
 def colsum(dY):
@@ -545,17 +544,46 @@ def colsum(dY):
     return db
 
 
-def _on_leaf_stream(dY, fn):
-    """Weight / bias gradients are leaves of the backward graph.  Queuing them on a second HIP stream (so that their
-    workgroups fill the CUs the backward-data chain leaves idle) was measured in round 1: no gain, and the bucketed
-    all-reduce hooks of dp.py would have needed an extra stream join -- removed; leaves run on the main stream."""
-    return fn()
-
-
 def _identity_prefix(n):
     h = L.host_i64(2)
     h[0], h[1] = 0, n
     return h
+
+
+def _param_grads(X, dY, rules, n_off, shape, want_w, want_b, bias_offsets=0, flags=0, swap=False):
+    """The parameter gradients of a convolution-type layer, Y[out] += X[in] . W[offset] over a rule list -- the one place that
+    decides how they are computed:
+        dW and db wanted, and the node names `bias_offsets`     one pass (scn_wgrad_bias_rules)
+        dW wanted                                               the weight gradient alone (scn_wgrad_rules, chunked above 32 offsets)
+        db wanted and not yet there                             colsum(dY)
+    rules: the layer's `metadata.Rules`, or None for a 1x1 layer (an identity prefix over the rows of dY, no row arrays); swap: the
+    rule list with its row roles exchanged (a Deconvolution runs its Convolution's).  The rows are asked for only where a weight
+    gradient is wanted: a `Rules` object compacts its lists at the first request, one launch a frozen layer must not cause.
+    bias_offsets: the mask of offsets whose rule lists together name every row of dY exactly once (the centre of a submanifold
+    filter, every offset of a Deconvolution, the one offset of a 1x1 layer); 0 where the node never takes the one-pass form (a
+    strided Convolution: a coarse row occurs once per child it has, and no set of offsets sorts that out) or has more offsets than
+    that form is used for.
+    -> (dW viewed as `shape`, db), each None where not wanted.  (Called with positional arguments: it runs once per layer and step.)
+    These are leaves of the backward graph and run on the main stream (a second stream for them was measured in round 1: no gain)."""
+    dW = db = None
+    if want_w:
+        if rules is None:
+            in_rows = out_rows = None
+            prefix_host = _identity_prefix(dY.shape[0])
+        elif swap:
+            in_rows, out_rows, prefix_host = rules.out_rows, rules.in_rows, rules.prefix_host
+        else:
+            in_rows, out_rows, prefix_host = rules.in_rows, rules.out_rows, rules.prefix_host
+        if want_b and bias_offsets:
+            dW, db = _wgrad(X, dY, in_rows, out_rows, prefix_host, n_off, bias_offsets, flags, True)
+        elif n_off > 32:
+            dW = wgrad_rules(X, dY, in_rows, out_rows, prefix_host, n_off, flags)
+        else:
+            dW = _wgrad(X, dY, in_rows, out_rows, prefix_host, n_off, 0, flags, False)[0]
+        dW = dW.view(shape)
+    if want_b and db is None:
+        db = colsum(dY)
+    return dW, db
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -593,7 +621,7 @@ class SubmanifoldConvolutionFunction(torch.autograd.Function):
         n_off = rb.k ** 3
         cin = X.shape[1]
         fl = L.F_RELU_IN if ctx.relu_in else 0
-        dX = dW = db = None
+        dX = None
         if ctx.needs_input_grad[0]:
             if USE_TILES and rb.rules is not None and rb.tiles is not None:
                 dX = conv_rules(dY, rb.tiles, rb.n, W, None, cin, L.F_W_TRANSPOSED | L.F_OFF_REVERSE,
@@ -602,23 +630,9 @@ class SubmanifoldConvolutionFunction(torch.autograd.Function):
                 dX = gemm_table(dY, rb.table, n_off, rb.n, W, None, cin, L.F_W_TRANSPOSED | L.F_OFF_REVERSE,
                                 relu_mask=X if ctx.relu_in else None,
                                 n_rules=rb.rules.count if rb.rules is not None else rb.n)
-        def leaves():
-            dW = db = None
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
-                ir, orr = (None, None) if rb.k == 1 else (rb.rules.in_rows, rb.rules.out_rows)
-                ph = _identity_prefix(rb.n) if rb.k == 1 else rb.rules.prefix_host
-                if want_b and n_off <= 32:      # the centre offset lists every row once: bias gradient from the same pass
-                    dW, db = wgrad_bias_rules(X, dY, ir, orr, ph, n_off, 1 << (n_off // 2), fl)
-                else:
-                    dW = wgrad_rules(X, dY, ir, orr, ph, n_off, fl)
-                    if want_b:
-                        db = colsum(dY)
-                dW = dW.view_as(W)
-            elif want_b:
-                db = colsum(dY)
-            return dW, db
-        dW, db = _on_leaf_stream(dY, leaves)
+        # the centre offset lists every row once (filters of up to 32 offsets: one call of the one-pass form)
+        dW, db = _param_grads(X, dY, None if rb.k == 1 else rb.rules, n_off, W.shape, ctx.needs_input_grad[1],
+                              ctx.has_bias and ctx.needs_input_grad[2], 1 << (n_off // 2) if n_off <= 32 else 0, fl)
         dR = dY if (len(ctx.needs_input_grad) > 7 and ctx.needs_input_grad[7]) else None
         return dX, dW, db, None, None, None, None, dR
 
@@ -631,11 +645,23 @@ class ResidualBlockFunction(torch.autograd.Function):
     """Same kernels as the layer-by-layer path; what the fusion removes is the glue: the AddTable runs in the epilogue
     of the second convolution (forward) and the sum of the two gradient paths of x in the epilogue of the first
     convolution's backward-data kernel (SCN_F_RESIDUAL_LAST: dX = mask(conv1^T dY1) + dY) -- no elementwise launches, one
-    autograd node instead of two."""
+    autograd node instead of two.
+
+    One node for both storage types, told apart by `features.dtype`.  bf16-STORED features (BASELINE configs 3-5): x,
+    the intermediate h, the result and every gradient tensor of the block are torch.bfloat16; the parameters stay fp32 (rounded to
+    bf16 as they are staged into LDS) and their gradients come back fp32.  Six launches either way: the tile convolution x 4
+    (two forward, two backward-data with the ReLU mask / the skip gradient in the epilogue) and the weight gradients."""
 
     @staticmethod
     def forward(ctx, features, w1, b1, w2, b2, metadata: Metadata, spatial_size):
-        X, W1, W2 = _f32(features), _f32(w1), _f32(w2)
+        hb = _is_bf16(features)
+        if hb:
+            if features.shape[1] % 8 != 0 or w1.shape[-1] % 8 != 0:
+                raise L.ScnError("bf16 storage needs channel counts that are multiples of 8 (16-byte row pieces)")
+            X = features.contiguous()
+        else:
+            X = _f32(features)
+        W1, W2 = _f32(w1), _f32(w2)
         rb = metadata.subm_rulebook(spatial_size, 3)
         B1 = _f32(b1) if b1 is not None else None
         B2 = _f32(b2) if b2 is not None else None
@@ -644,106 +670,49 @@ class ResidualBlockFunction(torch.autograd.Function):
         _rec_relu(X); _rec_relu(Y1)
         ctx.save_for_backward(X, Y1, W1, W2)
         ctx.rb, ctx.has_b1, ctx.has_b2 = rb, b1 is not None, b2 is not None
+        # the packed backward-data images of the forward that is running (bf16 storage alone has any)
+        ctx.bwd_images = (packed_image(W1, W1.shape[-1], W1.shape[1], 27, _BACK),
+                          packed_image(W2, W2.shape[-1], W2.shape[1], 27, _BACK)) if hb else (None, None)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         X, Y1, W1, W2 = ctx.saved_tensors
         rb, r = ctx.rb, ctx.rb.rules
-        dY = _f32(dY)
+        dY = dY.to(torch.bfloat16).contiguous() if _is_bf16(X) else _f32(dY)
         need = ctx.needs_input_grad
-        back = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
-        dY1 = conv_rules(dY, rb.tiles, rb.n, W2, None, W2.shape[1], back, relu_mask=Y1, n_rules=r.count)
-        centre = 1 << 13
-
-        def wgrad(Xin, G, W, want_w, want_b):
-            if want_w and want_b:
-                dW, db = wgrad_bias_rules(Xin, G, r.in_rows, r.out_rows, r.prefix_host, 27, centre, L.F_RELU_IN)
-                return dW.view_as(W), db
-            if want_w:
-                return wgrad_rules(Xin, G, r.in_rows, r.out_rows, r.prefix_host, 27, L.F_RELU_IN).view_as(W), None
-            return None, (colsum(G) if want_b else None)
+        centre = 1 << 13                # the centre offset lists every row once
+        dY1 = conv_rules(dY, rb.tiles, rb.n, W2, None, W2.shape[1], _BACK, relu_mask=Y1, n_rules=r.count, image=ctx.bwd_images[1])
         want_b1, want_b2 = ctx.has_b1 and need[2], ctx.has_b2 and need[4]
-        # both weight gradients in one launch (same rule list, same channel counts; bias gradients both or neither)
+        # both weight gradients in one launch (same rule list, same channel counts; bias gradients both or neither).  The launch
+        # wants contiguous operands, and all four are by construction in both storage types: X left the forward's `_f32` /
+        # `.contiguous()`, dY the line above, Y1 and dY1 are slabs `conv_rules` allocated
         pair = (WGRAD_PAIR and need[1] and need[3] and want_b1 == want_b2 and W1.shape == W2.shape
-                and W1.shape[1] == W1.shape[2] and r.prefix_host[0] == 0 and X.is_contiguous() and Y1.is_contiguous()
-                and dY.is_contiguous() and dY1.is_contiguous())
+                and W1.shape[1] == W1.shape[2] and r.prefix_host[0] == 0)
         if not pair:
-            dW2, db2 = _on_leaf_stream(dY, lambda: wgrad(Y1, dY, W2, need[3], want_b2))
+            dW2, db2 = _param_grads(Y1, dY, r, 27, W2.shape, need[3], want_b2, centre, L.F_RELU_IN)
         dX = None
         if need[0]:
-            dX = conv_rules(dY1, rb.tiles, rb.n, W1, None, W1.shape[1], back | L.F_RESIDUAL_LAST, relu_mask=X,
-                            residual=dY, n_rules=r.count)
+            dX = conv_rules(dY1, rb.tiles, rb.n, W1, None, W1.shape[1], _BACK | L.F_RESIDUAL_LAST, relu_mask=X,
+                            residual=dY, n_rules=r.count, image=ctx.bwd_images[0])
         if pair:
-            dWp, dbp = wgrad_bias_rules2(X, dY1, Y1, dY, r.in_rows, r.out_rows, r.prefix_host, 27,
-                                         centre if want_b1 else 0, L.F_RELU_IN)
+            dWp, dbp = wgrad_bias_rules2(X, dY1, Y1, dY, r.in_rows, r.out_rows, r.prefix_host, 27, centre if want_b1 else 0,
+                                         L.F_RELU_IN)
             dW1, dW2 = dWp[0].view_as(W1), dWp[1].view_as(W2)
             db1, db2 = (dbp[0], dbp[1]) if dbp is not None else (None, None)
         else:
-            dW1, db1 = _on_leaf_stream(dY1, lambda: wgrad(X, dY1, W1, need[1], want_b1))
+            dW1, db1 = _param_grads(X, dY1, r, 27, W1.shape, need[1], want_b1, centre, L.F_RELU_IN)
         return dX, dW1, db1, dW2, db2, None, None
 
 
-class ResidualBlockFunctionBF16(torch.autograd.Function):
-    """ResidualBlockFunction for bf16-STORED features (BASELINE configs 3-5): x, the intermediate h, the
-    result and every gradient tensor of the block are torch.bfloat16; the parameters stay fp32 (rounded to bf16 as
-    they are staged into LDS) and their gradients come back fp32.  Six launches: scn_conv_tiles_bf16 x 4 (two forward,
-    two backward-data with the ReLU mask / the skip gradient in the epilogue) and scn_wgrad_rules_bf16 x 2."""
+class ResidualBlockFunctionBF16(ResidualBlockFunction):
+    """`ResidualBlockFunction` under the name the bf16 storage path had: it refuses anything but bf16-stored features."""
 
     @staticmethod
-    def forward(ctx, features, w1, b1, w2, b2, metadata: Metadata, spatial_size):
+    def forward(ctx, features, *rest):
         if features.dtype != torch.bfloat16:
             raise L.ScnError("ResidualBlockFunctionBF16 takes torch.bfloat16 features")
-        if features.shape[1] % 8 != 0 or w1.shape[-1] % 8 != 0:
-            raise L.ScnError("bf16 storage needs channel counts that are multiples of 8 (16-byte row pieces)")
-        X = features.contiguous()
-        W1, W2 = _f32(w1), _f32(w2)
-        rb = metadata.subm_rulebook(spatial_size, 3)
-        B1 = _f32(b1) if b1 is not None else None
-        B2 = _f32(b2) if b2 is not None else None
-        Y1 = conv_rules_bf16(X, rb.tiles, rb.n, W1, B1, W1.shape[-1], L.F_RELU_IN, n_rules=rb.rules.count)
-        Y = conv_rules_bf16(Y1, rb.tiles, rb.n, W2, B2, W2.shape[-1], L.F_RELU_IN, residual=X, n_rules=rb.rules.count)
-        _rec_relu(X); _rec_relu(Y1)
-        ctx.save_for_backward(X, Y1, W1, W2)
-        ctx.rb, ctx.has_b1, ctx.has_b2 = rb, b1 is not None, b2 is not None
-        ctx.bwd_images = (packed_image(W1, W1.shape[-1], W1.shape[1], 27, _BACK),
-                          packed_image(W2, W2.shape[-1], W2.shape[1], 27, _BACK))
-        return Y
-
-    @staticmethod
-    def backward(ctx, dY):
-        X, Y1, W1, W2 = ctx.saved_tensors
-        rb, r = ctx.rb, ctx.rb.rules
-        dY = dY.to(torch.bfloat16).contiguous()
-        need = ctx.needs_input_grad
-        back = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
-        dY1 = conv_rules_bf16(dY, rb.tiles, rb.n, W2, None, W2.shape[1], back, relu_mask=Y1, image=ctx.bwd_images[1],
-                              n_rules=r.count)
-
-        def wgrad(Xin, G, W, want_w, want_b):
-            if want_w and want_b:        # the centre offset lists every row once: bias gradient from the same pass
-                dW, db = wgrad_bias_rules(Xin, G, r.in_rows, r.out_rows, r.prefix_host, 27, 1 << 13, L.F_RELU_IN)
-                return dW.view_as(W), db
-            dW = wgrad_rules_bf16(Xin, G, r.in_rows, r.out_rows, r.prefix_host, 27, L.F_RELU_IN).view_as(W) \
-                if want_w else None
-            return dW, (colsum(G) if want_b else None)
-        want_b1, want_b2 = ctx.has_b1 and need[2], ctx.has_b2 and need[4]
-        pair = (WGRAD_PAIR and need[1] and need[3] and want_b1 == want_b2 and W1.shape == W2.shape
-                and W1.shape[1] == W1.shape[2] and r.prefix_host[0] == 0 and dY1.is_contiguous())
-        if not pair:
-            dW2, db2 = wgrad(Y1, dY, W2, need[3], want_b2)
-        dX = None
-        if need[0]:
-            dX = conv_rules_bf16(dY1, rb.tiles, rb.n, W1, None, W1.shape[1], back | L.F_RESIDUAL_LAST, relu_mask=X,
-                                 residual=dY, image=ctx.bwd_images[0], n_rules=r.count)
-        if pair:            # both weight gradients in one launch (see ResidualBlockFunction)
-            dWp, dbp = wgrad_bias_rules2(X, dY1, Y1, dY, r.in_rows, r.out_rows, r.prefix_host, 27,
-                                         (1 << 13) if want_b1 else 0, L.F_RELU_IN)
-            dW1, dW2 = dWp[0].view_as(W1), dWp[1].view_as(W2)
-            db1, db2 = (dbp[0], dbp[1]) if dbp is not None else (None, None)
-        else:
-            dW1, db1 = wgrad(X, dY1, W1, need[1], want_b1)
-        return dX, dW1, db1, dW2, db2, None, None
+        return ResidualBlockFunction.forward(ctx, features, *rest)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -773,18 +742,12 @@ class ConvolutionFunction(torch.autograd.Function):
         rb, r = ctx.rb, ctx.rb.rules
         dY = _feat(dY)
         fl = L.F_RELU_IN if ctx.relu_in else 0
-        dX = dW = db = None
+        dX = None
         if ctx.needs_input_grad[0]:      # dX[f] = dY[parent f] . W[off f]^T : rule list with roles swapped
             dX = gemm_rules(dY, r.out_rows, r.in_rows, r.prefix_host, rb.n_off, rb.n_fine, W, None, X.shape[1],
                             L.F_W_TRANSPOSED, relu_mask=X if ctx.relu_in else None)
-        def leaves():
-            dW = db = None
-            if ctx.needs_input_grad[1]:
-                dW = wgrad_rules(X, dY, r.in_rows, r.out_rows, r.prefix_host, rb.n_off, fl).view_as(W)
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                db = colsum(dY)
-            return dW, db
-        dW, db = _on_leaf_stream(dY, leaves)
+        # (no bias_offsets: a coarse row is named once per child, so db is always the column sum)
+        dW, db = _param_grads(X, dY, r, rb.n_off, W.shape, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], 0, fl)
         return dX, dW, db, None, None, None, None
 
 
@@ -817,7 +780,7 @@ class DeconvolutionFunction(torch.autograd.Function):
         rb, r = ctx.rb, ctx.rb.rules
         dY = _feat(dY)
         fl = L.F_RELU_IN if ctx.relu_in else 0
-        dX = dW = db = None
+        dX = None
         if ctx.needs_input_grad[0]:      # dX[c] = sum_o dY[child[o][c]] . W[o]^T
             if USE_TILES and rb.tiles is not None:
                 dX = conv_rules(dY, rb.tiles, rb.n_coarse, W, None, X.shape[1], L.F_W_TRANSPOSED,
@@ -825,21 +788,10 @@ class DeconvolutionFunction(torch.autograd.Function):
             else:
                 dX = gemm_table(dY, rb.child, rb.n_off, rb.n_coarse, W, None, X.shape[1], L.F_W_TRANSPOSED,
                                 relu_mask=X if ctx.relu_in else None, n_rules=rb.n_fine)
-        def leaves():
-            dW = db = None
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
-                if want_b and rb.n_off <= 27:      # every fine (output) row occurs in exactly one of the rule lists
-                    dW, db = wgrad_bias_rules(X, dY, r.out_rows, r.in_rows, r.prefix_host, rb.n_off, (1 << rb.n_off) - 1, fl)
-                else:
-                    dW = wgrad_rules(X, dY, r.out_rows, r.in_rows, r.prefix_host, rb.n_off, fl)
-                    if want_b:
-                        db = colsum(dY)
-                dW = dW.view_as(W)
-            elif want_b:
-                db = colsum(dY)
-            return dW, db
-        dW, db = _on_leaf_stream(dY, leaves)
+        # the Convolution's rule list with its roles swapped; every fine (output) row occurs in exactly one of the rule lists, so
+        # all offsets together carry the bias pass (filters of up to 27 offsets)
+        dW, db = _param_grads(X, dY, r, rb.n_off, W.shape, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2],
+                              (1 << rb.n_off) - 1 if rb.n_off <= 27 else 0, fl, True)
         return dX, dW, db, None, None, None, None
 
 
@@ -862,22 +814,10 @@ class NetworkInNetworkFunction(torch.autograd.Function):
         X, W = ctx.saved_tensors
         dY = _feat(dY)
         n = X.shape[0]
-        dX = dW = db = None
+        dX = None
         if ctx.needs_input_grad[0]:
             dX = gemm_table(dY, None, 1, n, W, None, X.shape[1], L.F_W_TRANSPOSED)
-        def leaves():
-            dW = db = None
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
-                if want_b:
-                    dW, db = wgrad_bias_rules(X, dY, None, None, _identity_prefix(n), 1, 1)
-                else:
-                    dW = wgrad_rules(X, dY, None, None, _identity_prefix(n), 1)
-                dW = dW.view_as(W)
-            elif want_b:
-                db = colsum(dY)
-            return dW, db
-        dW, db = _on_leaf_stream(dY, leaves)
+        dW, db = _param_grads(X, dY, None, 1, W.shape, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], 1)
         return dX, dW, db
 
 
@@ -953,12 +893,9 @@ class JoinedNetworkInNetworkFunction(torch.autograd.Function):
             c = X.shape[1]
             if len(dXs) <= k:
                 dXs.append(gemm_table(dY, None, 1, n, W[r0:r0 + c], None, c, L.F_W_TRANSPOSED) if need[2 + k] else None)
-            if need[0]:
-                if k == 0 and ctx.has_bias and need[1]:
-                    dWk, db = wgrad_bias_rules(X, dY, None, None, _identity_prefix(n), 1, 1)
-                else:
-                    dWk = wgrad_rules(X, dY, None, None, _identity_prefix(n), 1)
-                dW[r0:r0 + c] = dWk.view(c, -1)
+            if need[0]:                 # (db in the first part's pass)
+                dW[r0:r0 + c], dbk = _param_grads(X, dY, None, 1, (c, -1), True, k == 0 and ctx.has_bias and need[1], 1)
+                db = dbk if k == 0 else db
             r0 += c
         if db is None and ctx.has_bias and need[1]:
             db = colsum(dY)

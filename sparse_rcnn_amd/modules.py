@@ -345,11 +345,10 @@ class Sequential(torch.nn.Sequential):
                 a, inner = list(m._modules.values())
                 if type(a) is Identity and type(inner) is Sequential and inner._is_plain_residual_branch(input):
                     c1, c2 = inner._modules["1"], inner._modules["3"]          # ReLU, SubM3, ReLU, SubM3
-                    fn = (F.ResidualBlockFunctionBF16 if input.features.dtype == torch.bfloat16
-                          else F.ResidualBlockFunction)                        # bf16-stored features: CastFeatures
                     w1, b1 = c1._wb(input.features.shape[1])
                     w2, b2 = c2._wb(w1.shape[-1])
-                    y = fn.apply(input.features, w1, b1, w2, b2, input.metadata, input.spatial_size)
+                    # (one node for fp32 and for bf16-stored features -- CastFeatures -- : it dispatches on the storage type)
+                    y = F.ResidualBlockFunction.apply(input.features, w1, b1, w2, b2, input.metadata, input.spatial_size)
                     input = _out(input, y)
                     i += 2
                     continue
@@ -406,7 +405,7 @@ FUSE_BLOCK = _os.environ.get("SCN_FUSE_BLOCK", "1") != "0"
 class CastFeatures(Module):
     """Storage dtype of the feature slab (not a reference module): `CastFeatures(torch.bfloat16)` in front of a run of
     residual units and `CastFeatures(torch.float32)` behind it puts those units on the bf16 storage path
-    (ResidualBlockFunctionBF16); every other layer takes fp32 features."""
+    (ResidualBlockFunction on bf16 features); every other layer takes fp32 features."""
 
     def __init__(self, dtype):
         super().__init__()

@@ -187,7 +187,7 @@ class SparseUNet(nn.Module):
         if self.identity_first and self.channels[0] != cin:
             raise ValueError("identity_first needs channels[0] == cin")
         # bf16_blocks: the residual units (28 of the 44 convolutions) keep their features, intermediates and gradients
-        # in bf16 (functional.ResidualBlockFunctionBF16); the strided / 1x1 layers between them stay fp32, with one
+        # in bf16 (functional.ResidualBlockFunction on bf16 features); the strided / 1x1 layers between them stay fp32, with one
         # cast on either side of a run of units.  Not the reference's arithmetic: BASELINE configs 3-5.
         # bf16_blocks="all": every layer after the first 1x1 convolution keeps its features in bf16 (the strided
         # convolutions, deconvolutions and 1x1 layers through the bf16 entry points of the fp32-arithmetic kernels),

@@ -15,21 +15,46 @@ QUIET = ("bytes", "counters", "version", "debug", "timing", "last_error", "step_
          "step_discard", "group_counts", "requirements", "describe", "launches")
 
 
-class _Counting:
-    """The library handle with every launching entry point counted by name."""
+_INTS = (L.i32, L.i64, C.c_uint32, C.c_uint64)
 
-    def __init__(self, lib):
+
+def describe_call(name, args):
+    """One call as text: every integer argument (by the argtypes of `_lib._SIGS`) as its value, every pointer argument as `p`,
+    or `0` where it is NULL, every floating-point argument as `f`."""
+    out = []
+    for a, t in zip(args, L._SIGS[name][1]):
+        if t in _INTS:
+            out.append(str(int(getattr(a, "value", a))))
+        elif t in (L.f32, C.c_double):
+            out.append("f")
+        else:
+            v = getattr(a, "value", a) if isinstance(a, (C.c_void_p, C.c_char_p)) else a
+            out.append("0" if v is None or (isinstance(v, int) and v == 0) or not bool(v) else "p")
+    return f"{name}({','.join(out)})"
+
+
+class _Counting:
+    """The library handle with every launching entry point counted by name.  log: a list that receives `describe_call` of every
+    counted call in order, and of the QUIET calls whose name starts with one of `log_also` (those stay uncounted)."""
+
+    def __init__(self, lib, log=None, log_also=()):
         self._lib, self.calls, self._made = lib, collections.Counter(), {}
+        self.log, self._log_also = log, tuple(log_also)
 
     def __getattr__(self, name):
         fn = self._made.get(name)
         if fn is None:
             raw = getattr(self._lib, name)
-            if any(q in name for q in QUIET):
+            quiet = any(q in name for q in QUIET)
+            logged = self.log is not None and (not quiet or name.startswith(self._log_also))
+            if quiet and not logged:
                 fn = raw
             else:
                 def fn(*a, _raw=raw, _name=name):
-                    self.calls[_name] += 1
+                    if not quiet:
+                        self.calls[_name] += 1
+                    if logged:
+                        self.log.append(describe_call(_name, a))
                     return _raw(*a)
             self._made[name] = fn
         return fn
