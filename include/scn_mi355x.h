@@ -85,7 +85,9 @@ extern "C" {
  *      additive within 5: + the executor op SCN_OP_ADD_RELU, no new entry point (178 entry points);
  *      additive within 5: + the executor ops SCN_OP_BN_STATS / _BN_FWD / _BN_BWD and the op flag SCN_XF_BN_TRAINING;
  *                           SCN_OP_WGRAD_SUBM with b < 0 is scn_wgrad_rules(_bf16); no new entry point (178 entry points);
- *      additive within 5: + scn_conv_tiles_bf16_plan_describe (179 entry points) */
+ *      additive within 5: + scn_conv_tiles_bf16_plan_describe (179 entry points);
+ *      additive within 5: + the switches SCN_WGRAD_STEP_OVERLAP and SCN_EXEC_HOLD_LEAVES, no new entry point (179 entry
+ *      points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -511,7 +513,15 @@ int scn_wgrad_defer_flush(scn_stream_t stream);
  * Until the flush has been queued the caller keeps everything the held launches read or write untouched: the operand slabs,
  * the rule lists, the gradient buffers and a scratch region of its OWN per pass.  The job tables of a flush (any number of
  * jobs; the argument form of a pass's flush carries six) go through a per-device ring of pinned host slots, each guarded by an
- * event, and one hipMemcpyAsync on s: these few buffers are the one thing the library allocates itself. */
+ * event, and one hipMemcpyAsync on s: these few buffers are the one thing the library allocates itself.
+ * The end of a step in stream order: a flush that holds both grid variants forks -- the table copy runs ahead on a
+ * non-blocking side stream the library owns (one per device, created at the first such flush), then k_wgrad_group<4>, the jobs
+ * that launch on their own and the held column sums run there behind an event of s, k_wgrad_group<2> runs on s, and s waits
+ * for the side stream before the sum launch; HIP events only, no kernel waits for another.  With one variant nothing forks;
+ * the developer switch SCN_WGRAD_STEP_OVERLAP=0 keeps everything on s.  Same arguments per job either way: same bits.
+ * Held column sums: inside a pass that scn_exec_run runs under a scope that holds, an SCN_OP_COLSUM (fp32) after which the
+ * pass has only weight gradients is recorded like them and launched by the flush -- it leaves the backward-data chain; its
+ * partial sums stay in the shared region of the pass's own scratch.  SCN_EXEC_HOLD_LEAVES=0: in place. */
 int scn_wgrad_step_begin(void);
 int scn_wgrad_step_hold(int on);
 int scn_wgrad_step_flush(scn_stream_t stream);

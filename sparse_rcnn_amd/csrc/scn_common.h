@@ -50,7 +50,7 @@ enum Switch {
     SW_TS_SPLIT, SW_TS_SPLIT_MAX, SW_TS_NO_TAIL, SW_TS_W_HALF, SW_TS_W_BOTH, SW_TB_NB, SW_TB_KH, SW_TB_STREAM,
     SW_TB_NO_XORDER, SW_TS_STREAM, SW_TSS_NW, SW_EXEC_DEFER_SUMS, SW_PYRAMID_V1, SW_PYRAMID_ONE_STREAM, SW_WD_NO_T3,
     SW_WGRAD_BF16_MFMA, SW_WGRAD_SPLITS, SW_WD_NO_EVEC, SW_PYRAMID_NO_BRICKS, SW_CU_BUDGET, SW_EXP_A, SW_EXP_B, SW_TS_NO_CHAIN, SW_TS_PROG, SW_TB_NO_BINS,
-    SW_EXEC_GROUP_WGRAD, SW_EXEC_GROUP_STEP, SW_COUNT
+    SW_EXEC_GROUP_WGRAD, SW_EXEC_GROUP_STEP, SW_WGRAD_STEP_OVERLAP, SW_EXEC_HOLD_LEAVES, SW_COUNT
 };
 struct SwitchVal { bool set = false; long long i = 0; double f = 0.0; };
 SwitchVal sw(Switch s);
@@ -71,6 +71,11 @@ struct DeviceOnce {
 // Between scn_wgrad_defer_begin and _flush on the calling thread: record the fp32 weight-gradient unit launches too, and run
 // them as grouped launches at the flush (scn_wgrad.hip, k_wgrad_group).  Internal to scn_exec_run_streams.
 int wgrad_defer_group(bool on);
+// Under a step scope that holds on the calling thread (scn_wgrad_step_hold; SCN_EXEC_HOLD_LEAVES=0: never): a column sum of the
+// pass can be recorded instead of launched; scn_wgrad_step_flush runs it with the step's other leaves, beside its grids.  The
+// caller vouches that dY, db and scratch stay untouched until then.  Internal to scn_exec_run_streams.
+bool wgrad_step_holding();
+int wgrad_step_hold_colsum(const float* dY, int64_t n, int c, float* db, void* scratch);
 
 inline hipStream_t S(scn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 

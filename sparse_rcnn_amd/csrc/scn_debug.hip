@@ -19,7 +19,7 @@ Entry g_sw[SW_COUNT] = {
     {"SCN_WGRAD_SPLITS", {}},    {"SCN_WD_NO_EVEC", {}},    {"SCN_PYRAMID_NO_BRICKS", {}},            {"SCN_CU_BUDGET", {}},
     {"SCN_EXP_A", {}},           {"SCN_EXP_B", {}},         {"SCN_TS_NO_CHAIN", {}},
     {"SCN_TS_PROG", {}},         {"SCN_TB_NO_BINS", {}},    {"SCN_EXEC_GROUP_WGRAD", {}},
-    {"SCN_EXEC_GROUP_STEP", {}},
+    {"SCN_EXEC_GROUP_STEP", {}}, {"SCN_WGRAD_STEP_OVERLAP", {}}, {"SCN_EXEC_HOLD_LEAVES", {}},
 };
 std::once_flag g_once;
 std::mutex g_mu;

@@ -363,6 +363,15 @@ bool overwritten_later(const scn_exec_op* ops, int n_ops, int i, void* const* bu
     }
     return false;
 }
+
+// A column sum whose launch moves to the step's flush keeps its partial sums in the pass's shared scratch region until then:
+// true when every op after it is a weight gradient with a region of its own (no later op of the pass touches the shared region).
+bool holdable_colsum(const scn_exec_op* ops, int n_ops, int i, const std::vector<int64_t>& own) {
+    if (own.empty()) return false;
+    for (int j = i + 1; j < n_ops; ++j)
+        if (!is_wgrad(ops[j].op) || own[j] == 0) return false;
+    return true;
+}
 }  // namespace
 
 extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn_exec_level* levels, int n_levels,
@@ -437,6 +446,15 @@ extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn
                 r.info[6] = child ? L.n : (L.prefix_host ? L.prefix_host[27] - L.prefix_host[0] : 0);
                 g_timing.recs.push_back(r);
             }
+        } else if (ops[i].op == SCN_OP_COLSUM && group && !bf(ops[i]) && holdable_colsum(ops, n_ops, i, own) &&
+                   scn::wgrad_step_holding() && !overwritten_later(ops, n_ops, i, bufs)) {
+            // a step scope holds this pass: the column sum is a leaf like the weight gradients -- it reads a slab the scope keeps
+            // alive, nobody reads its result before the optimizer -- so it leaves the backward-data chain and runs at the step's
+            // flush.  Its partial sums stay in the pass's shared region, which nothing after it touches (holdable_colsum) and which
+            // is the pass's own allocation under a scope that holds (include/scn_mi355x.h, scn_wgrad_step_hold)
+            const scn_exec_op& o = ops[i];
+            SCN_REQUIRE(o.level >= 0 && o.level < n_levels);
+            rc = scn::wgrad_step_hold_colsum(B<float>(c, o.x), rows_of(o, levels[o.level]), o.cin, G<float>(c, o.b), scratch);
         } else if (group && is_wgrad(ops[i].op) && overwritten_later(ops, n_ops, i, bufs)) {
             (void)scn::wgrad_defer_group(false);
             rc = run_op(c, ops[i], own[i] ? (char*)scratch + own[i] : nullptr);

@@ -821,11 +821,13 @@ thread_local DeferState g_defer;
 
 // Step scope (scn_wgrad_step_begin / _hold / _flush): above the pass scope, per calling thread.  While it holds, the flush of
 // a pass launches nothing: its recorded unit launches and sums move here, and scn_wgrad_step_flush runs the whole step's.
+struct ColsumLeaf { const float* dY; int64_t n; int c; float* db; void* scratch; };
 struct StepState {
     bool open = false, hold = false;
     std::vector<SumArgs> jobs; std::vector<int> blocks;
     std::vector<WdLaunch> units;
-    void clear() { jobs.clear(); blocks.clear(); units.clear(); }
+    std::vector<ColsumLeaf> colsums;             // scn::wgrad_step_hold_colsum: run by the flush, in recording order
+    void clear() { jobs.clear(); blocks.clear(); units.clear(); colsums.clear(); }
 };
 thread_local StepState g_step;
 
@@ -842,6 +844,17 @@ struct TableRing {
     std::mutex mu;
     Slot slot[N];
     int next = 0;
+    // The flush's side stream (flush_step forks the <4> grid onto it) and its events, created at the device's first flush and
+    // kept like the slots.
+    hipStream_t side = nullptr;
+    hipEvent_t copied = nullptr, fork = nullptr, join = nullptr;
+    int streams() {                                            // (under `mu`, on the ring's device)
+        if (!side) SCN_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        if (!copied) SCN_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        if (!fork) SCN_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+        if (!join) SCN_HIP(hipEventCreateWithFlags(&join, hipEventDisableTiming));
+        return SCN_OK;
+    }
     int release(Slot& s) {
         if (s.busy) SCN_HIP(hipEventSynchronize(s.ev));
         s.busy = false;
@@ -962,6 +975,9 @@ int flush_units(scn_stream_t stream) {
 // standalone launch, longest unit first across the whole step -- then ONE launch for all the sums.  EDGE and bf16-row forms,
 // and a variant with a single job, launch on their own.  The job tables travel through one slot of the table ring:
 // [GJob x n2][GJob x n4][SumArgs x ns][int x (n2 + 1)][int x (n4 + 1)][int x (ns + 1)], one copy.
+// With both grids present the flush forks: the copy runs ahead on the ring's side stream, then <4> and the jobs that launch on
+// their own run there beside <2> on the caller's, an event joins them ahead of the sums, and the slot's guard event goes
+// behind the join.
 int flush_step(scn_stream_t stream) {
     const std::vector<WdLaunch>& R = g_step.units;
     std::vector<int> m2, m4;
@@ -975,15 +991,27 @@ int flush_step(scn_stream_t stream) {
     std::vector<char> grouped(R.size(), 0);
     for (int k : m2) grouped[k] = 1;
     for (int k : m4) grouped[k] = 1;
-    for (size_t k = 0; k < R.size(); ++k)
-        if (!grouped[k]) {
-            const int rc = launch_direct(R[k], stream);
+    auto run_directs = [&](scn_stream_t s) {     // ... and the held column sums: the leaves of the step that are no grid job
+        for (size_t k = 0; k < R.size(); ++k)
+            if (!grouped[k]) {
+                const int rc = launch_direct(R[k], s);
+                if (rc != SCN_OK) return rc;
+            }
+        for (const ColsumLeaf& l : g_step.colsums) {
+            const int rc = scn_colsum(l.dY, l.n, l.c, l.db, l.scratch, s);
             if (rc != SCN_OK) return rc;
         }
+        return (int)SCN_OK;
+    };
     sort_members(R, m2);
     sort_members(R, m4);
     const size_t n2 = m2.size(), n4 = m4.size(), ns = g_step.jobs.size();
-    if (n2 + n4 + ns == 0) return SCN_OK;
+    if (n2 + n4 + ns == 0) return run_directs(stream);
+    // Both grids present: <4> (gather-bound, 4 waves per SIMD) and the jobs that launch on their own go to the side stream,
+    // <2> (MFMA-bound, 2 waves per SIMD) stays on the caller's; the sums wait for both.  Neither grid reads what the other
+    // writes, and each job keeps its arguments: same bits in either order.  SCN_WGRAD_STEP_OVERLAP=0: one stream.
+    const scn::SwitchVal ov = scn::sw(scn::SW_WGRAD_STEP_OVERLAP);
+    const bool fork = n2 && n4 && !(ov.set && ov.i == 0);
     auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
     const size_t o2 = 0, o4 = up(o2 + n2 * sizeof(GJob)), os = up(o4 + n4 * sizeof(GJob));
     const size_t b2 = up(os + ns * sizeof(SumArgs)), b4 = up(b2 + (n2 + 1) * sizeof(int));
@@ -995,7 +1023,12 @@ int flush_step(scn_stream_t stream) {
     std::lock_guard<std::mutex> ring_lock(ring.mu);
     TableRing::Slot* slot = nullptr;
     int rc = ring.take(bytes, &slot);
+    if (rc == SCN_OK && fork) rc = ring.streams();
     if (rc != SCN_OK) return rc;
+    if (!fork) {
+        rc = run_directs(stream);
+        if (rc != SCN_OK) return rc;
+    }
     char* h = slot->host;
     memset(h, 0, bytes);
     size_t lds2 = 0, lds4 = 0;
@@ -1018,16 +1051,43 @@ int flush_step(scn_stream_t stream) {
         memcpy(h + os + q * sizeof(SumArgs), &g_step.jobs[q], sizeof(SumArgs));
         ss[q + 1] = ss[q] + g_step.blocks[q];
     }
-    SCN_HIP(hipMemcpyAsync(slot->dev, h, bytes, hipMemcpyHostToDevice, S(stream)));
-    // from here on the slot is in use by the stream: the event goes behind whatever was queued, also after a failed launch
-    const char* d = slot->dev;
-    if (n2) {
-        GroupTable t{(const GJob*)(d + o2), (const int*)(d + b2), (int)n2};
-        rc = launch_group(2, t, (unsigned)s2[n2], lds2, stream);
+    // The table copy depends on nothing the caller's stream holds.  A flush that forks queues it on the side stream, where it
+    // runs as soon as the host has queued it -- the host is ahead of the GPU -- so the caller's stream finds it done instead of
+    // idling for it between the step's last kernel and the grids; the side stream then waits for the caller's stream.
+    bool side_used = false, forked = false;
+    if (fork) {
+        SCN_HIP(hipMemcpyAsync(slot->dev, h, bytes, hipMemcpyHostToDevice, ring.side));
+        side_used = true;
+        if (hipEventRecord(ring.copied, ring.side) != hipSuccess || hipStreamWaitEvent(S(stream), ring.copied, 0) != hipSuccess ||
+            hipEventRecord(ring.fork, S(stream)) != hipSuccess || hipStreamWaitEvent(ring.side, ring.fork, 0) != hipSuccess)
+            rc = scn::fail(SCN_EHIP, "%sthe step flush could not fork its side stream", "");
+        else forked = true;
+    } else {
+        SCN_HIP(hipMemcpyAsync(slot->dev, h, bytes, hipMemcpyHostToDevice, S(stream)));
     }
-    if (rc == SCN_OK && n4) {
+    // from here on the slot is in use by the stream(s): the event goes behind whatever was queued, also after a failed launch
+    const char* d = slot->dev;
+    const scn_stream_t s4s = forked ? (scn_stream_t)ring.side : stream;
+    auto grid2 = [&]() {
+        GroupTable t{(const GJob*)(d + o2), (const int*)(d + b2), (int)n2};
+        return launch_group(2, t, (unsigned)s2[n2], lds2, stream);
+    };
+    auto grid4 = [&]() {
         GroupTable t{(const GJob*)(d + o4), (const int*)(d + b4), (int)n4};
-        rc = launch_group(4, t, (unsigned)s4[n4], lds4, stream);
+        return launch_group(4, t, (unsigned)s4[n4], lds4, s4s);
+    };
+    if (forked) {
+        if (rc == SCN_OK) rc = grid4();
+        if (rc == SCN_OK) rc = run_directs(s4s);
+        if (rc == SCN_OK) rc = grid2();
+    } else {
+        if (rc == SCN_OK && n2) rc = grid2();                   // (a fork that failed has set rc: nothing launches)
+        if (rc == SCN_OK && n4) rc = grid4();
+    }
+    // the join is queued whatever happened above: nothing may stay on the side stream that the caller's stream does not wait for
+    if (side_used && (hipEventRecord(ring.join, ring.side) != hipSuccess || hipStreamWaitEvent(S(stream), ring.join, 0) != hipSuccess)) {
+        (void)hipStreamSynchronize(ring.side);
+        if (rc == SCN_OK) rc = scn::fail(SCN_EHIP, "%sthe step flush could not join its side stream", "");
     }
     if (rc == SCN_OK && ns) {
         g_counts[3].fetch_add(1, std::memory_order_relaxed);
@@ -1043,6 +1103,15 @@ int flush_step(scn_stream_t stream) {
 }  // namespace
 
 namespace scn {
+bool wgrad_step_holding() {
+    const SwitchVal v = sw(SW_EXEC_HOLD_LEAVES);
+    return g_step.open && g_step.hold && !(v.set && v.i == 0);
+}
+int wgrad_step_hold_colsum(const float* dY, int64_t n, int c, float* db, void* scratch) {
+    SCN_REQUIRE(g_step.open && g_step.hold && n >= 0 && c >= 1 && db && scratch && (n == 0 || dY));
+    g_step.colsums.push_back(ColsumLeaf{dY, n, c, db, scratch});
+    return SCN_OK;
+}
 int wgrad_defer_group(bool on) {
     if (on && !g_defer.on) return SCN_EINVAL;
     g_defer.group = on;
