@@ -87,7 +87,9 @@ extern "C" {
  *                           SCN_OP_WGRAD_SUBM with b < 0 is scn_wgrad_rules(_bf16); no new entry point (178 entry points);
  *      additive within 5: + scn_conv_tiles_bf16_plan_describe (179 entry points);
  *      additive within 5: + the switches SCN_WGRAD_STEP_OVERLAP and SCN_EXEC_HOLD_LEAVES, no new entry point (179 entry
- *      points) */
+ *      points);
+ *      additive within 5: + the executor ops SCN_OP_GRAD_NORM / SCN_OP_GRAD_SCALE (global-norm gradient clipping), no new entry
+ *                           point (179 entry points) */
 #define SCN_ABI_VERSION 5
 
 /* flags for the gather-GEMM entry points */
@@ -812,8 +814,24 @@ enum {
      * pass's shared region (scn_exec_requirements counts it). */
     SCN_OP_BN_STATS = 17,    /* scn_bn_stats: x -> bufs[y] = mean[cin] | biased var[cin]                                       */
     SCN_OP_BN_FWD = 18,      /* scn_bn_fwd: x -> y                                                                             */
-    SCN_OP_BN_BWD = 19       /* scn_bn_bwd: x, m = dY -> y = dX, grads[b] = dgamma[cin] | dbeta[cin]; SCN_XF_BN_TRAINING: the
+    SCN_OP_BN_BWD = 19,      /* scn_bn_bwd: x, m = dY -> y = dX, grads[b] = dgamma[cin] | dbeta[cin]; SCN_XF_BN_TRAINING: the
                               * statistics were the batch's (the gradient passes through them), else constants                 */
+    /* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2; scn_clip.hip) over a list of fp32 segments out of
+     * the grads[] table; neither op is an entry point of its own or takes SCN_XF_BF16.  T = levels[level].n segments; segment i is
+     * grads[w + i] with prefix_host[i + 1] - prefix_host[i] elements (prefix_host: the level's host int64 pointer, here [T + 1]; one
+     * flat buffer is T = 1); empty segments are skipped, segments must not overlap.  Checked before anything is launched
+     * (SCN_EINVAL, the message names the op): a negative count, a NULL pointer with a positive count, a pointer that is not 4-byte
+     * aligned, a record buffer id that is negative or names no buffer.  The table travels in the kernel arguments, at most 80
+     * segments per launch; 16-byte accesses after a scalar head of at most 3 elements. */
+    SCN_OP_GRAD_NORM = 20,   /* bufs[y] = 4 floats {total_norm, clip_coef, nonfinite, 0}.  S = the sum of squares of every element,
+                              * accumulated in double in a fixed order (one partial sum per 4096-element chunk in the pass's shared
+                              * scratch -- 8 bytes per chunk, scn_exec_requirements counts them -- then one launch of one workgroup
+                              * adds them; no atomics).  total_norm = (float)(sqrt(S) * |gs|), gs = the fp32 whose bits are c1 (the
+                              * scale the update applies to the gradient); clip_coef in fp32 as torch computes it: c = max_norm /
+                              * (total_norm + 1e-6f), c > 1 ? 1 : c (a NaN stays), max_norm = the fp32 whose bits are aux (+inf:
+                              * the coefficient is 1); nonfinite = 1 when S is not finite, else 0                              */
+    SCN_OP_GRAD_SCALE = 21   /* every element of every segment: g = g * ((float*)bufs[x1])[1], in place, one fp32 multiply; a
+                              * workgroup that reads the coefficient 1.0f returns without touching the gradient (same bits)     */
 };
 #define SCN_XF_BF16 (1 << 16)        /* op flag: the op's feature slabs are bf16-stored                                      */
 #define SCN_XF_BN_TRAINING (1 << 18) /* op flag (BN_BWD; BN_FWD carries it too): batch statistics, see SCN_OP_BN_BWD                    */

@@ -93,6 +93,14 @@ inline int ew_grid(int64_t work_items, int block) {
 int add_relu(const float* X, const float* X1, int64_t count, float* Y, scn_stream_t stream);
 int add_relu_bf16(const uint16_t* X, const uint16_t* X1, int64_t count, uint16_t* Y, scn_stream_t stream);
 
+// Global-norm gradient clipping over T fp32 segments (scn_clip.hip): the step executor's SCN_OP_GRAD_NORM / SCN_OP_GRAD_SCALE.
+// Segment i: grads[i], prefix[i + 1] - prefix[i] elements (prefix: host int64 [T + 1]).  grad_norm_blocks: the workgroups whose
+// partial sums (one double each) the norm keeps in `scratch`, -1 for a negative count.
+int64_t grad_norm_blocks(const int64_t* prefix, int64_t T);
+int grad_norm(void* const* grads, const int64_t* prefix, int64_t T, float grad_scale, float max_norm, float* record,
+              void* scratch, int64_t scratch_bytes, scn_stream_t stream);
+int grad_scale(void* const* grads, const int64_t* prefix, int64_t T, const float* record, scn_stream_t stream);
+
 }  // namespace scn
 
 // ---- device-side key packing / hashing (shared by index kernels) ----

@@ -32,6 +32,7 @@ struct Ctx {
     void* scratch;
     int32_t* arrival;
     scn_stream_t stream;
+    int64_t scratch_bytes = 0;       // of `scratch` (the ops that check their own need: SCN_OP_GRAD_NORM)
 };
 
 inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
@@ -228,6 +229,23 @@ int run_op(const Ctx& c0, const scn_exec_op& o, void* own_scratch = nullptr) {
                           P<float>(c, o.w + 1), leak, (o.flags & SCN_XF_BN_TRAINING) ? 1 : 0, B<float>(c, o.y), dgamma,
                           dgamma + o.cin, c.scratch, st);
     }
+    // Global-norm gradient clipping (scn_clip.hip) over the L.n fp32 segments grads[w], grads[w + 1], ...; segment i has
+    // prefix_host[i + 1] - prefix_host[i] elements.  The whole table is checked before anything is launched.
+    case SCN_OP_GRAD_NORM:
+    case SCN_OP_GRAD_SCALE: {
+        const bool norm = o.op == SCN_OP_GRAD_NORM;
+        const char* name = norm ? "SCN_OP_GRAD_NORM" : "SCN_OP_GRAD_SCALE";
+        const int rec = norm ? o.y : o.x1;
+        if (rec < 0 || c.bufs[rec] == nullptr)
+            return scn::fail(SCN_EINVAL, "%s: the record buffer id %lld (y of the norm, x1 of the scale) is out of range", name, rec);
+        if (h || L.n < 0 || o.w < 0 || (L.n > 0 && c.grads == nullptr))
+            return scn::fail(SCN_EINVAL, "%s: fp32 segments grads[w ...] with w >= 0 required (%lld segments)", name, L.n);
+        void* const* g = c.grads ? c.grads + o.w : nullptr;
+        if (norm)
+            return scn::grad_norm(g, L.prefix_host, L.n, bits_f32(o.c1), bits_f32(o.aux), B<float>(c, rec), c.scratch,
+                                  c.scratch_bytes, st);
+        return scn::grad_scale(g, L.prefix_host, L.n, B<float>(c, rec), st);
+    }
     default:
         return scn::fail(SCN_EINVAL, "scn_exec_run: unknown op %s%lld", "", o.op);
     }
@@ -267,6 +285,12 @@ int pass_needs(const scn_exec_op* ops, int n_ops, const scn_exec_level* levels, 
         case SCN_OP_COLSUM: s = (int64_t)SCN_COLSUM_BLOCKS * o.cin * (int64_t)sizeof(float); break;
         case SCN_OP_BN_STATS:
         case SCN_OP_BN_BWD: s = o.cin >= 1 ? scn_bn_scratch_bytes(o.cin) : -1; break;
+        case SCN_OP_GRAD_NORM: {     // one double per workgroup of the partial-sum launches
+            const int64_t blocks = scn::grad_norm_blocks(L.prefix_host, L.n);
+            s = blocks < 0 ? -1 : blocks * (int64_t)sizeof(double);
+            break;
+        }
+        case SCN_OP_GRAD_SCALE: s = scn::grad_norm_blocks(L.prefix_host, L.n) < 0 ? -1 : 0; break;
         default: {
             const int64_t w = wgrad_scratch_of(o, L);
             if (w < 0) return scn::fail(SCN_EINVAL, "scn_exec: op %s%lld has bad arguments", "", i);
@@ -413,8 +437,8 @@ extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn
     // discards the scope (scn_wgrad_step_discard).
     const scn::SwitchVal group_sw = scn::sw(scn::SW_EXEC_GROUP_WGRAD);
     const bool group = defer && !(group_sw.set && group_sw.i == 0) && !g_timing.on;
-    Ctx c{levels, n_levels, bufs, params, grads, scratch, arrival, stream};
-    Ctx cs{levels, n_levels, bufs, params, grads, side_scratch, arrival, side_stream};
+    Ctx c{levels, n_levels, bufs, params, grads, scratch, arrival, stream, scratch_bytes};
+    Ctx cs{levels, n_levels, bufs, params, grads, side_scratch, arrival, side_stream, side_scratch_bytes};
     if (defer) SCN_REQUIRE(scn_wgrad_defer_begin() == SCN_OK);
     if (group) SCN_REQUIRE(scn::wgrad_defer_group(true) == SCN_OK);
     bool side_used = false;
@@ -443,7 +467,10 @@ extern "C" int scn_exec_run_streams(const scn_exec_op* ops, int n_ops, const scn
                 // op, bf16, cin, cout, rows in, rows out, rules (a child table holds every fine row once)
                 r.info[0] = o.op; r.info[1] = bf(o) ? 1 : 0; r.info[2] = o.cin; r.info[3] = o.cout;
                 r.info[4] = L.n; r.info[5] = child ? L.n_coarse : L.n;
-                r.info[6] = child ? L.n : (L.prefix_host ? L.prefix_host[27] - L.prefix_host[0] : 0);
+                // (the clip ops' prefix_host is the caller's [L.n + 1] count prefix, not a 28-entry rule prefix: their elements)
+                const bool clip = o.op == SCN_OP_GRAD_NORM || o.op == SCN_OP_GRAD_SCALE;
+                if (clip) r.info[6] = (rc == SCN_OK && L.prefix_host && L.n >= 0) ? L.prefix_host[L.n] - L.prefix_host[0] : 0;
+                else r.info[6] = child ? L.n : (L.prefix_host ? L.prefix_host[27] - L.prefix_host[0] : 0);
                 g_timing.recs.push_back(r);
             }
         } else if (ops[i].op == SCN_OP_COLSUM && group && !bf(ops[i]) && holdable_colsum(ops, n_ops, i, own) &&

@@ -60,6 +60,9 @@ class FlatParams:
         self.grad_scale = 1.0         # mean gradient = flat_grad * grad_scale (valid after all_reduce_mean)
         self.flat_grad_valid = False  # False after a step that never packed the flat buffer (step_single_rank fast path)
         self.sync = True              # False inside `accumulate()`: a backward only accumulates into `.grad`
+        self.max_grad_norm = None     # a bound: every update below clips the gradient it reads to this L2 norm first (clip_grad_norm)
+        self.clip_record = None       # this object's device record (total_norm, clip_coef, nonfinite, 0), allocated at its first clip
+        self._clip_need = {}          # segment counts -> scratch bytes (scn_exec_requirements, asked once per layout)
         off = 0
         for p in self.params:
             n = p.numel()
@@ -277,19 +280,61 @@ class FlatParams:
             off += p.numel()
         return out
 
+    def clip_grad_norm(self, max_norm: float, packed: bool | None = None):
+        """Clip the gradient the next update reads to the L2 norm `max_norm`, on the device and without a host wait
+        (torch.nn.utils.clip_grad_norm_'s arithmetic; executor.clip_segments: SCN_OP_GRAD_NORM + SCN_OP_GRAD_SCALE in one call).
+        Between the reduction and the update.  Packed path (`flat_grad_valid`): ONE segment, the whole flat_grad, and the norm
+        is that of the MEAN gradient over ranks and micro-batches (|grad_scale| x the norm of the buffer) -- every rank computes
+        it from the same bytes, so all ranks scale by the same coefficient without a collective.  One-rank fast path: the
+        segments are the `.grad` tensors that exist (adopted in-place views included) where autograd left them, no packing; a
+        parameter without a gradient stays without one.  The update kernels still apply grad_scale themselves.
+        -> `.clip_record`, this object's own device record (total_norm, clip_coef, nonfinite, 0): no other object's clip and
+        no `optim.clip_grad_norm_` call writes it."""
+        from . import executor as EX
+        from .optim import clip_buffers
+        if not self.flat.is_cuda:
+            raise ValueError("FlatParams.clip_grad_norm: the clip runs on the MI355X only (no CPU fallback)")
+        if self.flat_grad_valid if packed is None else packed:    # (sgd_step / adam_step read flat_grad: packed=True)
+            ptrs, counts, gs = [self.flat_grad.data_ptr()], [self.flat_grad.numel()], self.grad_scale
+        else:
+            grads = [p.grad for p in self.params if p.grad is not None]
+            if not all(g.is_contiguous() and g.dtype == torch.float32 for g in grads):
+                raise ValueError("FlatParams.clip_grad_norm: gradients must be contiguous fp32")
+            ptrs, counts, gs = [g.data_ptr() for g in grads], [g.numel() for g in grads], 1.0
+        # the record is this object's own (another step's or a caller's clip on the same stream must not show through
+        # `.clip_record`); only the scratch, dead once the call's kernels have run, is the one shared per device and stream
+        if self.clip_record is None:
+            self.clip_record = torch.zeros(4, dtype=torch.float32, device=self.flat.device)
+        key = tuple(counts)
+        need = self._clip_need.get(key)
+        if need is None:
+            need = self._clip_need[key] = EX.clip_scratch_bytes(counts)
+        with torch.cuda.device(self.flat.device):
+            EX.clip_segments(ptrs, counts, float(max_norm), gs, self.clip_record, clip_buffers(self.flat.device, need)[1])
+        return self.clip_record
+
     def sgd_step(self, lr: float):
+        if self.max_grad_norm is not None:
+            self.clip_grad_norm(self.max_grad_norm, packed=True)
         self.flat.add_(self.flat_grad, alpha=-lr * self.grad_scale)
+
+    def single_rank_step_packs(self):
+        """Whether step_single_rank / adam_step_single_rank go through all_reduce_mean and the packed flat gradient (buckets, more
+        than one rank, a rank weight, SCN_STEP_PACKED) or take the one-rank fast path over the `.grad` tensors."""
+        return bool(self.buckets or os.environ.get("SCN_STEP_PACKED") or _dist_on(2) or self.rank_weight != 1.0)
 
     def step_single_rank(self, lr: float):
         """all_reduce_mean + sgd_step for ONE rank without a process group: there is nothing to reduce, so the gradients
         need not be packed into the flat bucket first (a 50 MB copy at 32->256 channels) -- the update reads them where
         autograd left them, one multi-tensor launch.  Same arithmetic per element as sgd_step.  The flat gradient buffer
         is NOT filled on this path (`flat_grad_valid` False; `mean_grad()` raises)."""
-        if self.buckets or os.environ.get("SCN_STEP_PACKED") or _dist_on(2) or self.rank_weight != 1.0:
+        if self.single_rank_step_packs():
             self.all_reduce_mean()
             self.sgd_step(lr)
             return
         self.flat_grad_valid = False
+        if self.max_grad_norm is not None:
+            self.clip_grad_norm(self.max_grad_norm)
         if self._datas[0].data_ptr() != self.params[0].data_ptr() or self._datas[-1].data_ptr() != self.params[-1].data_ptr():
             self._datas = [p.data for p in self.params]        # (a parameter was re-pointed after construction: module.to(...))
         grads = [p.grad for p in self.params]
@@ -308,6 +353,8 @@ class FlatParams:
         gather_grads fills them -- so all step counts and moments advance together and the ranks stay in lockstep.  (The
         one-rank fast path of adam_step_single_rank skips a None gradient instead, as torch.optim.Adam does: the two differ
         only for a parameter that got no gradient, e.g. mask-branch weights after an empty ROI crop.)"""
+        if self.max_grad_norm is not None:
+            self.clip_grad_norm(self.max_grad_norm, packed=True)
         adam.step_flat(self)
 
     def adam_step_single_rank(self, adam):
@@ -315,11 +362,13 @@ class FlatParams:
         gradients where autograd left them (one segment per parameter, no packing; `flat_grad_valid` False).  On the fast
         path a parameter whose `.grad` is None is skipped and its step count does not advance, as in torch.optim.Adam;
         the packed path (adam_step) advances every parameter instead."""
-        if self.buckets or os.environ.get("SCN_STEP_PACKED") or _dist_on(2) or self.rank_weight != 1.0:
+        if self.single_rank_step_packs():
             self.all_reduce_mean()
             self.adam_step(adam)
             return
         self.flat_grad_valid = False
+        if self.max_grad_norm is not None:
+            self.clip_grad_norm(self.max_grad_norm)
         if self._datas[0].data_ptr() != self.params[0].data_ptr() or self._datas[-1].data_ptr() != self.params[-1].data_ptr():
             self._datas = [p.data for p in self.params]
         adam.step_params(self._datas, [p.grad for p in self.params])

@@ -64,6 +64,7 @@ OP_GEMM_IDENT, OP_CONV_SUBM, OP_CONV_CHILD, OP_RULES_CHILD, OP_ROWS2 = 1, 2, 3, 
 OP_WGRAD_SUBM, OP_WGRAD2_SUBM, OP_WGRAD_DOWN, OP_WGRAD_UP, OP_WGRAD_IDENT, OP_COLSUM, OP_ADD, OP_CAST = 6, 7, 8, 9, 10, 11, 12, 13
 OP_RELU, OP_RELU_BWD, OP_ADD_RELU = 14, 15, 16
 OP_BN_STATS, OP_BN_FWD, OP_BN_BWD = 17, 18, 19
+OP_GRAD_NORM, OP_GRAD_SCALE = 20, 21
 XF_BF16, XF_COARSE_ROWS, XF_BN_TRAINING = 1 << 16, 1 << 17, 1 << 18
 VEC = -1                                # `level` of a buffer that is one row whatever the level sizes are (batch mean | variance)
 BACK = L.F_W_TRANSPOSED | L.F_OFF_REVERSE
@@ -733,6 +734,54 @@ def run_add_relu(x_ptr, x1_ptr, y_ptr, rows, c, bf16, scratch):
     ops = (ExecOp * 1)(ExecOp(OP_ADD_RELU, XF_BF16 if bf16 else 0, 0, int(c), 0, 0, 2, -1, -1, 1, -1, 0, -1, -1, 0, 0))
     table = (vp * 3)(x_ptr, x1_ptr, y_ptr)
     L.check(lib.scn_exec_run(ops, 1, levels, 1, table, None, None, scratch.data_ptr(), scratch.numel(), None, L.stream()))
+
+
+CLIP_MAX_SEGS = 80                      # segments per launch of the clip kernels (include/scn_mi355x.h: SCN_OP_GRAD_NORM)
+
+
+def clip_plan(counts, max_norm, grad_scale):
+    """The pseudo-level and the two-op plan of a global-norm clip over segments of `counts` elements: SCN_OP_GRAD_NORM writes
+    the record (buffer 0), SCN_OP_GRAD_SCALE reads its coefficient.  -> (ops, levels, prefix): `prefix` is the host int64 array
+    the level points to, the caller keeps it alive until the call has returned."""
+    counts = [int(n) for n in counts]
+    prefix = (i64 * (len(counts) + 1))()
+    for i, n in enumerate(counts):
+        prefix[i + 1] = prefix[i] + n
+    levels = (ExecLevel * 1)()
+    levels[0].n = len(counts)
+    levels[0].prefix_host = _addr(prefix)
+    ops = (ExecOp * 2)(
+        ExecOp(OP_GRAD_NORM, 0, 0, 0, 0, -1, 0, -1, -1, -1, -1, _f32_bits(grad_scale), 0, -1, _f32_bits(max_norm), 0),
+        ExecOp(OP_GRAD_SCALE, 0, 0, 0, 0, -1, -1, -1, -1, 0, -1, 0, 0, -1, 0, 0))
+    return ops, levels, prefix
+
+
+def clip_scratch_bytes(counts):
+    """Scratch of clip_segments, as the library counts it: scn_exec_requirements on the plan (8 bytes per workgroup of the
+    partial-sum launches, never less than the executor's 256).  No GPU needed."""
+    ops, levels, prefix = clip_plan(counts, 1.0, 1.0)
+    scratch, arrival = C.c_int64(0), C.c_int64(0)
+    L.check(L.load().scn_exec_requirements(ops, 2, levels, 1, C.byref(scratch), C.byref(arrival)))
+    return scratch.value
+
+
+def clip_launches(counts):
+    """Kernel launches of one clip_segments call: the partial sums and the scale take one launch per CLIP_MAX_SEGS non-empty
+    segments each, the record one."""
+    return 2 * -(-sum(1 for n in counts if n) // CLIP_MAX_SEGS) + 1
+
+
+def clip_segments(grad_ptrs, counts, max_norm, grad_scale, record, scratch):
+    """torch.nn.utils.clip_grad_norm_ (norm_type 2) over fp32 segments as ONE scn_exec_run call on torch's current stream:
+    record[0:4] = (|grad_scale| x the L2 norm of all elements, min(1, max_norm / (that + 1e-6)), 1.0 if the sum of squares is not
+    finite, 0), then every element is multiplied by record[1] unless it is 1.  Raw addresses and element counts; record: a device
+    fp32 tensor of at least 4 elements; scratch: a device uint8 tensor of at least clip_scratch_bytes(counts).  No host wait."""
+    ops, levels, prefix = clip_plan(counts, max_norm, grad_scale)
+    n = len(counts)
+    grads = (vp * max(n, 1))(*[int(p) for p in grad_ptrs])
+    table = (vp * 1)(record.data_ptr())
+    L.check(L.lib().scn_exec_run(ops, 2, levels, 1, table, None, grads, scratch.data_ptr(), scratch.numel() * scratch.element_size(),
+                                 None, L.stream()))
 
 
 def _lean_layout(stage, ns):

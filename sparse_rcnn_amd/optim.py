@@ -64,6 +64,56 @@ def _check_param(p):
         raise ValueError("sparse_rcnn_amd.optim.Adam: parameters must be contiguous")
 
 
+_clip_cache = {}                         # (device index, stream handle) -> [record, scratch]
+
+
+def clip_buffers(device, scratch_bytes):
+    """The record (4 floats) and the scratch of a clip on `device` and torch's current stream there, kept per (device, stream):
+    the scratch is allocated again only when a longer table asks for more."""
+    with torch.cuda.device(device):
+        key = (torch.cuda.current_device(), L.stream())
+        hit = _clip_cache.get(key)
+        if hit is None:
+            hit = _clip_cache[key] = [torch.zeros(4, dtype=torch.float32, device=device), None]
+        if hit[1] is None or hit[1].numel() < scratch_bytes:
+            hit[1] = torch.empty(max(int(scratch_bytes), 256), dtype=torch.uint8, device=device)
+    return hit[0], hit[1]
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ on the library's two clip kernels (SCN_OP_GRAD_NORM + SCN_OP_GRAD_SCALE, one executor
+    call over the gradients where autograd left them): the L2 norm over every `.grad` that is not None, accumulated in double
+    in a fixed order, and `grad *= min(1, max_norm / (norm + 1e-6))` in place.  -> the total norm as a 0-dim device tensor, a
+    view of the call's record (valid until the next clip on this device and stream); no host wait unless error_if_nonfinite.
+    `foreach` is accepted and ignored.  Gradients: fp32, contiguous, on the GPU (ValueError otherwise); L2 only."""
+    from . import executor as EX
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    if float(norm_type) != 2.0:
+        raise ValueError("sparse_rcnn_amd.optim.clip_grad_norm_: norm_type %r is not implemented, only the L2 norm "
+                         "(norm_type=2)" % (norm_type,))
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    for g in grads:
+        if g.device.type != "cuda":
+            raise ValueError("sparse_rcnn_amd.optim.clip_grad_norm_: gradient on %s -- the clip runs on the MI355X only (no CPU "
+                             "fallback); move the model to the GPU first" % g.device)
+        if g.is_sparse or g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
+            raise ValueError("sparse_rcnn_amd.optim.clip_grad_norm_: gradients must be contiguous fp32 on one device")
+    counts = [g.numel() for g in grads]
+    record, scratch = clip_buffers(dev, EX.clip_scratch_bytes(counts))
+    with torch.cuda.device(dev):
+        EX.clip_segments([g.data_ptr() for g in grads], counts, float(max_norm), 1.0, record, scratch)
+    if error_if_nonfinite and record[2].item() != 0.0:
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it "
+                           "cannot be clipped. To disable this error and scale the gradients by the non-finite norm anyway, "
+                           "set `error_if_nonfinite=False`")
+    return record[0]
+
+
 class _DeviceState:
     """The flat moments of the parameters of one device: slot i = params[i], moments at [off[i], off[i] + n[i])."""
 
@@ -247,11 +297,13 @@ class FlatAdam:
     """Adam state of a `dp.FlatParams` (one parameter group): flat moments `exp_avg` / `exp_avg_sq` aligned element for element
     with `FlatParams.flat`, and one step count per parameter.  Driven by `FlatParams.adam_step` (the packed / all-reduced
     gradient: segments over the flat buffers) and `FlatParams.adam_step_single_rank` (one rank: the gradients where autograd
-    left them, one segment per parameter)."""
+    left them, one segment per parameter).
+    Over a CPU buffer the state is laid out and the object constructs -- a step built to be inspected or described without a GPU,
+    as an SGD step can be -- and every update (`step_flat`, `step_params`) raises ValueError: there is no CPU fallback."""
 
     def __init__(self, fp, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False):
-        if not fp.flat.is_cuda or fp.flat.dtype != torch.float32:
-            raise ValueError("FlatAdam: fp32 parameters on the GPU only (no CPU fallback)")
+        if fp.flat.dtype != torch.float32:
+            raise ValueError("FlatAdam: fp32 parameters only (got %s)" % fp.flat.dtype)
         if not (0.0 <= lr and 0.0 <= eps and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and 0.0 <= weight_decay):
             raise ValueError("FlatAdam: invalid hyperparameters")
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
@@ -267,6 +319,11 @@ class FlatAdam:
         self.table["v"] = self.exp_avg_sq.data_ptr() + 4 * self.off
         self._p0 = None
 
+    @staticmethod
+    def _require_gpu(t):
+        if not t.is_cuda:
+            raise ValueError("FlatAdam: fp32 parameters on the GPU only (no CPU fallback)")
+
     def _consts(self, step):
         return constants(self.lr, self.betas[0], self.betas[1], self.weight_decay, self.decoupled_weight_decay, float(step))
 
@@ -280,6 +337,7 @@ class FlatAdam:
     def step_flat(self, fp):
         """Every parameter advances (the packed gradient holds zeros where no rank produced one): one segment per run of
         parameters with equal step counts over flat / flat_grad -- one segment while all counts agree."""
+        self._require_gpu(fp.flat)
         self.steps += 1.0
         cut = np.flatnonzero(np.diff(self.steps)) + 1
         starts = np.concatenate([[0], cut]).astype(np.int64)
@@ -296,6 +354,7 @@ class FlatAdam:
 
     def step_params(self, datas, grads):
         """Parameters whose gradient is None are skipped, their step counts stay (torch.optim.Adam's rule)."""
+        self._require_gpu(self.exp_avg)
         if self._p0 != datas[0].data_ptr():
             self.table["p"] = [d.data_ptr() for d in datas]
             self._p0 = datas[0].data_ptr()

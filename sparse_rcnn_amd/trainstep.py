@@ -224,8 +224,14 @@ class SceneStep:
                  class_loss=False, segmentation_loss=False, batches=None, step_group=True, dense_class=False,
                  upsample_heads=False, class_storage=None, simple_class=False, multitask_loss=False, loss_weights=None,
                  bottleneck_divisor=0, main_path_relu=False, relu_first=True, drop_input_relu=True, use_residuals=True,
-                 bn_stages=False, train=None, init_state=None):
-        """train (None: nothing changes -- every parameter is trained): a non-empty tuple of part names out of `PARTS`
+                 bn_stages=False, train=None, init_state=None, max_grad_norm=None):
+        """max_grad_norm (None: nothing changes -- nothing is built or launched): a positive finite bound on the L2 norm of the
+        gradient the update reads -- the mean over ranks and micro-batches -- clipped on the device once per optimizer step, after
+        the last micro-batch and the reduction, before Adam or SGD (FlatParams.clip_grad_norm: SCN_OP_GRAD_NORM +
+        SCN_OP_GRAD_SCALE, torch.nn.utils.clip_grad_norm_'s arithmetic with the sum of squares in double; no host wait).
+        `.grad_norm`: (total_norm, clip_coef, nonfinite) of the last step, read from the device when asked for.  Zero, negative,
+        NaN, inf, or a `train=` step whose trained parts have no parameters: ValueError.
+        train (None: nothing changes -- every parameter is trained): a non-empty tuple of part names out of `PARTS`
         ("backbone", "rpn", "class", "mask", "segmentation"); the parameters of every part NOT named are frozen
         (requires_grad False) before the flat buffer is built, so the flat buffer, the gradient buckets and the optimizer cover
         the named parts only and a frozen parameter never receives a `.grad` -- the reference's training in stages:
@@ -324,6 +330,7 @@ class SceneStep:
         (None: all of them; ref-crop-rpn has 256 per crop, which would put > 3000 boxes through the mask branch).
         optimizer: "sgd" (plain SGD on the flat buffer) or "adam" (the reference's optimizer, scannet_config/run.py:403-416,
         1449: the fused Adam launch of optim.FlatAdam with `betas`, `eps`, `weight_decay`; lr=None -> the reference's 4e-4).
+        On a CPU device either optimizer's step constructs (to be inspected and described) and refuses when it is stepped.
         batches_per_step: micro-batches whose gradients are accumulated before ONE all-reduce + update, each scaled by
         1 / batches_per_step -- the reference's `(loss / batches_per_step).backward()` ... `optimizer.step()`
         (ndsis/training/training.py:436,458-460; 2 or 6 with the mask head, scannet_config/run.py:377-396).  Micro-batch k
@@ -343,6 +350,12 @@ class SceneStep:
         if dtype not in ("f32", "bf16", "bf16-blocks"):
             raise ValueError("dtype: f32 | bf16 | bf16-blocks")
         self._check_train(train, requested, multitask_loss)
+        self._max_grad_norm = None               # (read through the `max_grad_norm` property)
+        if max_grad_norm is not None:
+            bound = float(max_grad_norm)
+            if not (bound > 0 and bound < float("inf")):
+                raise ValueError(f"max_grad_norm: a positive finite bound required (None: no clipping), got {max_grad_norm!r}")
+            self._max_grad_norm = bound
         if requested["segmentation"] and not self.n_boxes:
             raise ValueError("segmentation_loss=True needs boxes (n_boxes > 0)")
         # 2. the scenes, resident on the device
@@ -585,7 +598,11 @@ class SceneStep:
                 for p in self._part(name).parameters():
                     p.requires_grad_(False)
                     frozen_params.append(p)
+        if self.max_grad_norm is not None and not any(p.requires_grad for p in self.model.parameters()):
+            raise ValueError("max_grad_norm: the parts this step trains (" + ", ".join(self.trainable) + ") have no parameters, "
+                             "there is no gradient to clip")
         self.flat = FlatParams(self.model, n_buckets=n_buckets)
+        self.flat.max_grad_norm = self.max_grad_norm
         broadcast_params(self.flat)
         broadcast_tensors([p.data for p in frozen_params])      # (more than one rank: the frozen parameters are equal everywhere too)
 
@@ -1092,6 +1109,21 @@ class SceneStep:
         else:
             self.flat.step_single_rank(self.lr)  # = all_reduce_mean + sgd_step; one rank: no packing into the flat bucket
 
+    @property
+    def max_grad_norm(self):
+        """The bound the step clips its gradient to (None: no clipping), as given at construction."""
+        return self._max_grad_norm
+
+    @property
+    def grad_norm(self):
+        """(total_norm, clip_coef, nonfinite) of the last step's clip, read from the device record on access (the step's only host
+        wait for it); None without max_grad_norm or before the first step."""
+        rec = self.flat.clip_record
+        if self.max_grad_norm is None or rec is None:
+            return None
+        total, coef, bad = rec[:3].tolist()
+        return total, coef, bool(bad)
+
     def finish(self):
         """Join the index build started by the last step (it belongs to the timed region)."""
         if self._md_next is not None:
@@ -1247,14 +1279,28 @@ class SceneStep:
             f"; {self.batches_per_step} micro-batches (scenes) accumulated per optimizer step (training.py:436,458-460), "
             "voxels = all of them")
 
+    def _describe_clip(self):
+        if self.max_grad_norm is None:
+            return ""
+        from .executor import clip_launches
+        # (step(): the count-weighted step reduces explicitly; otherwise FlatParams decides between the packed and the fast path)
+        packed = self.weighting == "count" or self.flat.single_rank_step_packs()
+        n = [self.flat.flat.numel()] if packed else [p.numel() for p in self.flat.params]
+        return (f"; the gradient the update reads is clipped to the L2 norm {self.max_grad_norm:g} on the device before it "
+                "(SCN_OP_GRAD_NORM + SCN_OP_GRAD_SCALE in one executor call, scn_clip.hip: sum of squares in double, fixed order, "
+                f"torch's fp32 coefficient, no host wait; {clip_launches(n)} launches per step over "
+                + ("the packed flat gradient" if packed else f"the {len(n)} gradient tensors where autograd left them, one rank")
+                + "; `.grad_norm` reads the step's own record)")
+
     def _describe_optimizer(self):
         if self.adam is not None:
             a = self.adam
             return (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + Adam (the reference's optimizer, scannet_config/run.py:"
                     f"1449) on the flat parameter buffer, lr {self.lr:g}, betas ({a.betas[0]:g}, {a.betas[1]:g}), eps {a.eps:g}, "
-                    f"weight decay {a.weight_decay:g}: one fused update launch per <= 80 tensors")
+                    f"weight decay {a.weight_decay:g}: one fused update launch per <= 80 tensors" + self._describe_clip())
         return (f"; step = rulebooks + fwd + bwd (+ grad all-reduce) + plain SGD on the flat parameter buffer, lr {self.lr:g} "
-                "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)")
+                "(the reference trains with Adam, scannet_config/run.py:1449: three more passes over the buffer)"
+                + self._describe_clip())
 
     def _describe_tail(self):
         s = ""

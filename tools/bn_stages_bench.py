@@ -23,7 +23,7 @@ STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 WARMUP = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 NAMES = {1: "gemm_ident", 2: "conv_subm", 3: "conv_child", 4: "rules_child", 5: "rows2", 6: "wgrad_subm", 7: "wgrad2_subm",
          8: "wgrad_down", 9: "wgrad_up", 10: "wgrad_ident", 11: "colsum", 12: "add", 13: "cast", 14: "relu", 15: "relu_bwd",
-         16: "add_relu", 17: "bn_stats", 18: "bn_fwd", 19: "bn_bwd"}
+         16: "add_relu", 17: "bn_stats", 18: "bn_fwd", 19: "bn_bwd", 20: "grad_norm", 21: "grad_scale"}
 
 def _nodes(t):
     names, seen, todo = collections.Counter(), set(), [t.grad_fn]

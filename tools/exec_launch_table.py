@@ -14,7 +14,7 @@ from sparse_rcnn_amd.trainstep import SceneStep
 
 NAMES = {1: "gemm_ident", 2: "conv_subm", 3: "conv_child", 4: "rules_child", 5: "rows2", 6: "wgrad_subm", 7: "wgrad2_subm",
          8: "wgrad_down", 9: "wgrad_up", 10: "wgrad_ident", 11: "colsum", 12: "add", 13: "cast", 14: "relu", 15: "relu_bwd",
-         16: "add_relu", 17: "bn_stats", 18: "bn_fwd", 19: "bn_bwd"}
+         16: "add_relu", 17: "bn_stats", 18: "bn_fwd", 19: "bn_bwd", 20: "grad_norm", 21: "grad_scale"}
 wl = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 dt = sys.argv[2] if len(sys.argv) > 2 else "f32"
 job = SceneStep(wl, torch.device("cuda", 0), dtype=dt)
